@@ -13,6 +13,12 @@ itself (`torch.distributed.run`, a child process; this process touches no
 GPU) and forwards rank 0's line.  Prints ONE JSON line (rank 0).  value =
 blocks solved and applied per second, whole job; score gain per second is
 reported beside it.
+
+A plain run sets up, warms up, times `--steps` rounds and prints the line
+(`ms_per_step` = wall time of one timed round).  `--full` adds what the
+headline does not need: the CPU baselines (B1, the C port, scipy; timed before
+the GPU run) and the roofline's latency / LDS view (lone-block launches after
+it).  `--dump-outputs DIR` writes what the timed rounds returned (dump_outputs).
 """
 from __future__ import annotations
 
@@ -61,7 +67,15 @@ def parse():
                     help="budget of the CPU port / scipy baselines (rank 0, before the GPU run)")
     ap.add_argument("--b1-seconds", type=float, default=6.0,
                     help="budget per rank count of the reference-semantics baseline B1")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baselines out")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the CPU baselines (B1, the C port, scipy) before "
+                         "the GPU run and the latency / LDS view of the roofline (lone-block launches "
+                         "after it); a plain run only sets up, warms up, times the steps and prints")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the round loop returned for them as "
+                         "DIR/<name>.npy (rank 0): the assignment and every timed round's sums and score")
     ap.add_argument("--score-check-every", type=int, default=None,
                     help="0: rescore the whole state every round (the reference); K: the round's sums "
                          "from the block kernels' exact deltas (all-reduced at N > 1) with a full "
@@ -70,7 +84,12 @@ def parse():
                     help="test only: 'gloo' with --one-device rehearses N ranks on one GPU")
     ap.add_argument("--one-device", action="store_true",
                     help="test only: every rank uses cuda:0 (functional N>1 runs on a 1-GPU box)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_cpu_baseline = True
+    return args
 
 
 # --------------------------------------------------------------------------- launcher
@@ -402,6 +421,24 @@ def stored_traffic(knames, blocks: int, n: int = 256, mode: int = 0):
                             f"at {blocks} blocks of n = {n} per launch"}
 
 
+# --------------------------------------------------------------------------- outputs
+def dump_outputs(path: str, types, res) -> None:
+    """What a caller of the timed round loop holds after its last round, one
+    .npy per array: the gift type of every child (`types`, updated in place;
+    type ids are below 2^24, exact in float32) and the loop's result, i.e. the
+    exact integer (S_child, S_gift) and the score of every timed round and the
+    best score (float64; the sums stay far below 2^53).  About 4 MB at 1M
+    children.  The data, the block samples and the solver are seeded and
+    integer-exact, so two runs with the same arguments write the same bytes."""
+    os.makedirs(path, exist_ok=True)
+    h = res.history
+    np.save(os.path.join(path, "types.npy"), types.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "round_sums.npy"),
+            np.array([[st.s_child, st.s_gift] for st in h], dtype=np.float64).reshape(len(h), 2))
+    np.save(os.path.join(path, "round_scores.npy"), np.array([st.score for st in h], dtype=np.float64))
+    np.save(os.path.join(path, "best_score.npy"), np.array([res.best_score], dtype=np.float64))
+
+
 # --------------------------------------------------------------------------- main
 def main():
     args = parse()
@@ -535,6 +572,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, types, res)
     ev = eng.ev
     state = {"best": res.best_score}
     launches = len(ev)
@@ -552,10 +591,10 @@ def main():
     # latency / occupancy view from the Dijkstra steps of the TIMED launches:
     # the kernel is a serial chain of Dijkstra steps per block.  The lone
     # per-step latency is measured by re-running round 0's longest block
-    # alone (same kernel design, untimed region).
+    # alone (same kernel design, untimed region): launches of their own, --full only.
     latency = None
     lds = None
-    if my_blocks:
+    if args.full and my_blocks:
         st_all = steps_dev[:min(eng.calls, max_calls), :my_blocks].cpu().numpy().astype(np.int64)
         st = st_all[[k for _, _, k in ev if k < len(st_all)]]  # (the launches the events timed)
         bmax = int(st_all[0].argmax())

@@ -8,7 +8,10 @@ import os
 import sys
 
 
-def rank_main(rank, size, port, mode, n, rounds, seed, out):
+def rank_main(rank, size, port, mode, n, rounds, seed, out_dir):
+    """Leaves its result as out_dir/rank<rank>.pkl (read by the parent after
+    the join; no server process forked from the parent's HIP context)."""
+    import pickle
     here = os.path.dirname(os.path.abspath(__file__))
     root = os.path.dirname(here)
     for p in (os.path.join(root, "mpi-hungarian-method_amd"), here):
@@ -37,7 +40,9 @@ def rank_main(rank, size, port, mode, n, rounds, seed, out):
 
         res = run_rounds(Rec(ctx), types, mode=mode, n=n, seed=seed, max_rounds=rounds,
                          patience=100, world=World(rank, size, None))
-        out[rank] = (types.cpu().numpy(), [(st.s_child, st.s_gift) for st in res.history],
-                     [st.score for st in res.history], ctx.error_flags(), sums)
+        got = (types.cpu().numpy(), [(st.s_child, st.s_gift) for st in res.history],
+               [st.score for st in res.history], ctx.error_flags(), sums)
+        with open(os.path.join(out_dir, f"rank{rank}.pkl"), "wb") as f:
+            pickle.dump(got, f)
     finally:
         dist.destroy_process_group()

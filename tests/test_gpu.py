@@ -951,11 +951,12 @@ def test_santa_edge_block_sizes_vs_oracle(sh, ctx, full_data, mode, n, B):
 
 # --------------------------------------------------------------------------- config 4 on the HIP path
 @pytest.mark.parametrize("mode,rounds", [(0, 3), (1, 3), (2, 3)])
-def test_two_ranks_on_the_hip_path_equal_one_rank(sh, ctx, full_data, mode, rounds):
+def test_two_ranks_on_the_hip_path_equal_one_rank(sh, ctx, full_data, mode, rounds, tmp_path):
     """Config 4's sharding + exchange through GPUEngine: two ranks (one
     process each, both on cuda:0, gloo all-gather) run full rounds (3730
     singles / 78 twin blocks) and end with the single-rank run's type vector
     and every per-round (S_child, S_gift), bit for bit."""
+    import pickle
     import socket
 
     import torch.multiprocessing as mp
@@ -977,11 +978,12 @@ def test_two_ranks_on_the_hip_path_equal_one_rank(sh, ctx, full_data, mode, roun
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
-    mgr = mp.Manager()
-    out = mgr.dict()
-    mp.spawn(rank_main, args=(2, port, mode, 256, rounds, 41, out), nprocs=2, join=True)
+    # each rank leaves its result in a file (a Manager's server process would be
+    # forked from this process, which holds a HIP context and the runtime's threads)
+    mp.spawn(rank_main, args=(2, port, mode, 256, rounds, 41, str(tmp_path)), nprocs=2, join=True)
     for r in range(2):
-        t, sm, scores, flags, full = out[r]
+        with open(tmp_path / f"rank{r}.pkl", "rb") as f:
+            t, sm, scores, flags, full = pickle.load(f)
         assert flags == 0
         assert np.array_equal(t, want), f"rank {r} state differs"
         # two ranks take each round's sums from the delta all-reduce (§8(e));
@@ -1005,8 +1007,8 @@ def test_bench_launches_n_ranks(sh):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2",
-                        "--warmup", "1", "--one-device", "--dist-backend", "gloo", "--cpu-seconds", "1",
-                        "--b1-seconds", "1"],
+                        "--warmup", "1", "--one-device", "--dist-backend", "gloo", "--full",
+                        "--cpu-seconds", "1", "--b1-seconds", "1"],
                        capture_output=True, text=True, timeout=240, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

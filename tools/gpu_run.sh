@@ -26,12 +26,12 @@ for s in "$@"; do
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
     probe) step probe_sp 180 python -u tools/probe.py --reps 3 &&
            step probe_vt 180 python -u tools/probe.py --reps 3 --flags 32 ;;
-    bench) step bench 600 python -u bench.py ;;
-    bench_twins) step bench_twins 600 python -u bench.py --mode twins ;;
-    bench_triplets) step bench_triplets 600 python -u bench.py --mode triplets ;;
-    bench_n2000) step bench_n2000 600 python -u bench.py --n 2000 --steps 5 --warmup 1 --no-cpu-baseline ;;
-    bench_n2000cpu) step bench_n2000cpu 900 python -u bench.py --n 2000 --steps 5 --warmup 1 --b1-seconds 20 ;;
-    bench_twins3000) step bench_twins3000 900 python -u bench.py --mode twins --n 3000 --steps 5 --warmup 1 --b1-seconds 30 ;;
+    bench) step bench 600 python -u bench.py --full ;;
+    bench_twins) step bench_twins 600 python -u bench.py --full --mode twins ;;
+    bench_triplets) step bench_triplets 600 python -u bench.py --full --mode triplets ;;
+    bench_n2000) step bench_n2000 600 python -u bench.py --full --n 2000 --steps 5 --warmup 1 --no-cpu-baseline ;;
+    bench_n2000cpu) step bench_n2000cpu 900 python -u bench.py --full --n 2000 --steps 5 --warmup 1 --b1-seconds 20 ;;
+    bench_twins3000) step bench_twins3000 900 python -u bench.py --full --mode twins --n 3000 --steps 5 --warmup 1 --b1-seconds 30 ;;
     *) echo "unknown step $s"; exit 2 ;;
   esac
 done
