@@ -318,6 +318,37 @@ int lsap_solve_batched_hash(uint64_t seed, int64_t modulus, int n, int B,
                             void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Rectangular and ragged batches: B instances of nr x nc, 1 <= nr <= nc <=
+ * SH_MAX_N (scipy's SAP on wide input: one Dijkstra per row over nc columns).
+ * The four entries above are the case nr == nc, d_shape == NULL.
+ *   d_C     [B x nr x nc] row-major
+ *   d_col   int32 [B x nr]: the column of each row; -1 in every row of an
+ *           infeasible instance (f64) and in the padded rows of a ragged one
+ *   d_cost  [B] (nullable) sum of the chosen entries over the live rows
+ *   d_shape int32 [B x 2] (nullable): instance b solves the top-left
+ *           d_shape[2b] x d_shape[2b+1] corner of its padded nr x nc matrix
+ *           (row stride nc); nothing outside that corner is read, so the
+ *           padding may hold anything (NaN included).  An empty instance
+ *           (0 rows), and one whose shape is outside 0 <= nr_b <= nc_b <= nc,
+ *           nr_b <= nr, gets col = -1 and cost 0 and reads nothing.
+ *   hash:   C[b][i][j] = sh_hash_cost(seed, b, i, j) mod modulus -- the first
+ *           nr rows of the nc x nc matrix lsap_solve_batched_hash solves.
+ * Tall input (nr > nc) is not an ABI case: the caller solves the transpose and
+ * inverts the result, as scipy does internally (santa_hip.lsap does both).
+ * Checked on the host before any device call: SH_ERR_ARGS for nr < 1,
+ * nr > nc, nc > SH_MAX_N, B < 0, a null d_C or d_col with B > 0, or
+ * modulus <= 0.  B = 0 is a no-op.
+ * ------------------------------------------------------------------------ */
+int lsap_solve_batched_rect_i64(const int64_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                int32_t *d_col, int64_t *d_cost, unsigned flags, void *stream);
+int lsap_solve_batched_rect_i32(const int32_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                int32_t *d_col, int64_t *d_cost, unsigned flags, void *stream);
+int lsap_solve_batched_rect_f64(const double *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                int32_t *d_col, double *d_cost, unsigned flags, void *stream);
+int lsap_solve_batched_rect_hash(uint64_t seed, int64_t modulus, int nr, int nc, int B,
+                                 int32_t *d_col, int64_t *d_cost, unsigned flags, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Synthetic data of the Kaggle shape (host, deterministic, seeded counter
  * PRNG).  Wishlists: n_wish distinct gift types per child; good-kids: n_good
  * distinct children per gift; baseline: a feasible assignment (triplets and

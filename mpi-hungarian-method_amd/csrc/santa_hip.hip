@@ -89,11 +89,12 @@ __device__ __forceinline__ A pick(const A (&arr)[K], int k) {
 // ---------------------------------------------------------------------------
 // Shortest-augmenting-path core, scipy-exact.
 //
-// One wave64 owns one n x n instance.  Lane l owns columns j = l + 64k
-// (k < K), keeping spc/v/path/row4col/position-in-`remaining` in VGPRs; the
-// row duals u and col4row live in LDS.  Each Dijkstra step relaxes every
-// remaining column of row i, then a wave argmin picks the column scipy's
-// sequential scan would pick:
+// One wave64 owns one nr x n instance (nr <= n: nr rows over n columns, one
+// Dijkstra per row as scipy runs it on wide input).  Lane l owns columns
+// j = l + 64k (k < K), keeping spc/v/path/row4col/position-in-`remaining` in
+// VGPRs; the row duals u and col4row (nr entries each) live in LDS.  Each
+// Dijkstra step relaxes every remaining column of row i, then a wave argmin
+// picks the column scipy's sequential scan would pick:
 //   min spc; ties -> the LAST unassigned column in `remaining` order, else the
 //   FIRST column at the minimum.
 // The tie key is a 32-bit word (class, position key, row4col, column), so the
@@ -102,10 +103,12 @@ __device__ __forceinline__ A pick(const A (&arr)[K], int k) {
 //
 // Loader::load(i, T c[K]) returns row i's costs of this lane's columns.
 // On return col4row[i] (LDS) holds the assignment.  Returns 0 or -1
-// (infeasible: only possible for float64 with +inf entries).
+// (infeasible: only possible for float64 with +inf entries; with nr < n a
+// Dijkstra can run dry -- no finite path length left -- while columns are
+// still unassigned, which is the same test).
 // ---------------------------------------------------------------------------
 template <int K, typename T, typename Loader>
-__device__ int sap_solve(const int n, Loader &ld, T *__restrict__ u_l,
+__device__ int sap_solve(const int nr, const int n, Loader &ld, T *__restrict__ u_l,
                          int16_t *__restrict__ c4r_l, int64_t &steps_out) {
   const int lane = threadIdx.x;
   const T INF = VT<T>::inf();
@@ -118,7 +121,7 @@ __device__ int sap_solve(const int n, Loader &ld, T *__restrict__ u_l,
     path[k] = -1;
   }
   int64_t steps = 0;
-  for (int cur = 0; cur < n; ++cur) {
+  for (int cur = 0; cur < nr; ++cur) {
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       const int j = lane + WAVE * k;
@@ -283,7 +286,9 @@ __device__ __forceinline__ int64_t single_cost(uint32_t code, int nw1, int64_t E
 // ---------------------------------------------------------------------------
 // int64 multi-wave solver (identical decisions to the algorithm above).
 //
-// One workgroup of NW waves owns one n x n instance.  Thread (wave w, lane l)
+// One workgroup of NW waves owns one nr x n instance (nr = n; with RECT
+// nr <= n rows over n columns -- only the count of Dijkstras differs,
+// everything held per column spans n).  Thread (wave w, lane l)
 // owns columns j = w*64K + k*64 + l (k < K), keeping spc / -v / path /
 // position-in-`remaining` / row4col of its columns in VGPRs, so every SIMD of
 // the CU relaxes a quarter of the row per Dijkstra step.  The argmin of a
@@ -403,8 +408,8 @@ __device__ __forceinline__ uint32_t lds_addr(const void *p) {
 }
 
 struct SolveLds {
-  int64_t *u;       // [n]   row duals
-  int16_t *c4r;     // [n]   col4row (the result)
+  int64_t *u;       // [n]   row duals            (RECT: [nr])
+  int16_t *c4r;     // [n]   col4row (the result) (RECT: [nr])
   int16_t *r4c;     // [n]   row4col
   int16_t *path;    // [n]   path dump of the visited columns (sap_solve_mw: scipy's
                     //       `remaining` during a Dijkstra's steps, see there)
@@ -463,9 +468,14 @@ __device__ __forceinline__ int mw_col(int w, int k, int lane) {
 // mask rm goes to ~0 (a removed column's relaxation r >= minVal >= its spc
 // never updates it; its key's high word is ~0), the mover's position bits
 // flip.  The sink step needs none of it.
-template <int NW, int K, typename Loader, int FB = 10, typename... LA>
+template <int NW, int K, typename Loader, int FB = 10, bool RECT = false, typename... LA>
 __device__ __forceinline__ void sap_solve_mw(const int n, const Loader &ld, const SolveLds &S, int64_t &steps_out,
                              int &fallbacks, const bool exact, const LA &...la) {
+  // RECT (the generic LSAP kernels only; a flag, so that the square
+  // instantiations of the Santa kernels compile as they always did): ld.nr
+  // rows (S.u, S.c4r) over n >= ld.nr columns (S.r4c, S.path, `remaining`)
+  int nr = n;
+  if constexpr (RECT) nr = ld.nr;
   // key fields: FB bits of position and of row/column (n <= 2^FB), 1 class bit
   constexpr int LOB = 2 * FB + 1;
   constexpr uint32_t FM = (1u << FB) - 1u;
@@ -500,7 +510,7 @@ __device__ __forceinline__ void sap_solve_mw(const int n, const Loader &ld, cons
   int par = 0;  // rotating step-argmin word (0..2)
   if (NW > 1 && tid < 3) S.red[tid] = ~0ull;
   __syncthreads();
-  for (int cur = 0; cur < n; ++cur) {
+  for (int cur = 0; cur < nr; ++cur) {
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       const int j = mw_col<NW, K>(w, k, lane);
@@ -1205,10 +1215,12 @@ __device__ __forceinline__ int64_t twin_lut_cost(uint32_t idx, int64_t E) {
 template <int NW, int K, typename S>
 struct GlobalLoader {  // generic LSAP: rows streamed from global memory
   const S *base;
-  int n;
+  int n;   // live columns: j >= n is never read
+  int ld;  // row stride (elements)
+  int nr;  // live rows (sap_solve_mw<.., RECT>)
   __device__ __forceinline__ void load(int i, int64_t (&c)[K]) const {
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const S *row = base + (size_t)i * n;
+    const S *row = base + (size_t)i * ld;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       const int j = mw_col<NW, K>(w, k, lane);
@@ -1218,11 +1230,12 @@ struct GlobalLoader {  // generic LSAP: rows streamed from global memory
 };
 
 template <int NW, int K>
-struct HashLoader {
+struct HashLoader {  // (generated per (b, i, j): no stride, n = live columns)
   uint64_t seed;
   int64_t mod;
   uint64_t b;
   int n;
+  int nr;  // live rows (sap_solve_mw<.., RECT>)
   __device__ __forceinline__ void load(int i, int64_t (&c)[K]) const {
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
@@ -5109,9 +5122,10 @@ __global__ __launch_bounds__(NW * WAVE) void santa_lb_kernel(SantaArgs a) {
 template <int K, typename S>
 struct GlobalLoaderF64 {
   const S *base;
-  int n;
+  int n;   // live columns: j >= n is never read
+  int ld;  // row stride (elements)
   __device__ __forceinline__ void load(int i, double (&c)[K]) const {
-    const S *row = base + (size_t)i * n;
+    const S *row = base + (size_t)i * ld;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       const int j = threadIdx.x + WAVE * k;
@@ -5120,46 +5134,77 @@ struct GlobalLoaderF64 {
   }
 };
 
-template <int NW, int K, typename S, bool HASH>
+// Instance b is the padded NR x NC matrix at C + b * NR * NC (row stride NC);
+// it solves the top-left nr x nc corner, (nr, nc) = (NR, NC) or, with `shape`,
+// (shape[2b], shape[2b+1]) -- wave-uniform, so it sits in SGPRs.  Rows
+// i >= nr get col = -1; an empty instance (nr == 0) or a shape outside
+// 0 <= nr <= nc <= NC, nr <= NR reads nothing and writes -1s and cost 0.
+__device__ __forceinline__ bool lsap_shape(const int32_t *shape, int b, int NR, int NC, int &nr, int &nc) {
+  nr = NR;
+  nc = NC;
+  if (shape) {
+    nr = __builtin_amdgcn_readfirstlane(shape[2 * (size_t)b]);
+    nc = __builtin_amdgcn_readfirstlane(shape[2 * (size_t)b + 1]);
+  }
+  return nr >= 1 && nr <= nc && nc <= NC && nr <= NR;
+}
+
+// RECT = false is the square launch (NR == NC, no shapes): one size throughout,
+// the code the square entries always ran (A/B profiles/lsap_rect_ab.jsonl: the
+// general form cost 512 x 512 instances 0.8 %).
+template <int NW, int K, typename S, bool HASH, bool RECT>
 __global__ __launch_bounds__(NW * WAVE) void lsap_i64_kernel(const S *C, uint64_t seed, int64_t mod,
-                                                             int n, int32_t *col, int64_t *cost,
+                                                             int NR_, int NC, const int32_t *shape,
+                                                             int32_t *col, int64_t *cost,
                                                              int32_t *fb, unsigned flags) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int b = blockIdx.x;
   const int tid = threadIdx.x;
+  const int NR = RECT ? NR_ : NC;
+  int nr = NC, n = NC;  // live rows and columns
+  if constexpr (RECT) {
+    if (!lsap_shape(shape, b, NR, NC, nr, n)) {
+      for (int i = tid; i < NR; i += NW * WAVE) col[(size_t)b * NR + i] = -1;
+      if (tid == 0 && cost) cost[b] = 0;
+      return;
+    }
+  }
   size_t off = 0;
   SolveLds Sl;
-  Sl.u = (int64_t *)(smem + off);    off += r16((size_t)n * 8);
-  Sl.c4r = (int16_t *)(smem + off);  off += r16((size_t)n * 2);
+  Sl.u = (int64_t *)(smem + off);    off += r16((size_t)nr * 8);
+  Sl.c4r = (int16_t *)(smem + off);  off += r16((size_t)nr * 2);
   Sl.r4c = (int16_t *)(smem + off);  off += r16((size_t)n * 2);
   Sl.path = (int16_t *)(smem + off); off += r16((size_t)n * 2);
   Sl.red = (uint64_t *)(smem + off); off += r16((size_t)4 * NW * 8);
   int64_t *part = (int64_t *)(smem + off);
   for (int i = tid; i < n; i += NW * WAVE) {
-    Sl.u[i] = 0;
-    Sl.c4r[i] = -1;
+    if (i < nr) {
+      Sl.u[i] = 0;
+      Sl.c4r[i] = -1;
+    }
     Sl.r4c[i] = -1;
   }
   __syncthreads();
   int64_t steps = 0;
   int fallbacks = 0;
   const bool exact = (flags & SH_FLAG_EXACT_ARGMIN) != 0;
+  const size_t base = (size_t)b * NR * NC;
   if constexpr (HASH) {
-    const HashLoader<NW, K> ld{seed, mod, (uint64_t)b, n};
-    sap_solve_mw<NW, K>(n, ld, Sl, steps, fallbacks, exact);
+    const HashLoader<NW, K> ld{seed, mod, (uint64_t)b, n, nr};
+    sap_solve_mw<NW, K, HashLoader<NW, K>, 10, RECT>(n, ld, Sl, steps, fallbacks, exact);
   } else {
-    const GlobalLoader<NW, K, S> ld{C + (size_t)b * n * n, n};
-    sap_solve_mw<NW, K>(n, ld, Sl, steps, fallbacks, exact);
+    const GlobalLoader<NW, K, S> ld{C + base, n, NC, nr};
+    sap_solve_mw<NW, K, GlobalLoader<NW, K, S>, 10, RECT>(n, ld, Sl, steps, fallbacks, exact);
   }
   int64_t acc = 0;
-  for (int i = tid; i < n; i += NW * WAVE) {
-    const int cidx = Sl.c4r[i];
-    col[(size_t)b * n + i] = cidx;
-    if (cost) {
+  for (int i = tid; i < NR; i += NW * WAVE) {
+    const int cidx = (i < nr) ? Sl.c4r[i] : -1;
+    col[(size_t)b * NR + i] = cidx;
+    if (cost && i < nr) {
       if constexpr (HASH)
         acc += (int64_t)(sh_hash_cost(seed, (uint64_t)b, (uint64_t)i, (uint64_t)cidx) % (uint64_t)mod);
       else
-        acc += (int64_t)C[(size_t)b * n * n + (size_t)i * n + cidx];
+        acc += (int64_t)C[base + (size_t)i * NC + cidx];
     }
   }
   acc = wave_sum_i64(acc);
@@ -5174,27 +5219,36 @@ __global__ __launch_bounds__(NW * WAVE) void lsap_i64_kernel(const S *C, uint64_
 }
 
 template <int K>
-__global__ __launch_bounds__(WAVE) void lsap_f64_kernel(const double *C, int n, int32_t *col,
+__global__ __launch_bounds__(WAVE) void lsap_f64_kernel(const double *C, int NR, int NC,
+                                                        const int32_t *shape, int32_t *col,
                                                         double *cost) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int b = blockIdx.x;
   const int lane = threadIdx.x;
+  int nr, n;  // live rows and columns (see lsap_i64_kernel)
+  if (!lsap_shape(shape, b, NR, NC, nr, n)) {
+    for (int i = lane; i < NR; i += WAVE) col[(size_t)b * NR + i] = -1;
+    if (lane == 0 && cost) cost[b] = 0;
+    return;
+  }
   double *u_l = (double *)smem;
-  int16_t *c4r_l = (int16_t *)(smem + r16((size_t)n * sizeof(double)));
-  for (int i = lane; i < n; i += WAVE) {
+  int16_t *c4r_l = (int16_t *)(smem + r16((size_t)nr * sizeof(double)));
+  for (int i = lane; i < nr; i += WAVE) {
     u_l[i] = 0;
     c4r_l[i] = -1;
   }
   __syncthreads();
   int64_t steps = 0;
-  GlobalLoaderF64<K, double> ld{C + (size_t)b * n * n, n};
-  const int st = sap_solve<K, double>(n, ld, u_l, c4r_l, steps);
+  const size_t base = (size_t)b * NR * NC;
+  GlobalLoaderF64<K, double> ld{C + base, n, NC};
+  const int st = sap_solve<K, double>(nr, n, ld, u_l, c4r_l, steps);
   __syncthreads();
   double acc = 0;
-  for (int i = lane; i < n; i += WAVE) {
-    const int cidx = (st == 0) ? c4r_l[i] : -1;
-    col[(size_t)b * n + i] = cidx;
-    if (st == 0 && cost) acc += C[(size_t)b * n * n + (size_t)i * n + cidx];
+  for (int i = lane; i < NR; i += WAVE) {
+    const bool live = st == 0 && i < nr;
+    const int cidx = live ? c4r_l[i] : -1;
+    col[(size_t)b * NR + i] = cidx;
+    if (live && cost) acc += C[base + (size_t)i * NC + cidx];
   }
   if (cost) {
     // wave sum in a fixed order (deterministic); it differs from numpy's sum
@@ -6305,22 +6359,33 @@ int sh_unpack_types(int16_t *d_types, const int32_t *d_rows, int count, const in
 }  // extern "C"
 
 namespace {
-int check_lsap_args(int n, int B, const int32_t *col) {
-  if (n <= 0 || n > SH_MAX_N) return fail(SH_ERR_ARGS, "n must be in [1, 1024]");
+// nr x nc instances (the square entries: nr == nc == n); host-side only.
+int check_lsap_args(int nr, int nc, int B, const int32_t *col) {
+  if (nr < 1 || nc > SH_MAX_N) return fail(SH_ERR_ARGS, "sizes must be in [1, 1024]");
+  if (nr > nc) return fail(SH_ERR_ARGS, "nr > nc: transpose tall input (as scipy does) and solve that");
   if (B < 0) return fail(SH_ERR_ARGS, "B < 0");
   if (!col && B > 0) return fail(SH_ERR_ARGS, "null col");
   return SH_OK;
 }
 
+// The launch configuration follows the column slots nc (a thread owns K of
+// them, as in the square case); the LDS size the rows and columns.
 template <typename S, bool HASH>
-int launch_lsap_i64(const S *C, uint64_t seed, int64_t mod, int n, int B, int32_t *col,
-                    int64_t *cost, unsigned flags, hipStream_t s) {
-  const int rc = check_lsap_args(n, B, col);
+int launch_lsap_i64(const S *C, uint64_t seed, int64_t mod, int nr, int n, int B, const int32_t *shape,
+                    int32_t *col, int64_t *cost, unsigned flags, hipStream_t s) {
+  const int rc = check_lsap_args(nr, n, B, col);
   if (rc || B == 0) return rc;
-  const size_t lds = r16((size_t)n * 8) + 3 * r16((size_t)n * 2) + r16((size_t)4 * 4 * 8) + 64;
-#define L_(NWW, KK)                                                                            \
-  hipLaunchKernelGGL((lsap_i64_kernel<NWW, KK, S, HASH>), dim3(B), dim3(NWW * WAVE), lds, s, C, \
-                     seed, mod, n, col, cost, (int32_t *)nullptr, flags)
+  const size_t lds = r16((size_t)nr * 8) + r16((size_t)nr * 2) + 2 * r16((size_t)n * 2) +
+                     r16((size_t)4 * 4 * 8) + 64;
+  const bool rect = nr != n || shape;
+#define L__(NWW, KK, RR)                                                                            \
+  hipLaunchKernelGGL((lsap_i64_kernel<NWW, KK, S, HASH, RR>), dim3(B), dim3(NWW * WAVE), lds, s, C, \
+                     seed, mod, nr, n, shape, col, cost, (int32_t *)nullptr, flags)
+#define L_(NWW, KK)                \
+  do {                             \
+    if (rect) L__(NWW, KK, true);  \
+    else L__(NWW, KK, false);      \
+  } while (0)
   // a batch that fills the chip many times over runs one wave per instance
   // with several columns per thread (fewer waves per block, more blocks per
   // CU: the large-block kernel's lesson): n <= 128 from 4096 instances
@@ -6334,15 +6399,18 @@ int launch_lsap_i64(const S *C, uint64_t seed, int64_t mod, int n, int B, int32_
   else if (n <= 512) L_(4, 2);
   else L_(4, 4);
 #undef L_
+#undef L__
   HIP_TRY(hipGetLastError());
   return SH_OK;
 }
 
-int launch_lsap_f64(const double *C, int n, int B, int32_t *col, double *cost, hipStream_t s) {
-  const int rc = check_lsap_args(n, B, col);
+int launch_lsap_f64(const double *C, int nr, int n, int B, const int32_t *shape, int32_t *col,
+                    double *cost, hipStream_t s) {
+  const int rc = check_lsap_args(nr, n, B, col);
   if (rc || B == 0) return rc;
-  const size_t lds = r16((size_t)n * 8) + r16((size_t)n * 2);
-#define L_(KK) hipLaunchKernelGGL((lsap_f64_kernel<KK>), dim3(B), dim3(WAVE), lds, s, C, n, col, cost)
+  const size_t lds = r16((size_t)nr * 8) + r16((size_t)nr * 2);
+#define L_(KK) \
+  hipLaunchKernelGGL((lsap_f64_kernel<KK>), dim3(B), dim3(WAVE), lds, s, C, nr, n, shape, col, cost)
   switch (pick_k(n)) {
     case 1: L_(1); break;
     case 2: L_(2); break;
@@ -6360,28 +6428,52 @@ extern "C" {
 
 int lsap_solve_batched_i64(const int64_t *d_C, int n, int B, int32_t *d_col, int64_t *d_cost,
                            unsigned flags, void *stream) {
-  if (!d_C && B > 0) return fail(SH_ERR_ARGS, "null C");
-  return launch_lsap_i64<int64_t, false>(d_C, 0, 1, n, B, d_col, d_cost, flags, (hipStream_t)stream);
+  return lsap_solve_batched_rect_i64(d_C, n, n, B, nullptr, d_col, d_cost, flags, stream);
 }
 
 int lsap_solve_batched_i32(const int32_t *d_C, int n, int B, int32_t *d_col, int64_t *d_cost,
                            unsigned flags, void *stream) {
-  if (!d_C && B > 0) return fail(SH_ERR_ARGS, "null C");
-  return launch_lsap_i64<int32_t, false>(d_C, 0, 1, n, B, d_col, d_cost, flags, (hipStream_t)stream);
+  return lsap_solve_batched_rect_i32(d_C, n, n, B, nullptr, d_col, d_cost, flags, stream);
 }
 
 int lsap_solve_batched_f64(const double *d_C, int n, int B, int32_t *d_col, double *d_cost,
                            unsigned flags, void *stream) {
-  if (!d_C && B > 0) return fail(SH_ERR_ARGS, "null C");
-  (void)flags;
-  return launch_lsap_f64(d_C, n, B, d_col, d_cost, (hipStream_t)stream);
+  return lsap_solve_batched_rect_f64(d_C, n, n, B, nullptr, d_col, d_cost, flags, stream);
 }
 
 int lsap_solve_batched_hash(uint64_t seed, int64_t modulus, int n, int B, int32_t *d_col,
                             int64_t *d_cost, unsigned flags, void *stream) {
+  return lsap_solve_batched_rect_hash(seed, modulus, n, n, B, d_col, d_cost, flags, stream);
+}
+
+// nr x nc instances, nr <= nc (the square entries above: nr == nc, no shapes).
+// Every check here is on the host and precedes the first device call.
+int lsap_solve_batched_rect_i64(const int64_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                int32_t *d_col, int64_t *d_cost, unsigned flags, void *stream) {
+  if (!d_C && B > 0) return fail(SH_ERR_ARGS, "null C");
+  return launch_lsap_i64<int64_t, false>(d_C, 0, 1, nr, nc, B, d_shape, d_col, d_cost, flags,
+                                         (hipStream_t)stream);
+}
+
+int lsap_solve_batched_rect_i32(const int32_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                int32_t *d_col, int64_t *d_cost, unsigned flags, void *stream) {
+  if (!d_C && B > 0) return fail(SH_ERR_ARGS, "null C");
+  return launch_lsap_i64<int32_t, false>(d_C, 0, 1, nr, nc, B, d_shape, d_col, d_cost, flags,
+                                         (hipStream_t)stream);
+}
+
+int lsap_solve_batched_rect_f64(const double *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                int32_t *d_col, double *d_cost, unsigned flags, void *stream) {
+  if (!d_C && B > 0) return fail(SH_ERR_ARGS, "null C");
+  (void)flags;
+  return launch_lsap_f64(d_C, nr, nc, B, d_shape, d_col, d_cost, (hipStream_t)stream);
+}
+
+int lsap_solve_batched_rect_hash(uint64_t seed, int64_t modulus, int nr, int nc, int B,
+                                 int32_t *d_col, int64_t *d_cost, unsigned flags, void *stream) {
   if (modulus <= 0) return fail(SH_ERR_ARGS, "modulus must be > 0");
-  return launch_lsap_i64<int64_t, true>(nullptr, seed, modulus, n, B, d_col, d_cost, flags,
-                                        (hipStream_t)stream);
+  return launch_lsap_i64<int64_t, true>(nullptr, seed, modulus, nr, nc, B, nullptr, d_col, d_cost,
+                                        flags, (hipStream_t)stream);
 }
 
 }  // extern "C"

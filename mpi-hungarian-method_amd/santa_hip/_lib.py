@@ -102,6 +102,10 @@ SIGNATURES = {
     "lsap_solve_batched_i32": (_I, [_P, _I, _I, _P, _P, _U, _P]),
     "lsap_solve_batched_f64": (_I, [_P, _I, _I, _P, _P, _U, _P]),
     "lsap_solve_batched_hash": (_I, [_U64, _I64, _I, _I, _P, _P, _U, _P]),
+    "lsap_solve_batched_rect_i64": (_I, [_P, _I, _I, _I, _P, _P, _P, _U, _P]),
+    "lsap_solve_batched_rect_i32": (_I, [_P, _I, _I, _I, _P, _P, _P, _U, _P]),
+    "lsap_solve_batched_rect_f64": (_I, [_P, _I, _I, _I, _P, _P, _P, _U, _P]),
+    "lsap_solve_batched_rect_hash": (_I, [_U64, _I64, _I, _I, _I, _P, _P, _U, _P]),
     "sh_gen_synthetic": (_I, [_U64, _I, _I, _I, _I, _I, _P, _P, _P]),
 }
 

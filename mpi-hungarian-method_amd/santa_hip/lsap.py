@@ -1,12 +1,13 @@
 """GPU linear_sum_assignment — the inner seam of the reference.
 
 `linear_sum_assignment(C)` is scipy's call at mpi_single.py:101 and
-mpi_twins.py:104; this module mirrors its surface for square matrices
-(the only shape the reference produces): same return value (row_ind,
-col_ind) as int64 numpy arrays, same ValueError on NaN / -inf / infeasible
-input.  Solves run on the GPU through the C-ABI batched solvers; float64
-input is replayed with scipy's own float64 arithmetic, so even the
-permutation on ties is scipy's.
+mpi_twins.py:104; this module mirrors its surface for any shape (the
+reference produces square blocks; wide, tall and ragged batches are the
+solver's own surface): same return value (row_ind, col_ind) as int64 numpy
+arrays, same ValueError on NaN / -inf / infeasible input.  Solves run on the
+GPU through the C-ABI batched solvers; float64 input is replayed with scipy's
+own float64 arithmetic, so even the permutation on ties is scipy's.  Tall
+input is solved as its transpose and inverted, as scipy does internally.
 """
 from __future__ import annotations
 
@@ -27,48 +28,156 @@ INT64_COST_LIMIT = 1 << 50  # |C| bound that keeps every SAP value < 2^62 (n <= 
 EXACT_INT_LIMIT = 1 << 53   # float64 holds every integer below this exactly
 
 
-def solve_batched(C: torch.Tensor, with_cost: bool = True, flags: int = 0):
-    """C: device tensor [B, n, n] (int64 / int32 / float64) -> (col int32 [B, n], cost [B]).
+# ---------------------------------------------------------------------------
+# Host-only pieces (pure: no GPU, no library call).
+# ---------------------------------------------------------------------------
+def check_shapes(shapes, B: int, NR: int, NC: int) -> np.ndarray:
+    """The per-instance shapes of a padded [B, NR, NC] batch as int32 [B, 2]
+    on the host; ValueError unless 0 <= nr_b <= NR and nr_b <= nc_b <= NC."""
+    if isinstance(shapes, torch.Tensor):
+        shapes = shapes.detach().cpu().numpy()
+    sh = np.asarray(shapes)
+    if sh.shape != (B, 2) or not np.issubdtype(sh.dtype, np.integer):
+        raise ValueError(f"shapes must be an integer [B, 2] = [{B}, 2] array, got {sh.dtype} {sh.shape}")
+    sh = sh.astype(np.int64)
+    nr, nc = sh[:, 0], sh[:, 1]
+    bad = np.flatnonzero((nr < 0) | (nr > NR) | (nc < 0) | (nc > NC))
+    if bad.size:
+        b = int(bad[0])
+        raise ValueError(f"shapes[{b}] = ({int(nr[b])}, {int(nc[b])}) is outside the padded "
+                         f"[{NR}, {NC}] matrix")
+    tall = np.flatnonzero(nr > nc)
+    if tall.size:
+        b = int(tall[0])
+        raise ValueError(f"shapes[{b}] = ({int(nr[b])}, {int(nc[b])}) is tall (nr > nc): "
+                         "transpose the batch so that every instance has nr <= nc")
+    return np.ascontiguousarray(sh, dtype=np.int32)
 
-    Infeasible blocks get col = -1 (float64 with +inf only).  int64 costs
-    must satisfy |C| < 2^50 (checked on the device)."""
-    require_gpu()
-    if C.dim() != 3 or C.shape[1] != C.shape[2]:
-        raise ValueError("expected [B, n, n]")
-    C = C.contiguous()
-    B, n, _ = C.shape
+
+def invert_tall(col_t: torch.Tensor, nr: int) -> torch.Tensor:
+    """col_t int32 [B, nc]: the solution of the transposed (wide) batch, i.e.
+    the row of the tall matrix that each of its nc columns took (-1: none).
+    Returns the tall batch's per-row columns, int32 [B, nr], -1 for the
+    nr - nc rows left out (and everywhere for an infeasible instance)."""
+    B, nc = col_t.shape
+    out = torch.full((B, nr + 1), -1, dtype=torch.int32, device=col_t.device)
+    idx = torch.where(col_t >= 0, col_t, torch.full_like(col_t, nr)).long()  # (-1 -> the spare slot)
+    src = torch.arange(nc, dtype=torch.int32, device=col_t.device).expand(B, nc)
+    out.scatter_(1, idx, src)
+    return out[:, :nr].contiguous()
+
+
+def tall_result(col_t):
+    """scipy's (row_ind, col_ind) of a tall matrix from the solution col_t of
+    its transpose: rows sorted ascending, each with its column."""
+    col_t = np.asarray(col_t, dtype=np.int64)
+    order = np.argsort(col_t)
+    return col_t[order], order.astype(np.int64)
+
+
+def exact_int64_route(C: np.ndarray) -> bool:
+    """Whether an integer matrix is solved in exact int64: scipy solves in
+    float64, and the int64 solve makes scipy's decisions only while every
+    value scipy forms is an integer below 2^53 (no float64 rounding).  Duals
+    and path lengths stay within a few max(nr, nc) * max|C|, so
+    4 (max(nr, nc) + 1) max|C| < 2^53 is a safe bound.  It is taken in Python
+    ints before any negation (np.abs / -C wrap at INT64_MIN)."""
+    if not np.issubdtype(C.dtype, np.integer):
+        return False
+    if C.size == 0:
+        return True
+    return 4 * (max(C.shape) + 1) * max(int(C.max()), -int(C.min())) < EXACT_INT_LIMIT
+
+
+# ---------------------------------------------------------------------------
+def _solve_wide(C: torch.Tensor, with_cost: bool, fl: int, shape_dev):
+    """C contiguous [B, nr, nc], 1 <= nr <= nc (the square C-ABI entries are
+    the rect ones with nr == nc and no shapes)."""
+    B, nr, nc = C.shape
     dev = C.device
-    col = torch.empty((B, n), dtype=torch.int32, device=dev)
+    col = torch.empty((B, nr), dtype=torch.int32, device=dev)
     s = current_stream_handle(dev)
     L = _lib.lib()
-    fl = _lib.SH_COMPAT_TIEBREAK | flags
     if C.dtype == torch.int64:
         # (max / -min as Python ints: abs() wraps at INT64_MIN)
         if C.numel() and max(int(C.max()), -int(C.min())) >= INT64_COST_LIMIT:
             raise ValueError("int64 costs must satisfy |C| < 2**50; pass float64 instead")
         cost = torch.empty(B, dtype=torch.int64, device=dev) if with_cost else None
-        rc = L.lsap_solve_batched_i64(_p(C), n, B, _p(col), _p(cost), fl, s)
+        rc = L.lsap_solve_batched_rect_i64(_p(C), nr, nc, B, _p(shape_dev), _p(col), _p(cost), fl, s)
     elif C.dtype == torch.int32:
         cost = torch.empty(B, dtype=torch.int64, device=dev) if with_cost else None
-        rc = L.lsap_solve_batched_i32(_p(C), n, B, _p(col), _p(cost), fl, s)
+        rc = L.lsap_solve_batched_rect_i32(_p(C), nr, nc, B, _p(shape_dev), _p(col), _p(cost), fl, s)
     elif C.dtype == torch.float64:
         cost = torch.empty(B, dtype=torch.float64, device=dev) if with_cost else None
-        rc = L.lsap_solve_batched_f64(_p(C), n, B, _p(col), _p(cost), fl, s)
+        rc = L.lsap_solve_batched_rect_f64(_p(C), nr, nc, B, _p(shape_dev), _p(col), _p(cost), fl, s)
     else:
         raise TypeError(f"unsupported dtype {C.dtype}")
     _lib.check(rc, "lsap_solve_batched")
     return col, cost
 
 
-def solve_hash(seed: int, modulus: int, n: int, B: int, device: int | str = 0, with_cost: bool = True):
-    """Solve B device-generated n x n matrices (sampler.hash_matrix on the host)."""
+def solve_batched(C: torch.Tensor, with_cost: bool = True, flags: int = 0, shapes=None,
+                  maximize: bool = False):
+    """C: device tensor [B, NR, NC] (int64 / int32 / float64) -> (col int32 [B, NR], cost [B]).
+
+    col[b, i] is the column of row i, -1 for a row without one: the NR - NC
+    rows scipy leaves out of a tall instance, every row of an infeasible
+    instance (float64 with +inf only), and the padded rows of a ragged one.
+    `shapes` ([B, 2] integers, host or device) makes the batch ragged:
+    instance b is the top-left shapes[b] = (nr_b, nc_b) corner of its padded
+    matrix, 0 <= nr_b <= NR, nr_b <= nc_b <= NC; the padding is never read.
+    Tall batches (NR > NC) are solved as their transpose and inverted on the
+    device.  maximize negates the matrix (and the cost back).  int64 costs
+    must satisfy |C| < 2^50 over the whole padded tensor (checked on the
+    device)."""
+    require_gpu()
+    if C.dim() != 3:
+        raise ValueError("expected [B, NR, NC]")
+    B, NR, NC = C.shape
+    if max(NR, NC) > _lib.SH_MAX_N:
+        raise ValueError(f"max(NR, NC) = {max(NR, NC)} > {_lib.SH_MAX_N}")
+    if C.dtype not in (torch.int64, torch.int32, torch.float64):
+        raise TypeError(f"unsupported dtype {C.dtype}")
+    dev = C.device
+    shape_dev = None
+    if shapes is not None:
+        if NR > NC:
+            raise ValueError(f"a ragged batch must be padded wide, got [{NR}, {NC}]: "
+                             "transpose the batch so that every instance has nr <= nc")
+        shape_dev = torch.from_numpy(check_shapes(shapes, B, NR, NC)).to(dev)
+    if B == 0 or NR == 0 or NC == 0:
+        cdt = torch.float64 if C.dtype == torch.float64 else torch.int64
+        return (torch.full((B, NR), -1, dtype=torch.int32, device=dev),
+                torch.zeros(B, dtype=cdt, device=dev) if with_cost else None)
+    if maximize:  # (int32: -INT32_MIN wraps, so widen; the int64 bound covers int64)
+        C = -(C.to(torch.int64) if C.dtype == torch.int32 else C)
+    fl = _lib.SH_COMPAT_TIEBREAK | flags
+    if NR > NC:
+        col_t, cost = _solve_wide(C.transpose(1, 2).contiguous(), with_cost, fl, None)
+        col = invert_tall(col_t, NR)
+    else:
+        col, cost = _solve_wide(C.contiguous(), with_cost, fl, shape_dev)
+    if maximize and cost is not None:
+        cost = -cost
+    return col, cost
+
+
+def solve_hash(seed: int, modulus: int, n: int, B: int, device: int | str = 0, with_cost: bool = True,
+               nr: int | None = None):
+    """Solve B device-generated n x n matrices (sampler.hash_matrix on the host);
+    with nr, the first nr rows of each (an nr x n instance, nr <= n)."""
     require_gpu()
     dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-    col = torch.empty((B, n), dtype=torch.int32, device=dev)
+    col = torch.empty((B, n if nr is None else nr), dtype=torch.int32, device=dev)
     cost = torch.empty(B, dtype=torch.int64, device=dev) if with_cost else None
-    rc = _lib.lib().lsap_solve_batched_hash(ctypes.c_uint64(seed), ctypes.c_int64(modulus), n, B,
-                                            _p(col), _p(cost), _lib.SH_COMPAT_TIEBREAK,
-                                            current_stream_handle(dev))
+    L = _lib.lib()
+    s = current_stream_handle(dev)
+    if nr is None:
+        rc = L.lsap_solve_batched_hash(ctypes.c_uint64(seed), ctypes.c_int64(modulus), n, B,
+                                       _p(col), _p(cost), _lib.SH_COMPAT_TIEBREAK, s)
+    else:
+        rc = L.lsap_solve_batched_rect_hash(ctypes.c_uint64(seed), ctypes.c_int64(modulus), nr, n, B,
+                                            _p(col), _p(cost), _lib.SH_COMPAT_TIEBREAK, s)
     _lib.check(rc, "lsap_solve_batched_hash")
     return col, cost
 
@@ -76,20 +185,20 @@ def solve_hash(seed: int, modulus: int, n: int, B: int, device: int | str = 0, w
 def linear_sum_assignment(cost_matrix, maximize: bool = False, device: int | str = 0):
     """scipy.optimize.linear_sum_assignment for one matrix, solved on the GPU.
 
-    Square matrices only (the reference's blocks are square).  Integer
-    matrices whose sums stay below 2^53 are solved in exact int64 (where
-    scipy's float64 arithmetic is exact too); anything else in float64 with
-    scipy's operation order, so the permutation is scipy's either way."""
+    Any shape up to SH_MAX_N on the longer side: wide input returns
+    (arange(nr), col), tall input the rows scipy keeps, sorted, with their
+    columns.  Integer matrices whose sums stay below 2^53 are solved in exact
+    int64 (where scipy's float64 arithmetic is exact too); anything else in
+    float64 with scipy's operation order, so the permutation is scipy's
+    either way."""
     C = np.asarray(cost_matrix)
     if C.ndim != 2:
         raise ValueError("expected a matrix (2-D array), got a %r array" % (C.shape,))
-    if C.shape[0] != C.shape[1]:
-        raise ValueError("santa_hip solves square cost matrices only (the reference's blocks)")
-    n = C.shape[0]
-    if n == 0:
+    nr, nc = C.shape
+    if nr == 0 or nc == 0:
         return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
-    if n > _lib.SH_MAX_N:
-        raise ValueError(f"n = {n} > {_lib.SH_MAX_N}")
+    if max(nr, nc) > _lib.SH_MAX_N:
+        raise ValueError(f"max(nr, nc) = {max(nr, nc)} > {_lib.SH_MAX_N}")
     dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
     if C.dtype == np.bool_:
         C = C.astype(np.int64)
@@ -97,14 +206,12 @@ def linear_sum_assignment(cost_matrix, maximize: bool = False, device: int | str
         # negating an unsigned array wraps: widen first (uint64 beyond int64 -> float64)
         C = C.astype(np.int64) if (C.size == 0 or int(C.max()) <= np.iinfo(np.int64).max) \
             else C.astype(np.float64)
-    # scipy solves in float64.  Integer input is solved in exact int64, which
-    # makes scipy's decisions only while every value it forms is an integer
-    # below 2^53 (no float64 rounding); duals and path lengths stay within a few
-    # n * max|C|, so 4 (n + 1) max|C| < 2^53 is a safe bound.  The bound is
-    # taken in Python ints before any negation (np.abs / -C wrap at INT64_MIN).
-    # Wider ranges take the float64 replay of scipy's own arithmetic.
-    if np.issubdtype(C.dtype, np.integer) and \
-            (C.size == 0 or 4 * (n + 1) * max(int(C.max()), -int(C.min())) < EXACT_INT_LIMIT):
+    tall = nr > nc
+    if tall:  # scipy solves the transpose and re-orders the result (tall_result)
+        C = C.T
+    # Integer ranges wider than exact_int64_route allows take the float64
+    # replay of scipy's own arithmetic.
+    if exact_int64_route(C):
         Ci = np.ascontiguousarray(C, dtype=np.int64)
         Ct = torch.from_numpy(-Ci if maximize else Ci).to(dev)
     else:
@@ -118,4 +225,6 @@ def linear_sum_assignment(cost_matrix, maximize: bool = False, device: int | str
     col = col[0].cpu().numpy().astype(np.int64)
     if (col < 0).any():
         raise ValueError("cost matrix is infeasible")
-    return np.arange(n, dtype=np.int64), col
+    if tall:
+        return tall_result(col)
+    return np.arange(nr, dtype=np.int64), col
