@@ -83,6 +83,13 @@ extern "C" {
                                    kernel (santa_big_kernel) instead of the
                                    staged-row lattice kernel (A/B; identical
                                    results)                                 */
+#define SH_FLAG_F64_MW 16384u   /* floating-point lsap_solve_batched_* entries,
+                                   nc > 64: force the four-wave kernel
+                                   (lsap_f64_mw_kernel) ...               */
+#define SH_FLAG_F64_SW 32768u   /* ... or the one-wave kernel
+                                   (lsap_f64_kernel); A/B, identical results
+                                   bit for bit.  Both set: SH_ERR_ARGS.  The
+                                   integer and Santa entries ignore them  */
 #define SH_FLAG_NO_APPLY 1024u  /* solve and report (col, cost, deltas,
                                    steps) but leave the gift types untouched:
                                    blocks may then overlap (batched
@@ -338,6 +345,16 @@ int lsap_solve_batched_hash(uint64_t seed, int64_t modulus, int n, int B,
  * Checked on the host before any device call: SH_ERR_ARGS for nr < 1,
  * nr > nc, nc > SH_MAX_N, B < 0, a null d_C or d_col with B > 0, or
  * modulus <= 0.  B = 0 is a no-op.
+ *
+ * f32 / f16 / bf16: float32, IEEE half and bfloat16 costs (the 16-bit ones as
+ * const uint16_t *), read at their own width and widened to float64 in
+ * registers.  The widening is exact and scipy converts to float64 before it
+ * solves, so d_col and d_cost (double: the sum of the widened chosen entries,
+ * in the f64 entry's order) are bit for bit what the f64 entry returns for
+ * the widened matrix.  There are no square forms: pass nr == nc.
+ * The four floating-point entries run one wave per instance or, for nc > 64,
+ * four (default by size: DESIGN.md §7); SH_FLAG_F64_MW / SH_FLAG_F64_SW force
+ * one design, both together are SH_ERR_ARGS.
  * ------------------------------------------------------------------------ */
 int lsap_solve_batched_rect_i64(const int64_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
                                 int32_t *d_col, int64_t *d_cost, unsigned flags, void *stream);
@@ -345,6 +362,12 @@ int lsap_solve_batched_rect_i32(const int32_t *d_C, int nr, int nc, int B, const
                                 int32_t *d_col, int64_t *d_cost, unsigned flags, void *stream);
 int lsap_solve_batched_rect_f64(const double *d_C, int nr, int nc, int B, const int32_t *d_shape,
                                 int32_t *d_col, double *d_cost, unsigned flags, void *stream);
+int lsap_solve_batched_rect_f32(const float *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                int32_t *d_col, double *d_cost, unsigned flags, void *stream);
+int lsap_solve_batched_rect_f16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                int32_t *d_col, double *d_cost, unsigned flags, void *stream);
+int lsap_solve_batched_rect_bf16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                 int32_t *d_col, double *d_cost, unsigned flags, void *stream);
 int lsap_solve_batched_rect_hash(uint64_t seed, int64_t modulus, int nr, int nc, int B,
                                  int32_t *d_col, int64_t *d_cost, unsigned flags, void *stream);
 

@@ -5116,9 +5116,22 @@ __global__ __launch_bounds__(NW * WAVE) void santa_lb_kernel(SantaArgs a) {
 
 // ---------------------------------------------------------------------------
 // Generic batched LSAP.  int64 paths use the multi-wave solver (rows streamed
-// from global memory, or generated by hash); float64 uses the single-wave
-// scipy-replay solver sap_solve<K, double>.
+// from global memory, or generated by hash); floating-point costs use the
+// scipy-replay solvers in float64 arithmetic: sap_solve<K, double> (one wave
+// per instance) or sap_solve_mw_f64 (NW waves per instance).  The costs are
+// stored as float64, float32, float16 or bfloat16 and widened in registers
+// (exact; scipy converts to float64 before it solves).
 // ---------------------------------------------------------------------------
+struct sh_bf16 {
+  uint16_t bits;  // the high half of a float32
+};
+__device__ __forceinline__ double widen_f64(double x) { return x; }
+__device__ __forceinline__ double widen_f64(float x) { return (double)x; }
+__device__ __forceinline__ double widen_f64(_Float16 x) { return (double)x; }
+__device__ __forceinline__ double widen_f64(sh_bf16 x) {
+  return (double)__uint_as_float((uint32_t)x.bits << 16);
+}
+
 template <int K, typename S>
 struct GlobalLoaderF64 {
   const S *base;
@@ -5126,13 +5139,233 @@ struct GlobalLoaderF64 {
   int ld;  // row stride (elements)
   __device__ __forceinline__ void load(int i, double (&c)[K]) const {
     const S *row = base + (size_t)i * ld;
+    if constexpr (std::is_same<S, double>::value) {
 #pragma unroll
-    for (int k = 0; k < K; ++k) {
-      const int j = threadIdx.x + WAVE * k;
-      c[k] = (j < n) ? (double)row[j] : 0.0;
+      for (int k = 0; k < K; ++k) {
+        const int j = threadIdx.x + WAVE * k;
+        c[k] = (j < n) ? row[j] : 0.0;
+      }
+    } else {
+      // A narrow element is loaded without a branch, from its own column or
+      // for j >= n from the last live one (n >= 1; still never the padding),
+      // and widened after all K loads are issued: written like the float64
+      // form, the conversion lands inside the j < n branch next to its load
+      // and waits for it there, so the K load latencies of a step add up
+      // (measured: 2.6x on 1024-column float32 rows).
+      S raw[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) raw[k] = row[min((int)threadIdx.x + WAVE * k, n - 1)];
+#pragma unroll
+      for (int k = 0; k < K; ++k) c[k] = ((int)threadIdx.x + WAVE * k < n) ? widen_f64(raw[k]) : 0.0;
     }
   }
 };
+
+// The same rows for sap_solve_mw_f64: thread (w, lane) loads its mw_col columns.
+template <int NW, int K, typename S>
+struct GlobalLoaderF64MW {
+  const S *base;
+  int n;   // live columns: j >= n is never read
+  int ld;  // row stride (elements)
+  __device__ __forceinline__ void load(int i, double (&c)[K]) const {
+    const S *row = base + (size_t)i * ld;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if constexpr (std::is_same<S, double>::value) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        const int j = mw_col<NW, K>(w, k, lane);
+        c[k] = (j < n) ? row[j] : 0.0;
+      }
+    } else {  // (branch-free loads, widened after all K are issued: see GlobalLoaderF64)
+      S raw[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) raw[k] = row[min(mw_col<NW, K>(w, k, lane), n - 1)];
+#pragma unroll
+      for (int k = 0; k < K; ++k) c[k] = (mw_col<NW, K>(w, k, lane) < n) ? widen_f64(raw[k]) : 0.0;
+    }
+  }
+};
+
+// ---------------------------------------------------------------------------
+// float64 multi-wave replay solver: sap_solve<K, double>'s decisions and
+// arithmetic with the columns of one instance spread over NW waves as
+// sap_solve_mw spreads them (thread (w, lane) owns columns mw_col(w, k, lane),
+// k < K: spc / v / path / row4col / position-in-`remaining` in VGPRs; u,
+// col4row, row4col and the path dump in LDS).
+//
+// A double spc and the tie bits do not fit one 64-bit key, so a step's argmin
+// is the exact two-pass form at every level: minimum spc BY VALUE (-0.0 and
+// +0.0 tie, as in scipy's spc[j] == lowest), then minimum tie key (sap_solve's
+// 32-bit word) among the columns at that minimum.  A thread folds its K
+// columns into one (spc, key) pair, a wave folds its lanes' pairs with DPP,
+// the lane that owns the wave's winner writes the pair to the wave's LDS slot,
+// and after ONE barrier every wave folds the NW pairs.  The slots are
+// double-buffered by step parity: step t + 1's writes follow barrier t, which
+// every wave reaches after its reads of step t - 1.  The pair carries the
+// winning column's own spc, so minVal has the sign of zero scipy's has.
+//
+// The step loop is bounded by construction: each step removes one column from
+// `remaining`, and an empty `remaining` ends the instance as infeasible (only
+// input the caller should have rejected, NaN or -inf, gets there).
+// Returns 0, or -1 for an infeasible instance (block-uniform).
+// ---------------------------------------------------------------------------
+struct SolveLdsF64 {
+  double *u;       // [nr]  row duals
+  int16_t *c4r;    // [nr]  col4row (the result)
+  int16_t *r4c;    // [n]   row4col
+  int16_t *path;   // [n]   path dump of the visited columns
+  double *rv;      // [2 * NW]  the waves' step minima, by step parity
+  uint32_t *rk;    // [2 * NW]  and their tie keys
+};
+
+template <int CTRL, int ROWMASK>
+__device__ __forceinline__ double dpp_min_f64_step(double x) {
+  // (rows outside ROWMASK read their own value back: dpp_u64's old operand)
+  const double y = __longlong_as_double((long long)dpp_u64<CTRL, ROWMASK>((uint64_t)__double_as_longlong(x)));
+  return (y < x) ? y : x;
+}
+
+// Minimum by value over the 64 lanes, wave-uniform (the levels of
+// wave_min_u64_dpp); between -0.0 and +0.0 either may come back.
+__device__ __forceinline__ double wave_min_f64_dpp(double x) {
+  x = dpp_min_f64_step<0xB1, 0xF>(x);   // quad_perm [1,0,3,2]
+  x = dpp_min_f64_step<0x4E, 0xF>(x);   // quad_perm [2,3,0,1]
+  x = dpp_min_f64_step<0x141, 0xF>(x);  // row_half_mirror
+  x = dpp_min_f64_step<0x140, 0xF>(x);  // row_mirror
+  x = dpp_min_f64_step<0x142, 0xA>(x);  // row_bcast:15 -> rows 1, 3
+  x = dpp_min_f64_step<0x143, 0xC>(x);  // row_bcast:31 -> rows 2, 3
+  return __longlong_as_double((long long)readlane_u64((uint64_t)__double_as_longlong(x), 63));
+}
+
+template <int NW, int K, typename Loader>
+__device__ __forceinline__ int sap_solve_mw_f64(const int nr, const int n, const Loader &ld,
+                                                const SolveLdsF64 &S) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const double INF = VT<double>::inf();
+  double spc[K], v[K];
+  int path[K], r4c[K], pos[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    v[k] = 0;
+    path[k] = -1;
+  }
+  int par = 0;  // slot buffer of the step
+  for (int cur = 0; cur < nr; ++cur) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int j = mw_col<NW, K>(w, k, lane);
+      spc[k] = INF;
+      r4c[k] = (j < n) ? S.r4c[j] : -1;
+      pos[k] = (j < n) ? (n - 1 - j) : -1;
+    }
+    double minVal = 0;
+    int i = cur;
+    int sink = -1;
+    for (int nrem = n; nrem > 0; --nrem) {
+      const double ui = S.u[i];
+      double c[K];
+      ld.load(i, c);
+      // this thread's pair: best is the spc of the column bsec names
+      double best = INF;
+      uint32_t bsec = SEC_NONE;
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        if (pos[k] >= 0) {
+          const int j = mw_col<NW, K>(w, k, lane);
+          const double r = minVal + c[k] - ui - v[k];
+          if (r < spc[k]) {
+            spc[k] = r;
+            path[k] = i;
+          }
+          const uint32_t sec =
+              (r4c[k] < 0)
+                  ? (((uint32_t)(1023 - pos[k]) << 20) | (uint32_t)j)
+                  : ((1u << 30) | ((uint32_t)pos[k] << 20) |
+                     ((uint32_t)r4c[k] << 10) | (uint32_t)j);
+          if (spc[k] < best || (spc[k] == best && sec < bsec)) {
+            best = spc[k];
+            bsec = sec;
+          }
+        }
+      }
+      // the wave's pair, written by the lane that owns it (keys are unique per
+      // column; a wave without a remaining column writes (INF, SEC_NONE))
+      const double wm = wave_min_f64_dpp(best);
+      const uint32_t wk = wave_min_u32_dpp((best == wm) ? bsec : SEC_NONE);
+      if (best == wm && bsec == wk && (wk != SEC_NONE || lane == 0)) {
+        S.rv[par * NW + w] = best;
+        S.rk[par * NW + w] = wk;
+      }
+      __syncthreads();
+      double m = S.rv[par * NW];
+      uint32_t s = S.rk[par * NW];
+#pragma unroll
+      for (int q = 1; q < NW; ++q) {
+        const double mq = S.rv[par * NW + q];
+        const uint32_t sq = S.rk[par * NW + q];
+        if (mq < m || (mq == m && sq < s)) {
+          m = mq;
+          s = sq;
+        }
+      }
+      par ^= 1;
+      m = __longlong_as_double((long long)readlane_u64((uint64_t)__double_as_longlong(m), 0));
+      s = (uint32_t)__builtin_amdgcn_readfirstlane((int)s);
+      if (!(m < INF)) return -1;
+      // minVal = spc of the chosen column (scipy: lowest = spc[j]), sign of
+      // zero included: the pair carried that column's own spc
+      minVal = m;
+      const int jstar = (int)(s & 1023u);
+      const bool assigned = (s >> 30) & 1u;
+      const int pfield = (int)((s >> 20) & 1023u);
+      const int prem = assigned ? pfield : 1023 - pfield;
+      const int last = nrem - 1;
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        const int j = mw_col<NW, K>(w, k, lane);
+        if (j == jstar)
+          pos[k] = -1;
+        else if (pos[k] == last)
+          pos[k] = prem;
+      }
+      if (!assigned) {
+        sink = jstar;
+        break;
+      }
+      i = (int)((s >> 10) & 1023u);
+    }
+    if (sink < 0) return -1;  // `remaining` ran empty
+    // Dual update (scipy: u[cur] += minVal; u[i] += minVal - spc[col4row[i]]
+    // for the other visited rows; v[j] -= minVal - spc[j] for visited cols)
+    // and path dump of the visited columns.
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int j = mw_col<NW, K>(w, k, lane);
+      if (j < n && pos[k] < 0) {
+        const double d = minVal - spc[k];
+        v[k] = v[k] - d;
+        if (r4c[k] >= 0) S.u[r4c[k]] = S.u[r4c[k]] + d;
+        S.path[j] = (int16_t)path[k];
+      }
+    }
+    if (tid == 0) S.u[cur] = S.u[cur] + minVal;
+    __syncthreads();
+    if (tid == 0) {  // augment along the path from the sink back to cur (<= nr hops)
+      int j = sink;
+      for (int hop = 0; hop < nr; ++hop) {
+        const int pi = S.path[j];
+        if (pi < 0) break;  // (unreachable on valid input)
+        S.r4c[j] = (int16_t)pi;
+        const int t = S.c4r[pi];
+        S.c4r[pi] = (int16_t)j;
+        j = t;
+        if (pi == cur || j < 0) break;
+      }
+    }
+    __syncthreads();
+  }
+  return 0;
+}
 
 // Instance b is the padded NR x NC matrix at C + b * NR * NC (row stride NC);
 // it solves the top-left nr x nc corner, (nr, nc) = (NR, NC) or, with `shape`,
@@ -5218,8 +5451,8 @@ __global__ __launch_bounds__(NW * WAVE) void lsap_i64_kernel(const S *C, uint64_
   }
 }
 
-template <int K>
-__global__ __launch_bounds__(WAVE) void lsap_f64_kernel(const double *C, int NR, int NC,
+template <int K, typename S>
+__global__ __launch_bounds__(WAVE) void lsap_f64_kernel(const S *C, int NR, int NC,
                                                         const int32_t *shape, int32_t *col,
                                                         double *cost) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -5240,7 +5473,7 @@ __global__ __launch_bounds__(WAVE) void lsap_f64_kernel(const double *C, int NR,
   __syncthreads();
   int64_t steps = 0;
   const size_t base = (size_t)b * NR * NC;
-  GlobalLoaderF64<K, double> ld{C + base, n, NC};
+  GlobalLoaderF64<K, S> ld{C + base, n, NC};
   const int st = sap_solve<K, double>(nr, n, ld, u_l, c4r_l, steps);
   __syncthreads();
   double acc = 0;
@@ -5248,13 +5481,61 @@ __global__ __launch_bounds__(WAVE) void lsap_f64_kernel(const double *C, int NR,
     const bool live = st == 0 && i < nr;
     const int cidx = live ? c4r_l[i] : -1;
     col[(size_t)b * NR + i] = cidx;
-    if (live && cost) acc += C[base + (size_t)i * NC + cidx];
+    if (live && cost) acc += widen_f64(C[base + (size_t)i * NC + cidx]);
   }
   if (cost) {
     // wave sum in a fixed order (deterministic); it differs from numpy's sum
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, WAVE);
     if (lane == 0) cost[b] = acc;
+  }
+}
+
+// The same instance on NW waves (sap_solve_mw_f64).  Wave 0 sums the chosen
+// cost in lsap_f64_kernel's order, so both designs return the same bits.
+template <int NW, int K, typename S>
+__global__ __launch_bounds__(NW * WAVE) void lsap_f64_mw_kernel(const S *C, int NR, int NC,
+                                                                const int32_t *shape, int32_t *col,
+                                                                double *cost) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int WG = NW * WAVE;
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  int nr, n;  // live rows and columns (see lsap_i64_kernel)
+  if (!lsap_shape(shape, b, NR, NC, nr, n)) {
+    for (int i = tid; i < NR; i += WG) col[(size_t)b * NR + i] = -1;
+    if (tid == 0 && cost) cost[b] = 0;
+    return;
+  }
+  size_t off = 0;
+  SolveLdsF64 Sl;
+  Sl.u = (double *)(smem + off);      off += r16((size_t)nr * 8);
+  Sl.rv = (double *)(smem + off);     off += r16((size_t)2 * NW * 8);
+  Sl.rk = (uint32_t *)(smem + off);   off += r16((size_t)2 * NW * 4);
+  Sl.c4r = (int16_t *)(smem + off);   off += r16((size_t)nr * 2);
+  Sl.r4c = (int16_t *)(smem + off);   off += r16((size_t)n * 2);
+  Sl.path = (int16_t *)(smem + off);
+  for (int i = tid; i < n; i += WG) {
+    if (i < nr) {
+      Sl.u[i] = 0;
+      Sl.c4r[i] = -1;
+    }
+    Sl.r4c[i] = -1;
+    Sl.path[i] = -1;
+  }
+  __syncthreads();
+  const size_t base = (size_t)b * NR * NC;
+  const GlobalLoaderF64MW<NW, K, S> ld{C + base, n, NC};
+  const int st = sap_solve_mw_f64<NW, K>(nr, n, ld, Sl);
+  __syncthreads();
+  for (int i = tid; i < NR; i += WG) col[(size_t)b * NR + i] = (st == 0 && i < nr) ? Sl.c4r[i] : -1;
+  if (cost && tid < WAVE) {
+    double acc = 0;
+    for (int i = tid; i < NR; i += WAVE)
+      if (st == 0 && i < nr) acc += widen_f64(C[base + (size_t)i * NC + Sl.c4r[i]]);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, WAVE);
+    if (tid == 0) cost[b] = acc;
   }
 }
 
@@ -6404,21 +6685,53 @@ int launch_lsap_i64(const S *C, uint64_t seed, int64_t mod, int nr, int n, int B
   return SH_OK;
 }
 
-int launch_lsap_f64(const double *C, int nr, int n, int B, const int32_t *shape, int32_t *col,
-                    double *cost, hipStream_t s) {
+// Whether a float batch of B instances with nc columns runs four waves per
+// instance by default (measured: DESIGN §7, profiles/lsap_float_ab.jsonl).
+// Up to 1024 instances one wave each leaves SIMDs idle and four waves won at
+// every nc measured (128: 5-9 %, 256: 17-22 %, 512: 29-36 %, 1024: 38-49 %);
+// at 4096 instances one wave each won (nc = 128, 256, 512), and nothing
+// between 1024 and 4096 was measured except nc = 256 (2048: four waves, 5 %),
+// so those batches keep the kernel they always ran.
+bool f64_mw_default(int nc, int B) { return nc > WAVE && B <= 1024; }
+
+// Floating-point costs stored as S (double, float, _Float16, sh_bf16), solved
+// in float64.  One wave per instance (lsap_f64_kernel) or, for nc > 64, four
+// (lsap_f64_mw_kernel, 1 / 2 / 4 columns per thread as the integer path's):
+// the default is f64_mw_default above, SH_FLAG_F64_MW / SH_FLAG_F64_SW force one.
+template <typename S>
+int launch_lsap_f64(const S *C, int nr, int n, int B, const int32_t *shape, int32_t *col,
+                    double *cost, unsigned flags, hipStream_t s) {
+  if (!C && B > 0) return fail(SH_ERR_ARGS, "null C");
   const int rc = check_lsap_args(nr, n, B, col);
-  if (rc || B == 0) return rc;
-  const size_t lds = r16((size_t)nr * 8) + r16((size_t)nr * 2);
-#define L_(KK) \
-  hipLaunchKernelGGL((lsap_f64_kernel<KK>), dim3(B), dim3(WAVE), lds, s, C, nr, n, shape, col, cost)
-  switch (pick_k(n)) {
-    case 1: L_(1); break;
-    case 2: L_(2); break;
-    case 4: L_(4); break;
-    case 8: L_(8); break;
-    default: L_(16); break;
-  }
+  if (rc) return rc;
+  if ((flags & SH_FLAG_F64_MW) && (flags & SH_FLAG_F64_SW))
+    return fail(SH_ERR_ARGS, "SH_FLAG_F64_MW and SH_FLAG_F64_SW exclude each other");
+  if (B == 0) return SH_OK;
+  const bool mw = n > WAVE && !(flags & SH_FLAG_F64_SW) && ((flags & SH_FLAG_F64_MW) || f64_mw_default(n, B));
+  if (mw) {
+    constexpr int NW = 4;
+    const size_t lds = r16((size_t)nr * 8) + r16((size_t)2 * NW * 8) + r16((size_t)2 * NW * 4) +
+                       r16((size_t)nr * 2) + 2 * r16((size_t)n * 2);
+#define L_(KK)                                                                                     \
+  hipLaunchKernelGGL((lsap_f64_mw_kernel<NW, KK, S>), dim3(B), dim3(NW * WAVE), lds, s, C, nr, n, \
+                     shape, col, cost)
+    if (n <= 256) L_(1);
+    else if (n <= 512) L_(2);
+    else L_(4);
 #undef L_
+  } else {
+    const size_t lds = r16((size_t)nr * 8) + r16((size_t)nr * 2);
+#define L_(KK) \
+  hipLaunchKernelGGL((lsap_f64_kernel<KK, S>), dim3(B), dim3(WAVE), lds, s, C, nr, n, shape, col, cost)
+    switch (pick_k(n)) {
+      case 1: L_(1); break;
+      case 2: L_(2); break;
+      case 4: L_(4); break;
+      case 8: L_(8); break;
+      default: L_(16); break;
+    }
+#undef L_
+  }
   HIP_TRY(hipGetLastError());
   return SH_OK;
 }
@@ -6464,9 +6777,24 @@ int lsap_solve_batched_rect_i32(const int32_t *d_C, int nr, int nc, int B, const
 
 int lsap_solve_batched_rect_f64(const double *d_C, int nr, int nc, int B, const int32_t *d_shape,
                                 int32_t *d_col, double *d_cost, unsigned flags, void *stream) {
-  if (!d_C && B > 0) return fail(SH_ERR_ARGS, "null C");
-  (void)flags;
-  return launch_lsap_f64(d_C, nr, nc, B, d_shape, d_col, d_cost, (hipStream_t)stream);
+  return launch_lsap_f64(d_C, nr, nc, B, d_shape, d_col, d_cost, flags, (hipStream_t)stream);
+}
+
+int lsap_solve_batched_rect_f32(const float *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                int32_t *d_col, double *d_cost, unsigned flags, void *stream) {
+  return launch_lsap_f64(d_C, nr, nc, B, d_shape, d_col, d_cost, flags, (hipStream_t)stream);
+}
+
+int lsap_solve_batched_rect_f16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                int32_t *d_col, double *d_cost, unsigned flags, void *stream) {
+  return launch_lsap_f64((const _Float16 *)d_C, nr, nc, B, d_shape, d_col, d_cost, flags,
+                         (hipStream_t)stream);
+}
+
+int lsap_solve_batched_rect_bf16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                 int32_t *d_col, double *d_cost, unsigned flags, void *stream) {
+  return launch_lsap_f64((const sh_bf16 *)d_C, nr, nc, B, d_shape, d_col, d_cost, flags,
+                         (hipStream_t)stream);
 }
 
 int lsap_solve_batched_rect_hash(uint64_t seed, int64_t modulus, int nr, int nc, int B,

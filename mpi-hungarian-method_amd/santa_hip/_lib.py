@@ -33,6 +33,8 @@ SH_FLAG_NO_APPLY = 1024  # solve without writing the gift types (overlapping blo
 SH_FLAG_SP2 = 2048  # retired (round 4): the C-ABI refuses it (SH_ERR_ARGS)
 SH_FLAG_DT_TILE = 4096  # force the dense-tile one-wave kernel (santa_dt_kernel)
 SH_FLAG_BIG_ROWS = 8192  # singles n > 256: force the row-rebuild kernel (santa_big_kernel)
+SH_FLAG_F64_MW = 16384  # float LSAP entries, nc > 64: force the four-wave kernel (lsap_f64_mw_kernel)
+SH_FLAG_F64_SW = 32768  # float LSAP entries: force the one-wave kernel (lsap_f64_kernel)
 SH_ERRF_ROWS = 1
 SH_ERRF_INFEASIBLE = 2
 SH_ERRF_TYPE = 4
@@ -105,6 +107,9 @@ SIGNATURES = {
     "lsap_solve_batched_rect_i64": (_I, [_P, _I, _I, _I, _P, _P, _P, _U, _P]),
     "lsap_solve_batched_rect_i32": (_I, [_P, _I, _I, _I, _P, _P, _P, _U, _P]),
     "lsap_solve_batched_rect_f64": (_I, [_P, _I, _I, _I, _P, _P, _P, _U, _P]),
+    "lsap_solve_batched_rect_f32": (_I, [_P, _I, _I, _I, _P, _P, _P, _U, _P]),
+    "lsap_solve_batched_rect_f16": (_I, [_P, _I, _I, _I, _P, _P, _P, _U, _P]),
+    "lsap_solve_batched_rect_bf16": (_I, [_P, _I, _I, _I, _P, _P, _P, _U, _P]),
     "lsap_solve_batched_rect_hash": (_I, [_U64, _I64, _I, _I, _I, _P, _P, _U, _P]),
     "sh_gen_synthetic": (_I, [_U64, _I, _I, _I, _I, _I, _P, _P, _P]),
 }

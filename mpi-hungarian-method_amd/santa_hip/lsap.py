@@ -8,6 +8,8 @@ arrays, same ValueError on NaN / -inf / infeasible input.  Solves run on the
 GPU through the C-ABI batched solvers; float64 input is replayed with scipy's
 own float64 arithmetic, so even the permutation on ties is scipy's.  Tall
 input is solved as its transpose and inverted, as scipy does internally.
+solve_batched also takes float32, float16 and bfloat16 device tensors: read at
+their own width, widened in registers (exact) and solved as float64.
 """
 from __future__ import annotations
 
@@ -26,6 +28,9 @@ def _p(t):
 
 INT64_COST_LIMIT = 1 << 50  # |C| bound that keeps every SAP value < 2^62 (n <= 1024)
 EXACT_INT_LIMIT = 1 << 53   # float64 holds every integer below this exactly
+# floating-point cost dtypes of solve_batched and their C-ABI entries
+FLOAT_ENTRIES = {torch.float64: "lsap_solve_batched_rect_f64", torch.float32: "lsap_solve_batched_rect_f32",
+                 torch.float16: "lsap_solve_batched_rect_f16", torch.bfloat16: "lsap_solve_batched_rect_bf16"}
 
 
 # ---------------------------------------------------------------------------
@@ -107,9 +112,10 @@ def _solve_wide(C: torch.Tensor, with_cost: bool, fl: int, shape_dev):
     elif C.dtype == torch.int32:
         cost = torch.empty(B, dtype=torch.int64, device=dev) if with_cost else None
         rc = L.lsap_solve_batched_rect_i32(_p(C), nr, nc, B, _p(shape_dev), _p(col), _p(cost), fl, s)
-    elif C.dtype == torch.float64:
+    elif C.dtype in FLOAT_ENTRIES:  # read at their own width, solved in float64
         cost = torch.empty(B, dtype=torch.float64, device=dev) if with_cost else None
-        rc = L.lsap_solve_batched_rect_f64(_p(C), nr, nc, B, _p(shape_dev), _p(col), _p(cost), fl, s)
+        entry = getattr(L, FLOAT_ENTRIES[C.dtype])
+        rc = entry(_p(C), nr, nc, B, _p(shape_dev), _p(col), _p(cost), fl, s)
     else:
         raise TypeError(f"unsupported dtype {C.dtype}")
     _lib.check(rc, "lsap_solve_batched")
@@ -118,11 +124,16 @@ def _solve_wide(C: torch.Tensor, with_cost: bool, fl: int, shape_dev):
 
 def solve_batched(C: torch.Tensor, with_cost: bool = True, flags: int = 0, shapes=None,
                   maximize: bool = False):
-    """C: device tensor [B, NR, NC] (int64 / int32 / float64) -> (col int32 [B, NR], cost [B]).
+    """C: device tensor [B, NR, NC] (int64 / int32 / float64 / float32 /
+    float16 / bfloat16) -> (col int32 [B, NR], cost [B]).
 
+    Floating-point costs are read at their own width and solved in float64
+    (the widening is exact, and scipy converts to float64 before it solves):
+    col and cost (float64) are bit for bit those of C.double().  Any other
+    dtype raises TypeError.
     col[b, i] is the column of row i, -1 for a row without one: the NR - NC
     rows scipy leaves out of a tall instance, every row of an infeasible
-    instance (float64 with +inf only), and the padded rows of a ragged one.
+    instance (floating point with +inf only), and the padded rows of a ragged one.
     `shapes` ([B, 2] integers, host or device) makes the batch ragged:
     instance b is the top-left shapes[b] = (nr_b, nc_b) corner of its padded
     matrix, 0 <= nr_b <= NR, nr_b <= nc_b <= NC; the padding is never read.
@@ -136,7 +147,7 @@ def solve_batched(C: torch.Tensor, with_cost: bool = True, flags: int = 0, shape
     B, NR, NC = C.shape
     if max(NR, NC) > _lib.SH_MAX_N:
         raise ValueError(f"max(NR, NC) = {max(NR, NC)} > {_lib.SH_MAX_N}")
-    if C.dtype not in (torch.int64, torch.int32, torch.float64):
+    if C.dtype not in (torch.int64, torch.int32) and C.dtype not in FLOAT_ENTRIES:
         raise TypeError(f"unsupported dtype {C.dtype}")
     dev = C.device
     shape_dev = None
@@ -146,7 +157,7 @@ def solve_batched(C: torch.Tensor, with_cost: bool = True, flags: int = 0, shape
                              "transpose the batch so that every instance has nr <= nc")
         shape_dev = torch.from_numpy(check_shapes(shapes, B, NR, NC)).to(dev)
     if B == 0 or NR == 0 or NC == 0:
-        cdt = torch.float64 if C.dtype == torch.float64 else torch.int64
+        cdt = torch.float64 if C.dtype in FLOAT_ENTRIES else torch.int64
         return (torch.full((B, NR), -1, dtype=torch.int32, device=dev),
                 torch.zeros(B, dtype=cdt, device=dev) if with_cost else None)
     if maximize:  # (int32: -INT32_MIN wraps, so widen; the int64 bound covers int64)

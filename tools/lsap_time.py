@@ -1,26 +1,56 @@
-"""dev: time lsap_solve_batched_hash for a few cases on the library SANTA_HIP_LIB selects (A/B).
-    python tools/lsap_time.py [NxB | NRxNCxB ...]     (default: 256x512 512x256 1024x256 256x4096)
-NxB: B square n x n instances; NRxNCxB: B instances of the first nr rows of
-the same nc x nc matrices (lsap_solve_batched_rect_hash)."""
+"""dev: time the batched LSAP for a few cases on the library SANTA_HIP_LIB selects (A/B).
+    python tools/lsap_time.py [--dtype hash|f64|f32|f16|bf16] [--flags N] [--ties] [--tag TEXT]
+                              [NxB | NRxNCxB ...]     (default: 256x512 512x256 1024x256 256x4096)
+NxB: B square n x n instances; NRxNCxB: B instances of nr x nc.
+--dtype hash (the default): lsap_solve_batched_hash / _rect_hash, costs generated in the kernel.
+--dtype f64 / f32 / f16 / bf16: solve_batched on a device tensor of that dtype, generated on the
+  device from seed 7: torch.rand * 2^16, or with --ties the tie-heavy randint(0, 3) * 0.5.
+--flags: C-ABI flags passed on (SH_FLAG_F64_MW = 16384, SH_FLAG_F64_SW = 32768).
+Both take comma-separated lists (every combination is timed, per case).  SANTA_HIP_PKG names the
+directory that holds the santa_hip package of another checkout (an older commit, with
+SANTA_HIP_LIB its own library); the default is this tree's.
+One JSON line per case: best and median of 3 timed solves after a warm-up (HIP events, ms)."""
+import argparse
 import json
 import os
+import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "mpi-hungarian-method_amd"))
+sys.path.insert(0, os.environ.get("SANTA_HIP_PKG") or os.path.join(ROOT, "mpi-hungarian-method_amd"))
 import torch  # noqa: E402
 import santa_hip  # noqa: E402
 
-cases = [tuple(int(x) for x in c.split("x")) for c in sys.argv[1:]] or [(256, 512), (512, 256), (1024, 256),
-                                                                         (256, 4096)]
-for case in cases:
-    nr, (n, B) = (case[0], case[1:]) if len(case) == 3 else (None, case)
+ap = argparse.ArgumentParser()
+ap.add_argument("--dtype", default="hash")
+ap.add_argument("--flags", default="0")
+ap.add_argument("--ties", action="store_true")
+ap.add_argument("--tag", default=None)
+ap.add_argument("cases", nargs="*", default=["256x512", "512x256", "1024x256", "256x4096"])
+args = ap.parse_args()
+DT = {"f64": torch.float64, "f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
+dtypes, flag_list = args.dtype.split(","), [int(f) for f in args.flags.split(",")]
+assert all(d == "hash" or d in DT for d in dtypes), "--dtype: hash, f64, f32, f16 or bf16"
 
-    def solve():
-        if nr is None:
-            santa_hip.solve_hash(7, 1 << 16, n, B)
+for case, dtype, flags in [(tuple(int(x) for x in c.split("x")), d, f)
+                           for c in args.cases for d in dtypes for f in flag_list]:
+    nr, (n, B) = (case[0], case[1:]) if len(case) == 3 else (None, case)
+    if dtype == "hash":
+        def solve():
+            if nr is None:
+                santa_hip.solve_hash(7, 1 << 16, n, B)
+            else:
+                santa_hip.solve_hash(7, 1 << 16, n, B, nr=nr)
+    else:
+        g = torch.Generator(device="cuda").manual_seed(7)
+        shape = (B, n if nr is None else nr, n)
+        if args.ties:
+            C = torch.randint(0, 3, shape, generator=g, device="cuda").to(DT[dtype]) * 0.5
         else:
-            santa_hip.solve_hash(7, 1 << 16, n, B, nr=nr)
+            C = (torch.rand(shape, generator=g, device="cuda", dtype=torch.float64) * 65536.0).to(DT[dtype])
+
+        def solve():
+            santa_hip.solve_batched(C, with_cost=False, flags=flags)
 
     solve()
     torch.cuda.synchronize()
@@ -35,4 +65,8 @@ for case in cases:
     out = {"n": n, "B": B, "ms": min(ts)}
     if nr is not None:
         out = {"nr": nr, "nc": n, "B": B, "ms": min(ts)}
+    if dtype != "hash" or flags or args.tag:
+        out.update(dtype=dtype, flags=flags, ties=args.ties, median_ms=statistics.median(ts))
+    if args.tag:
+        out["tag"] = args.tag
     print(json.dumps(out))
