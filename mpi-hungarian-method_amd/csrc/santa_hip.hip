@@ -3559,8 +3559,6 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
   // flips by 0x7FC for the one column a Dijkstra assigns (its sink; a column,
   // once assigned, stays so); a column j >= n (never assigned) holds ~0
   u32x4 LI;  // (one VGPR tuple: the sink's flip is an indexed move)
-  // `remaining` at a Dijkstra's start: rem[p] = n - 1 - p for this lane's p
-  uint4 rem0;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     W[k] = 0;
@@ -3568,7 +3566,6 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
     const int j = 4 * lane + k;
     LI[k] = j < n ? (((uint32_t)(n - 1 - j) << 2) | (uint32_t)k) ^ 0x3FCu : ~0u;
   }
-  rem0 = make_uint4(n - 1 - 4 * lane, n - 2 - 4 * lane, n - 3 - 4 * lane, n - 4 - 4 * lane);
   // rem[p]: the column at position p of scipy's `remaining`; rowq[n - 1 - t]:
   // the LDS address of u_l[i] for the row i of step t (written by the step's
   // LDS group from the address it reads the dual with)
@@ -3592,42 +3589,72 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
   asm volatile("" : "+v"(ro0));
   const uint32_t lhalf = (uint32_t)lane >> 5;  // (the 32-lane half: a row's entries live in one)
   const uint32_t rob = lds_addr(rowc) + 4u * (uint32_t)ro0;  // (LDS byte address)
+  // the sink is the one column a Dijkstra assigns: flip its start tie bits
+  // (slot k of the one lane in lmask)
+  auto flip_sink = [&](uint64_t lmask, int k) __attribute__((always_inline)) {
+    uint64_t sv;
+    uint32_t tx;
+    asm volatile(
+        "s_mov_b64 %1, exec\n\t"
+        "s_mov_b64 exec, %3\n\t"
+        "s_set_gpr_idx_on %4, gpr_idx(SRC0)\n\t"
+        "v_mov_b32 %2, " SH_VREG(SP3_LI_V) "\n\t"
+        "s_set_gpr_idx_off\n\t"
+        "v_xor_b32 %2, 0x7fc, %2\n\t"
+        "s_set_gpr_idx_on %4, gpr_idx(DST)\n\t"
+        "v_mov_b32 " SH_VREG(SP3_LI_V) ", %2\n\t"
+        "s_set_gpr_idx_off\n\t"
+        "s_mov_b64 exec, %1"
+        : "+" SH_VTUPLE(SP3_LI_V, SP3_LI_VE)(LI), "=&s"(sv), "=&v"(tx)
+        : "s"(lmask), "s"(k)
+        : "m0");
+  };
   if (a.flags & SH_FLAG_BUILD_ONLY) {
     c4r = (uint32_t)(4 * lane) * 0x01010101u + 0x03020100u;
   } else {
+    // (n for the priority thresholds, opaque: the compiler otherwise takes
+    //  n - 2 from a vector it forms with the lanes' rem0 terms, and the
+    //  Dijkstra's scalar branches and operands turn into lane masks and VGPRs)
+    int np = n;
+    asm volatile("" : "+s"(np));
     for (int cur = 0; cur < n; ++cur) {
-      if (cur == n - SP3_PRIO_A) __builtin_amdgcn_s_setprio(2);  // (issue priority, above)
-      if (cur == n - SP3_PRIO_B) __builtin_amdgcn_s_setprio(1);
-      if (cur == n - SP3_PRIO_C) __builtin_amdgcn_s_setprio(0);
-      // Dijkstra set-up: remaining = [n-1 .. 0], every column < n live, spc = inf
+      if (cur == np - SP3_PRIO_A) __builtin_amdgcn_s_setprio(2);  // (issue priority, above)
+      if (cur == np - SP3_PRIO_B) __builtin_amdgcn_s_setprio(1);
+      if (cur == np - SP3_PRIO_C) __builtin_amdgcn_s_setprio(0);
+      // A Dijkstra's state: the peeled first step needs none of it (remaining
+      // = [n-1 .. 0], every column < n live, spc = inf are folded in); its
+      // hand-over sets what the generic loop holds after its step 0
       int ln = lane;
       asm volatile("" : "+v"(ln));
-      lo = LI;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) sbp[k] = ~0u;
-      *(uint4 *)(rem + 4 * ln) = rem0;
-      int nrem = n;
-      uint32_t rq = lds_addr(rem) + 4u * (uint32_t)(n - 1);  // &rem[nrem - 1], stepped down
-      asm volatile("" : "+v"(rq));  // (a VGPR: the LDS address operand, stepped by one VALU)
-      uint32_t mvb = (uint32_t)SP3_BIAS;  // minVal + BIAS (the key's value field of the last winner)
+      int nrem;
+      uint32_t rq;   // &rem[nrem - 1], stepped down (a VGPR: the LDS address operand, stepped by one VALU)
+      uint32_t mvb;  // minVal + BIAS (the key's value field of the last winner)
       int i = cur;
       int sink;
       // deferred book-keeping of the previous step, applied in the shadow of
       // the next step's LDS group: the winner (lane, slot) leaves `remaining`
       // (lo = ~0), the mover (the column at the last position) takes the
       // winner's position (its pkey bits ^= kX); a lane mask of 0: none
-      uint64_t wmask = 0, mmask = 0;
-      int kw = 0, kmv = 0;
-      uint32_t kX = 0;  // (a VGPR: the xor's vector operand)
-      asm volatile("" : "+v"(kX));
+      uint64_t wmask, mmask;
+      int kw, kmv;
+      uint32_t kX;  // (a VGPR: the xor's vector operand)
+      // a step's argmin: this lane's best key, the row of its column, the
+      // wave's minimum key and its class bit
+      uint32_t best, rsel, g;
+      uint32_t assigned;  // (the class bit in place: a scalar, not a lane mask)
       bool first = true;
-      for (;;) {
-        ++steps;
+      // The tile entry of row i for this lane (tw0, tw1: the tile dwords
+      // T0[(i >> 2) & 31], T1[(i >> 2) & 31], indexed by the caller: through
+      // the closure's reference the dynamic index would put the tile in scratch)
+      struct Entry {
+        uint32_t ea;   // the entry's rank field (SP2_MARK: the row's overflow marker)
+        int sslot;     // its row-buffer slot (the lane's dump slot outside the row's half)
+        int32_t sval;  // its value in key units
+      };
+      auto fetch = [&](int i, const uint32_t tw0, const uint32_t tw1) __attribute__((always_inline)) -> Entry {
         stamp(first ? tD : tC);
-        first = false;
         // the tile dword of row i: T0 or T1 by bit 7 of i, one v_bfi with a
         // sign-extended scalar mask (s_bfe_i32) instead of a compare and select
-        const uint32_t tw0 = T0[(i >> 2) & 31], tw1 = T1[(i >> 2) & 31];
         const uint32_t tsel = (uint32_t)__builtin_amdgcn_sbfe(i, 7, 1);
         uint32_t tw;  // (asm: the compiler turns the and/or form back into a compare and select)
         asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(tw) : "s"(tsel), "v"(tw1), "v"(tw0));
@@ -3637,18 +3664,42 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
         // the row's half of the wave (lanes 32L.., L = (i >> 1) & 1) as an SGPR mask
         uint32_t hb;  // (bit 1 of i in a VGPR: the compare below is VALU, no scalar mask)
         asm("v_bfe_u32 %0, %1, 1, 1" : "=v"(hb) : "s"(i));
+        Entry e;
         const bool mine = lhalf == hb;
-        const uint32_t ea = __builtin_amdgcn_ubfe(tw, sh + 9u, 7);
+        e.ea = __builtin_amdgcn_ubfe(tw, sh + 9u, 7);
         // expand the row: hit columns get -a (key units), the rest hold a
         // miss; read this lane's four columns; put the misses back (in-order LDS)
-        const int sslot = mine ? (int)__builtin_amdgcn_ubfe(tw, sh, 9) : 256 + x31;
-        const int32_t sval = -(int32_t)(ea << (9 + SP3_SH));
+        e.sslot = mine ? (int)__builtin_amdgcn_ubfe(tw, sh, 9) : 256 + x31;
+        e.sval = -(int32_t)(e.ea << (9 + SP3_SH));
         if constexpr (TIMED) {  // (A1: the tile fetch and the entry's fields)
-          asm volatile("" ::"v"(sslot), "v"(sval));
+          asm volatile("" ::"v"(e.sslot), "v"(e.sval));
           stamp(tA1);
         }
-        int32_t uraw;
-        int mover_v;  // the column at the last position of `remaining`
+        return e;
+      };
+      // One step of the Dijkstra on row i's entry, in two instantiations.
+      // FIRST: the first step with everything a first step knows folded in
+      // -- u~ = 0 (a row's dual is first touched by its own Dijkstra) and
+      // minVal = 0, so the step's value is BIAS and t = 0; spc = inf, so sbp
+      // is the relaxation value itself; every column < n is live with its
+      // start tie bits, so the key takes LI and lo is not formed; no dual or
+      // mover read, no rowq store, no book-keeping.  A row with more than 32
+      // hits re-reads its columns in either (the one overflow path below,
+      // behind a scalar branch; a separate entry into the generic step for
+      // such rows made the Dijkstra's control flow one that the compiler
+      // linearises with lane masks, and its scalar operands VGPRs).  Both
+      // instantiations are entered and left with every lane active, by scalar
+      // branches on wave-uniform values only (the generic step's asm sets
+      // exec to -1).
+      auto step = [&](auto first_tag, const Entry e) __attribute__((always_inline)) {
+        constexpr bool FIRST = decltype(first_tag)::value;
+        first = false;
+        const uint32_t ea = e.ea;
+        const int sslot = e.sslot;
+        const int32_t sval = e.sval;
+        ++steps;
+        int32_t uraw = 0;
+        int mover_v = 0;  // the column at the last position of `remaining`
         int2 c01, c23;
         // The step's LDS traffic as one issue group for every row (a row with
         // more than 32 hits has the marker, whose slot is a dump slot, in its
@@ -3672,33 +3723,46 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
         const uint32_t sa = lds_addr(rowc) + 4u * (uint32_t)sslot;
         const int32_t miss = SP3_MISS;
         uint32_t sv;  // (the mover's slot, read, xor-ed and written back)
-        asm volatile(
-            "ds_read_b32 %0, %6\n\t"
-            "ds_read_b32 %1, %7\n\t"
-            "ds_write_b32 %8, %9\n\t"
-            "ds_read_b64 %2, %10\n\t"
-            "ds_read_b64 %3, %10 offset:512\n\t"
-            "ds_write_b32 %8, %11\n\t"
-            "ds_write_b32 %7, %6 offset:1024\n\t"
-            "s_mov_b64 exec, %12\n\t"
-            "s_set_gpr_idx_on %13, gpr_idx(DST)\n\t"
-            "v_mov_b32 " SH_VREG(SP3_LO_V) ", -1\n\t"
-            "s_set_gpr_idx_off\n\t"
-            "s_mov_b64 exec, %14\n\t"
-            "s_set_gpr_idx_on %15, gpr_idx(SRC0)\n\t"
-            "v_mov_b32 %4, " SH_VREG(SP3_LO_V) "\n\t"
-            "s_set_gpr_idx_off\n\t"
-            "v_xor_b32 %4, %16, %4\n\t"
-            "s_set_gpr_idx_on %15, gpr_idx(DST)\n\t"
-            "v_mov_b32 " SH_VREG(SP3_LO_V) ", %4\n\t"
-            "s_set_gpr_idx_off\n\t"
-            "s_mov_b64 exec, -1\n\t"
-            "s_waitcnt lgkmcnt(0)"
-            : "=&v"(uraw), "=&v"(mover_v), "=&v"(c01), "=&v"(c23), "=&v"(sv),
-              "+" SH_VTUPLE(SP3_LO_V, SP3_LO_VE)(lo)
-            : "v"(ua), "v"(ra), "v"(sa), "v"(sval), "v"(rob), "v"(miss), "s"(wmask), "s"(kw), "s"(mmask),
-              "s"(kmv), "v"(kX)
-            : "memory", "m0");
+        if constexpr (FIRST) {  // (the scatter, the row reads and the un-scatter only)
+          asm volatile(
+              "ds_write_b32 %2, %3\n\t"
+              "ds_read_b64 %0, %4\n\t"
+              "ds_read_b64 %1, %4 offset:512\n\t"
+              "ds_write_b32 %2, %5\n\t"
+              "s_waitcnt lgkmcnt(0)"
+              : "=&v"(c01), "=&v"(c23)
+              : "v"(sa), "v"(sval), "v"(rob), "v"(miss)
+              : "memory");
+        } else {
+          // (reached with every lane active only, see above: it leaves exec = -1)
+          asm volatile(
+              "ds_read_b32 %0, %6\n\t"
+              "ds_read_b32 %1, %7\n\t"
+              "ds_write_b32 %8, %9\n\t"
+              "ds_read_b64 %2, %10\n\t"
+              "ds_read_b64 %3, %10 offset:512\n\t"
+              "ds_write_b32 %8, %11\n\t"
+              "ds_write_b32 %7, %6 offset:1024\n\t"
+              "s_mov_b64 exec, %12\n\t"
+              "s_set_gpr_idx_on %13, gpr_idx(DST)\n\t"
+              "v_mov_b32 " SH_VREG(SP3_LO_V) ", -1\n\t"
+              "s_set_gpr_idx_off\n\t"
+              "s_mov_b64 exec, %14\n\t"
+              "s_set_gpr_idx_on %15, gpr_idx(SRC0)\n\t"
+              "v_mov_b32 %4, " SH_VREG(SP3_LO_V) "\n\t"
+              "s_set_gpr_idx_off\n\t"
+              "v_xor_b32 %4, %16, %4\n\t"
+              "s_set_gpr_idx_on %15, gpr_idx(DST)\n\t"
+              "v_mov_b32 " SH_VREG(SP3_LO_V) ", %4\n\t"
+              "s_set_gpr_idx_off\n\t"
+              "s_mov_b64 exec, -1\n\t"
+              "s_waitcnt lgkmcnt(0)"
+              : "=&v"(uraw), "=&v"(mover_v), "=&v"(c01), "=&v"(c23), "=&v"(sv),
+                "+" SH_VTUPLE(SP3_LO_V, SP3_LO_VE)(lo)
+              : "v"(ua), "v"(ra), "v"(sa), "v"(sval), "v"(rob), "v"(miss), "s"(wmask), "s"(kw), "s"(mmask),
+                "s"(kmv), "v"(kX)
+              : "memory", "m0");
+        }
         // (a row with more than 32 hits: the tile's entries and the overflow
         // list scattered again, the four columns re-read; the other half's
         // marker only sends a row without overflow through here, count 0)
@@ -3724,57 +3788,129 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
         // step's shared resource: every SALU removed shortened the round,
         // profiles/r05t_sp3_valu_addr_ab.jsonl)
         // (BIAS - u~ = mvb - u: the range term u~ + CU is (BIAS + CU) - that)
-        const uint32_t bu = mvb - (uint32_t)uraw;
-        accU |= ((uint32_t)SP3_BIAS + LR.CU) - bu;
-        const uint32_t bse = (bu << SP3_SH) | (uint32_t)(n - nrem);
+        // (FIRST: u~ = 0 is in range, CU has no bit of MU; the value is BIAS, t = 0)
+        uint32_t bse = (uint32_t)SP3_BIAS << SP3_SH;
+        if constexpr (!FIRST) {
+          const uint32_t bu = mvb - (uint32_t)uraw;
+          accU |= ((uint32_t)SP3_BIAS + LR.CU) - bu;
+          bse = (bu << SP3_SH) | (uint32_t)(n - nrem);
+        }
         if constexpr (TIMED) {
           asm volatile("" ::"v"(cc[0]), "v"(cc[3]), "v"(bse));
           stamp(tA);
         }
-        uint32_t best = ~0u;
+        best = ~0u;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           // (a removed column never improves: r >= minVal >= its spc, and its
           // t is older; its key is ~0 whatever sbp holds)
           const uint32_t r = (uint32_t)Wp[k] + (uint32_t)cc[k] + bse;
-          sbp[k] = r < sbp[k] ? r : sbp[k];
-          const uint32_t key = (sbp[k] & SP3_KMASK) | lo[k];
+          uint32_t key;
+          if constexpr (FIRST) {
+            sbp[k] = r;
+            key = (r & SP3_KMASK) | LI[k];
+          } else {
+            sbp[k] = r < sbp[k] ? r : sbp[k];
+            key = (sbp[k] & SP3_KMASK) | lo[k];
+          }
           best = key < best ? key : best;
         }
         // the row of this lane's best column (byte best & 3 of r4c): formed in
         // the DPP chain's wait states, one readlane of it below gives the next
         // row (the bit-field offset is (best << 3) mod 32)
-        const uint32_t rsel = __builtin_amdgcn_ubfe(r4c, best << 3, 8);
-        const uint32_t g = wave_min_u32_dpp(best);
+        rsel = __builtin_amdgcn_ubfe(r4c, best << 3, 8);
+        g = wave_min_u32_dpp(best);
         if constexpr (TIMED) {
           asm volatile("" ::"s"(g));
           stamp(tB);
         }
         mvb = g >> SP3_SH;
         kw = (int)(g & 3u);
-        const uint32_t pkey = (g >> 2) & 255u;
-        const bool assigned = (g >> 10) & 1u;
-        const int lw = (int)__builtin_ctzll(__builtin_amdgcn_ballot_w64(best == g));
-        const int pstar = assigned ? (int)pkey : 255 - (int)pkey;
-        const int last = nrem - 1;
-        asm("v_lshlrev_b32 %0, 2, %1" : "=v"(kX) : "s"(last ^ pstar));
-        wmask = 1ull << lw;
-        const int mv = __builtin_amdgcn_readfirstlane(mover_v);
-        mmask = 1ull << (mv >> 2);
-        kmv = mv & 3;
-        {  // rem[pstar] = mover (every lane, same word; a no-op when pstar == last)
-          uint32_t pa;
-          asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(pa) : "s"(pstar), "v"(remv));
-          asm volatile("ds_write_b32 %0, %1" ::"v"(pa), "v"(mover_v) : "memory");
+        assigned = g & (1u << 10);
+        if constexpr (!FIRST) {  // (the peeled step's tail or hand-over decodes the rest, below)
+          const uint32_t pkey = (g >> 2) & 255u;
+          const int lw = (int)__builtin_ctzll(__builtin_amdgcn_ballot_w64(best == g));
+          const int pstar = assigned ? (int)pkey : 255 - (int)pkey;
+          const int last = nrem - 1;
+          asm("v_lshlrev_b32 %0, 2, %1" : "=v"(kX) : "s"(last ^ pstar));
+          wmask = 1ull << lw;
+          const int mv = __builtin_amdgcn_readfirstlane(mover_v);
+          mmask = 1ull << (mv >> 2);
+          kmv = mv & 3;
+          {  // rem[pstar] = mover (every lane, same word; a no-op when pstar == last)
+            uint32_t pa;
+            asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(pa) : "s"(pstar), "v"(remv));
+            asm volatile("ds_write_b32 %0, %1" ::"v"(pa), "v"(mover_v) : "memory");
+          }
+          --nrem;
+          rq -= 4u;
+          // (branch-free: both the winner's column and its row are formed; the
+          // row is the next step's when assigned, the column is the sink if not)
+          sink = 4 * lw + kw;
+          i = __builtin_amdgcn_readlane((int)rsel, lw);
         }
-        --nrem;
-        rq -= 4u;
-        // (branch-free: both the winner's column and its row are formed; the
-        // row is the next step's when assigned, the column is the sink if not)
-        sink = 4 * lw + kw;
-        i = __builtin_amdgcn_readlane((int)rsel, lw);
-        if (!assigned) break;
+      };
+      step(std::true_type{}, fetch(cur, T0[(cur >> 2) & 31], T1[(cur >> 2) & 31]));
+      // the winner's lane (the one lane holding the key) and column
+      const uint64_t wl = __builtin_amdgcn_ballot_w64(best == g);
+      const int lw = (int)__builtin_ctzll(wl);
+      sink = 4 * lw + kw;
+      if (!assigned) {
+        // The single-step Dijkstra (the common case: DESIGN §4.0b): row cur
+        // takes the unassigned column that won the first scan, and nothing
+        // else changes -- no column was visited, the sink's dual moves by 0,
+        // the path is the one hop sink -> cur.  So u[cur] = minVal (it was
+        // 0), the bytes of c4r and r4c by lane compares (row cur was never
+        // assigned: its byte is 0xFF; column sink neither: its byte is 0),
+        // the sink's tie bits flipped; W, Wp, accW and `remaining` (still
+        // pristine: the hand-over resets it, not the set-up) stay.
+        stamp(tC);
+        {
+          uint32_t ua;
+          asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(ua) : "s"(cur), "v"(ubv));
+          const int32_t mval = (int32_t)mvb - SP3_BIAS;
+          asm volatile("ds_write_b32 %0, %1" ::"v"(ua), "v"(mval) : "memory");
+        }
+        const uint32_t dl = (uint32_t)cur - 2u * (uint32_t)ro0;  // cur - 4 lane: the row's byte in its lane
+        c4r ^= dl < 4u ? (0xFFu ^ (uint32_t)sink) << (8u * dl) : 0u;
+        r4c |= best == g ? (uint32_t)cur << ((best << 3) & 31u) : 0u;
+        flip_sink(wl, kw);
+        stamp(tD1);
+        stamp(tD2);
+        continue;
       }
+      // Hand-over: the state the generic loop holds after its step 0 -- the
+      // winner (assigned: pstar = pkey) leaves `remaining`, the mover is
+      // column 0 (rem[n - 1] of a pristine `remaining`), rowq[n - 1] = &u[cur]
+      lo = LI;
+      const int pstar = (int)((g >> 2) & 255u);
+      asm("v_lshlrev_b32 %0, 2, %1" : "=v"(kX) : "s"((n - 1) ^ pstar));
+      wmask = wl;
+      mmask = 1ull;
+      kmv = 0;
+      {  // `remaining` at a Dijkstra's start: rem[p] = n - 1 - p for this lane's p
+        // (formed here, from the opaque lane: four VGPRs less across the solve)
+        const uint32_t p0 = (uint32_t)(n - 1) - 4u * (uint32_t)ln;
+        *(uint4 *)(rem + 4 * ln) = make_uint4(p0, p0 - 1u, p0 - 2u, p0 - 3u);
+      }
+      rq = lds_addr(rem) + 4u * (uint32_t)(n - 1);  // &rem[n - 1], stepped down below
+      asm volatile("" : "+v"(rq));
+      {
+        uint32_t pa, ua;
+        const uint32_t zero = 0u;
+        asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(pa) : "s"(pstar), "v"(remv));
+        asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(ua) : "s"(cur), "v"(ubv));
+        asm volatile(
+            "ds_write_b32 %0, %1\n\t"
+            "ds_write_b32 %2, %3 offset:1024" ::"v"(pa), "v"(zero), "v"(rq), "v"(ua)
+            : "memory");
+      }
+      nrem = n - 1;
+      rq -= 4u;
+      i = __builtin_amdgcn_readlane((int)rsel, lw);
+      do {
+        step(std::false_type{}, fetch(i, T0[(i >> 2) & 31], T1[(i >> 2) & 31]));
+      } while (assigned);
       stamp(tC);
       // Dual update (scipy's, in V units, deferred to the Dijkstra's end): the
       // columns that left `remaining` (lo = ~0; not the sink, whose update is
@@ -3785,9 +3921,13 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
       i32x4 prow;  // (one VGPR tuple: the augmentation selects prow[j & 3] by an indexed move)
       // (the visited columns and the sink only, exec-masked: DESIGN §4.0b; 1 % faster
       //  here, 2-4 % slower in santa_dt_kernel: profiles/r05h_masked_dual_ab.jsonl)
+      // (the sink's slot in this lane as one value per Dijkstra, sink - 4 lane
+      //  against k: the four column indices 4 lane + k kept across the solve
+      //  were the VGPRs that the peeled step's code had no room for)
+      const uint32_t dsk = (uint32_t)sink - 4u * (uint32_t)ln;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const bool vk = (lo[k] == ~0u || 4 * lane + k == sink) && (4 * lane + k < n);
+        const bool vk = (lo[k] == ~0u || dsk == (uint32_t)k) && (4 * lane + k < n);
         if (vk) {
           const int32_t dd = (int32_t)(mvb - (sbp[k] >> SP3_SH));
           W[k] += dd;
@@ -3798,24 +3938,7 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
         accW |= (uint32_t)W[k] + LR.CW;
       }
       if (lane == 0) __hip_atomic_fetch_add(u_l + cur, minVal, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      {  // the sink is the one column this Dijkstra assigns: flip its start tie bits
-        uint64_t sv;
-        uint32_t tx;
-        asm volatile(
-            "s_mov_b64 %1, exec\n\t"
-            "s_mov_b64 exec, %3\n\t"
-            "s_set_gpr_idx_on %4, gpr_idx(SRC0)\n\t"
-            "v_mov_b32 %2, " SH_VREG(SP3_LI_V) "\n\t"
-            "s_set_gpr_idx_off\n\t"
-            "v_xor_b32 %2, 0x7fc, %2\n\t"
-            "s_set_gpr_idx_on %4, gpr_idx(DST)\n\t"
-            "v_mov_b32 " SH_VREG(SP3_LI_V) ", %2\n\t"
-            "s_set_gpr_idx_off\n\t"
-            "s_mov_b64 exec, %1"
-            : "+" SH_VTUPLE(SP3_LI_V, SP3_LI_VE)(LI), "=&s"(sv), "=&v"(tx)
-            : "s"(1ull << (sink >> 2)), "s"(sink & 3)
-            : "m0");
-      }
+      flip_sink(1ull << (sink >> 2), sink & 3);
       stamp(tD1);
       // augment along the path from the sink back to cur (registers only; at
       // most n hops -- a path that does not reach cur in n hops can only come
