@@ -1,0 +1,1034 @@
+// santa_api.inc — host half of libsanta_hip.so: the context, the design picker,
+// one launcher per design and the C-ABI (include/santa_hip.h).
+//
+// Not a translation unit of its own: santa_hip.hip includes it at its end,
+// because the kernels it launches by name are templates in that file's
+// anonymous namespace.  Host code lives here so that santa_hip.hip's hash (the
+// profile summaries' source_sha16) changes only when device code does.
+namespace {
+thread_local std::string g_err;
+
+int fail(int code, const std::string &msg) {
+  g_err = msg;
+  return code;
+}
+
+#define HIP_TRY(expr)                                                              \
+  do {                                                                             \
+    hipError_t e_ = (expr);                                                        \
+    if (e_ != hipSuccess)                                                          \
+      return fail(SH_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+#define HIP_TRY_RC(expr)            \
+  do {                              \
+    const int rc_ = (expr);         \
+    if (rc_ != SH_OK) return rc_;   \
+  } while (0)
+
+int pick_k(int n) {
+  if (n <= 64) return 1;
+  if (n <= 128) return 2;
+  if (n <= 256) return 4;
+  if (n <= 512) return 8;
+  return 16;
+}
+
+int64_t miss_units(int n_wish) {
+  const float e = (float)(1.0 / (2.0 * n_wish));
+  return (int64_t)((double)e * 2147483648.0);
+}
+
+// Makes `device` current for the lifetime of the guard and restores the
+// caller's device afterwards: every context entry point runs on the context's
+// device (allocations, kernel attributes, launches) whatever is current.
+struct DeviceGuard {
+  int prev = -1;
+  explicit DeviceGuard(int device) {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (prev != device) (void)hipSetDevice(device);
+  }
+  ~DeviceGuard() {
+    int cur = -1;
+    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+  }
+};
+
+// A workgroup's LDS on gfx950, and the dynamic LDS a kernel may ask for before
+// its hipFuncAttributeMaxDynamicSharedMemorySize has been raised.
+constexpr size_t LDS_MAX = 160 * 1024;
+constexpr size_t LDS_NO_ATTR = 64 * 1024;
+
+// Dynamic-LDS attribute already raised for a kernel, per device (attributes
+// are per device; a process may drive several).
+constexpr int MAX_DEVICES = 64;
+struct AttrCache {
+  size_t bytes[MAX_DEVICES] = {};
+  bool need(int dev, size_t want) const { return dev < 0 || dev >= MAX_DEVICES || bytes[dev] < want; }
+  void set(int dev, size_t b) {
+    if (dev >= 0 && dev < MAX_DEVICES) bytes[dev] = b;
+  }
+};
+
+}  // namespace
+
+struct sh_ctx {
+  int device;
+  int nc, ng, nq, n_wish, n_good;
+  int64_t E;
+  int16_t *d_wish = nullptr;
+  uint32_t *d_wish10 = nullptr;  // packed copy for the tile build (santa_tile_kernel<2>), or null
+  int32_t *d_csr_off = nullptr;
+  uint32_t *d_csr = nullptr;
+  int32_t *d_err = nullptr;
+  // sparse-tile kernel: LDS bytes per block (sets blocks per CU) and the
+  // double-buffered overflow lists [2 counters | 2 x ovf_cap block ids]
+  int sp_budget = 0;
+  int32_t *d_ovf = nullptr;
+  int ovf_cap = 0;
+  // register-tile sparse design: per-block tile records [rec_cap x SP2_REC]
+  unsigned char *d_rec = nullptr;
+  int rec_cap = 0;
+  int ovf_par = 0;
+  int n_cu = 0;          // compute units
+  int dt_slots = 0, dt_slots_n = -1;    // cached dt_tile_slots for one n (pick_design asks every round)
+  int64_t *h_mail = nullptr;             // host mailbox (sh_publish_delta): coherent, mapped
+  int64_t *d_mail = nullptr;             // its device address
+};
+
+namespace {
+constexpr int SP_DEFAULT_BUDGET = LDS_MAX / 8;  // 8 blocks (waves) per CU
+
+// Hit-list capacity (entries) of the sparse kernel under the LDS budget: what
+// is left after the fixed state and the 64 dump dwords; the hit area also has
+// to hold the counting-sort scratch (ng x u32), which may exceed the budget.
+int sp_capacity(const sh_ctx *ctx) {
+  const SpLds L0 = sp_lds_layout(ctx->ng, 0);
+  const size_t budget = (size_t)(ctx->sp_budget > 0 ? ctx->sp_budget : SP_DEFAULT_BUDGET);
+  const size_t fixed = L0.hits + 2 * 64 * 2;
+  if (budget <= fixed) return 0;
+  const size_t cap = (budget - fixed) / 2;
+  return (int)std::min<size_t>(cap & ~(size_t)7, 65528);
+}
+}  // namespace
+
+extern "C" {
+
+const char *sh_last_error(void) { return g_err.c_str(); }
+
+int sh_version(void) { return 1; }
+
+int sh_ctx_create(sh_ctx **out, int device, const int16_t *h_wish, int n_wish,
+                  const int32_t *h_goodkids, int n_good, int nc, int ng, int nq) {
+  if (!out || !h_wish || !h_goodkids) return fail(SH_ERR_ARGS, "null pointer");
+  *out = nullptr;
+  if (nc <= 0 || ng <= 0 || nq <= 0 || nc > (1 << 30))
+    return fail(SH_ERR_ARGS, "need nc, ng, nq > 0");
+  if (n_wish <= 0 || n_wish > 127 || n_wish > ng)
+    return fail(SH_ERR_ARGS, "n_wish must be in [1, min(127, ng)]");
+  if ((size_t)nc * (size_t)n_wish >= ((size_t)1 << 31))
+    return fail(SH_ERR_ARGS, "nc * n_wish must be below 2^31 (32-bit wishlist offsets)");
+  if (n_good <= 0 || n_good > 32767 || n_good > nc)
+    return fail(SH_ERR_ARGS, "n_good must be in [1, min(32767, nc)]");
+  if (ng > 8192) return fail(SH_ERR_ARGS, "ng > 8192 unsupported (LDS chain heads)");
+  // validate wishlists: in range and distinct per row
+  {
+    std::vector<uint32_t> seen((size_t)ng, 0xFFFFFFFFu);
+    for (int c = 0; c < nc; ++c) {
+      const int16_t *row = h_wish + (size_t)c * n_wish;
+      for (int r = 0; r < n_wish; ++r) {
+        const int g = row[r];
+        if (g < 0 || g >= ng) return fail(SH_ERR_ARGS, "wishlist gift id out of range");
+        if (seen[g] == (uint32_t)c) return fail(SH_ERR_ARGS, "wishlist row has a repeated gift");
+        seen[g] = (uint32_t)c;
+      }
+    }
+  }
+  // inverse good-kids CSR: child -> (gift << 16 | rank), gift-major, rank-ascending
+  std::vector<int32_t> off((size_t)nc + 1, 0);
+  {
+    std::vector<int32_t> seen((size_t)nc, -1);
+    for (int g = 0; g < ng; ++g)
+      for (int k = 0; k < n_good; ++k) {
+        const int c = h_goodkids[(size_t)g * n_good + k];
+        if (c < 0 || c >= nc) return fail(SH_ERR_ARGS, "good-kids child id out of range");
+        if (seen[c] == g) return fail(SH_ERR_ARGS, "good-kids row has a repeated child");
+        seen[c] = g;
+        off[(size_t)c + 1]++;
+      }
+  }
+  for (int c = 0; c < nc; ++c) off[(size_t)c + 1] += off[c];
+  std::vector<uint32_t> ent((size_t)off[nc]);
+  {
+    std::vector<int32_t> fillp(off.begin(), off.end() - 1);
+    for (int g = 0; g < ng; ++g)
+      for (int k = 0; k < n_good; ++k) {
+        const int c = h_goodkids[(size_t)g * n_good + k];
+        ent[(size_t)fillp[c]++] = ((uint32_t)g << 16) | (uint32_t)k;
+      }
+  }
+  // exactness guard for the twin cost decode (see one_hit_residual)
+  const int64_t E = miss_units(n_wish);
+  {
+    const float e = (float)(1.0 / (2.0 * n_wish));
+    if ((double)e * 2147483648.0 != (double)E)
+      return fail(SH_ERR_ARGS, "miss value not on the 2^-31 grid");
+    for (int a = 1; a <= n_wish; ++a) {
+      const float s = (float)(-2.0 * a) + e;
+      const int64_t units = (int64_t)((double)s * 2147483648.0);
+      if (units != (int64_t)(-a) * 4294967296LL + one_hit_residual(a, E))
+        return fail(SH_ERR_ARGS, "twin cost decode mismatch");
+    }
+    // the 4-wave twins kernel's tile entries (twin_entry) decode to the same costs
+    if (E <= 0 || E >= ((int64_t)1 << 31)) return fail(SH_ERR_ARGS, "miss value out of the entry decode's range");
+    const int nw1 = n_wish + 1;
+    for (int c1 = 0; c1 <= n_wish; ++c1)
+      for (int c2 = 0; c2 <= n_wish; ++c2) {
+        const int a1 = c1 ? nw1 - c1 : 0, a2 = c2 ? nw1 - c2 : 0, aa = a1 + a2;
+        const int64_t m = (c1 && c2) ? 0 : (c1 || c2) ? one_hit_residual(aa, E) : 2 * E;
+        const uint32_t e16 = twin_entry((uint32_t)c1 | ((uint32_t)c2 << 8), nw1, E);
+        if (e16 > 0xFFFFu || twin_entry_cost<0>(e16, (uint32_t)E) != (int64_t)(-aa) * 4294967296LL + m)
+          return fail(SH_ERR_ARGS, "twin tile entry decode mismatch");
+      }
+  }
+  DeviceGuard dg(device);  // the caller's device is current again on return
+  sh_ctx *ctx = new sh_ctx();
+  ctx->device = device;
+  ctx->nc = nc; ctx->ng = ng; ctx->nq = nq; ctx->n_wish = n_wish; ctx->n_good = n_good;
+  ctx->E = E;
+  auto cleanup = [&](int rc) { sh_ctx_destroy(ctx); return rc; };
+  hipError_t e;
+  if ((e = hipSetDevice(device)) != hipSuccess) return cleanup(fail(SH_ERR_HIP, hipGetErrorString(e)));
+  const size_t wb = (size_t)nc * n_wish * sizeof(int16_t);
+  if ((e = hipMalloc(&ctx->d_wish, wb + 16)) != hipSuccess ||
+      (e = hipMalloc(&ctx->d_csr_off, off.size() * 4)) != hipSuccess ||
+      (e = hipMalloc(&ctx->d_csr, std::max<size_t>(ent.size(), 1) * 4)) != hipSuccess ||
+      (e = hipMalloc(&ctx->d_err, 16)) != hipSuccess)
+    return cleanup(fail(SH_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e)));
+  if ((e = hipMemcpy(ctx->d_wish, h_wish, wb, hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemcpy(ctx->d_csr_off, off.data(), off.size() * 4, hipMemcpyHostToDevice)) != hipSuccess ||
+      (ent.size() && (e = hipMemcpy(ctx->d_csr, ent.data(), ent.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) ||
+      (e = hipMemset(ctx->d_err, 0, 16)) != hipSuccess)
+    return cleanup(fail(SH_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e)));
+  // the tile build's packed wishlist: gift r of a row at bits 10 r .. 10 r + 9
+  // of its 32-dword line (one 128-byte line per row instead of 200 bytes over
+  // two or three)
+  if (n_wish % 4 == 0 && n_wish <= 102 && ng <= 1024) {
+    std::vector<uint32_t> pk((size_t)nc * 32, 0u);
+    for (int c = 0; c < nc; ++c) {
+      const int16_t *row = h_wish + (size_t)c * n_wish;
+      uint32_t *dst = pk.data() + (size_t)c * 32;
+      for (int r = 0; r < n_wish; ++r) {
+        const uint32_t g = (uint32_t)row[r], bit = 10u * (uint32_t)r, sh = bit & 31u;
+        dst[bit >> 5] |= g << sh;
+        if (sh > 22u) dst[(bit >> 5) + 1] |= g >> (32u - sh);
+      }
+    }
+    if ((e = hipMalloc(&ctx->d_wish10, pk.size() * 4)) != hipSuccess ||
+        (e = hipMemcpy(ctx->d_wish10, pk.data(), pk.size() * 4, hipMemcpyHostToDevice)) != hipSuccess)
+      return cleanup(fail(SH_ERR_HIP, std::string("packed wishlist: ") + hipGetErrorString(e)));
+  }
+  if ((e = hipDeviceGetAttribute(&ctx->n_cu, hipDeviceAttributeMultiprocessorCount, device)) != hipSuccess)
+    return cleanup(fail(SH_ERR_HIP, hipGetErrorString(e)));
+  if ((e = hipHostMalloc((void **)&ctx->h_mail, 8 * sizeof(int64_t), hipHostMallocMapped | hipHostMallocCoherent)) !=
+          hipSuccess ||
+      (e = hipHostGetDevicePointer((void **)&ctx->d_mail, ctx->h_mail, 0)) != hipSuccess)
+    return cleanup(fail(SH_ERR_HIP, std::string("mailbox: ") + hipGetErrorString(e)));
+  for (int q = 0; q < 8; ++q) ctx->h_mail[q] = 0;
+  *out = ctx;
+  return SH_OK;
+}
+
+void sh_ctx_destroy(sh_ctx *ctx) {
+  if (!ctx) return;
+  DeviceGuard dg(ctx->device);
+  if (ctx->d_wish) (void)hipFree(ctx->d_wish);
+  if (ctx->d_wish10) (void)hipFree(ctx->d_wish10);
+  if (ctx->d_csr_off) (void)hipFree(ctx->d_csr_off);
+  if (ctx->d_csr) (void)hipFree(ctx->d_csr);
+  if (ctx->d_err) (void)hipFree(ctx->d_err);
+  if (ctx->d_ovf) (void)hipFree(ctx->d_ovf);
+  if (ctx->d_rec) (void)hipFree(ctx->d_rec);
+  if (ctx->h_mail) (void)hipHostFree(ctx->h_mail);
+  delete ctx;
+}
+
+int sh_ctx_set_sparse_budget(sh_ctx *ctx, int bytes) {
+  if (!ctx) return fail(SH_ERR_ARGS, "null ctx");
+  if (bytes < 0 || (size_t)bytes > LDS_MAX) return fail(SH_ERR_ARGS, "budget must be in [0, 160 KiB]");
+  ctx->sp_budget = bytes;
+  return sp_capacity(ctx);
+}
+
+int sh_ctx_error_flags(sh_ctx *ctx, void *stream) {
+  if (!ctx) return fail(SH_ERR_ARGS, "null ctx");
+  DeviceGuard dg(ctx->device);
+  int32_t h = 0;
+  HIP_TRY(hipMemcpyAsync(&h, ctx->d_err, 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  HIP_TRY(hipMemsetAsync(ctx->d_err, 0, 4, (hipStream_t)stream));
+  return h;
+}
+
+int sh_sample_blocks(uint64_t seed, uint64_t round, int lo, int count, int stride, int n, int B,
+                     int32_t *d_rows, void *stream) {
+  if (!d_rows || n <= 0 || B < 0 || count <= 0 || stride <= 0)
+    return fail(SH_ERR_ARGS, "bad sampler arguments");
+  if ((int64_t)n * B > count) return fail(SH_ERR_ARGS, "B * n exceeds the eligible count");
+  if (B == 0) return SH_OK;
+  const ShFeistel f = sh_feistel_make(seed, round, (uint64_t)count);
+  const int total = n * B;
+  hipLaunchKernelGGL(sample_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, f,
+                     lo, stride, total, d_rows, (const int16_t *)nullptr, (int16_t *)nullptr);
+  HIP_TRY(hipGetLastError());
+  return SH_OK;
+}
+
+int sh_sample_blocks_undo(uint64_t seed, uint64_t round, int lo, int count, int stride, int n, int B,
+                          int32_t *d_rows, const int16_t *d_types, int16_t *d_undo, void *stream) {
+  if (!d_rows || !d_types || !d_undo || n <= 0 || B < 0 || count <= 0 || stride <= 0)
+    return fail(SH_ERR_ARGS, "bad sampler arguments");
+  if ((int64_t)n * B > count) return fail(SH_ERR_ARGS, "B * n exceeds the eligible count");
+  if (B == 0) return SH_OK;
+  const ShFeistel f = sh_feistel_make(seed, round, (uint64_t)count);
+  const int total = n * B;
+  hipLaunchKernelGGL(sample_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, f,
+                     lo, stride, total, d_rows, d_types, d_undo);
+  HIP_TRY(hipGetLastError());
+  return SH_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// Raises Kern's dynamic-LDS attribute to `lds` bytes where a launch or an
+// occupancy query of that size needs it: above LDS_NO_ATTR, once per device
+// and kernel (each instantiation has its own cache), never lowering it.
+template <auto Kern>
+int raise_lds(const sh_ctx *ctx, size_t lds) {
+  static thread_local AttrCache attr;
+  if (lds > LDS_NO_ATTR && attr.need(ctx->device, lds)) {
+    HIP_TRY(hipFuncSetAttribute((const void *)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    attr.set(ctx->device, lds);
+  }
+  return SH_OK;
+}
+
+// Launches Kern with `lds` bytes of dynamic LDS; above LDS_MAX the launch is
+// refused with `too_big`.
+template <auto Kern, typename... Args>
+int launch_lds(const sh_ctx *ctx, const char *too_big, int grid, int block, size_t lds, hipStream_t s,
+               const Args &...args) {
+  if (lds > LDS_MAX) return fail(SH_ERR_ARGS, too_big);
+  HIP_TRY_RC(raise_lds<Kern>(ctx, lds));
+  hipLaunchKernelGGL(Kern, dim3(grid), dim3(block), lds, s, args...);
+  HIP_TRY(hipGetLastError());
+  return SH_OK;
+}
+
+// Blocks of Kern the device holds at once (occupancy API x CUs).
+template <auto Kern>
+int occ_blocks(const sh_ctx *ctx, int threads, size_t lds) {
+  int per_cu = 0;
+  if (lds > LDS_MAX) return 0;
+  (void)raise_lds<Kern>(ctx, lds);
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, Kern, threads, lds) != hipSuccess) return 0;
+  return per_cu * ctx->n_cu;
+}
+
+// A launch over a block list (the fallback launches) loops over its list: one
+// workgroup per CU.
+int list_grid(const sh_ctx *ctx, int B) { return std::max(1, std::min(B, ctx->n_cu)); }
+
+template <int K, int MODE, bool TIMED = false>
+int launch_santa(const sh_ctx *ctx, const SantaArgs &a, int B, hipStream_t s) {
+  return launch_lds<santa_block_kernel<K, MODE, TIMED>>(ctx, "block too large for the LDS tile", B, SANTA_WG,
+                                                        santa_lds_layout(a.n, MODE, ctx->ng).total, s, a);
+}
+
+template <int MODE, int SV = 0>
+int launch_santa_vt(const sh_ctx *ctx, const SantaArgs &a, int B, hipStream_t s) {
+  const VtLds L = vt_lds_layout(ctx->ng);
+  if (L.total > LDS_NO_ATTR) return fail(SH_ERR_ARGS, "too many gift types for the LDS chain heads");
+  if ((SV == 0) != (a.blist != nullptr)) return fail(SH_ERR_ARGS, "santa_vt_kernel<0, 0> is the fallback launch only");
+  hipLaunchKernelGGL((santa_vt_kernel<MODE, SV>), dim3(a.blist ? list_grid(ctx, B) : B), dim3(VT_WG), L.total, s, a);
+  HIP_TRY(hipGetLastError());
+  return SH_OK;
+}
+
+// LIST: the launch over santa_lb_kernel's block list (launch_big_list).
+template <int MODE, int NW, int K, int FB, bool LIST = false>
+int launch_big_cfg(const sh_ctx *ctx, const SantaArgs &a, int B, hipStream_t s) {
+  if (a.n > NW * WAVE * K) return fail(SH_ERR_ARGS, "large-block config covers fewer columns than n");
+  return launch_lds<santa_big_kernel<MODE, NW, K, FB, LIST>>(ctx, "block too large for LDS", LIST ? list_grid(ctx, B) : B,
+                                                             NW * WAVE, big_lds_layout(a.n, MODE, ctx->ng, NW, K).total,
+                                                             s, a);
+}
+
+// The fallback launch of santa_lb_kernel (singles): a workgroup per CU loops
+// over the listed blocks, in with_big_cfg's full-round configuration for
+// n <= LB_MAX_N (fewer waves per block: the loop's registers stay out of
+// scratch), spelled out so that only these list instantiations exist.
+int launch_big_list(const sh_ctx *ctx, const SantaArgs &a, int B, hipStream_t s) {
+  if (a.n <= 512) return launch_big_cfg<0, 2, 4, 10, true>(ctx, a, B, s);
+  if (a.n <= 1024) return launch_big_cfg<0, 4, 4, 10, true>(ctx, a, B, s);
+  return launch_big_cfg<0, 8, 4, 12, true>(ctx, a, B, s);
+}
+
+template <int NW_, int K_, int FB_>
+struct BigCfg {
+  static constexpr int NW = NW_, K = K_, FB = FB_;
+};
+
+// The santa_big_kernel configuration of a launch of B blocks of n rows, handed
+// to f as a BigCfg<NW, K, FB> tag: one picker for the launch and for its
+// occupancy (sh_resident_blocks), so the two cannot drift.
+// A full round (at least one block per CU: 477 blocks at n = 2000) runs
+// four columns per thread, so ceil(n / 256) waves per block -- fewer waves
+// per SIMD competing for issue between each block's barriers than 16: n =
+// 2000 round 0 113 -> 78 ms (8 waves; 4 waves x 8 columns: 93 ms), n = 1024
+// 101 -> 30 ms and n = 600 76 -> 21 ms (4 waves); the row rebuild takes one
+// thread per wish of a unit, (MODE + 1) * n_wish <= NW * 64.  A few blocks
+// (twins at 3000 pairs: 6 per round, triplets) keep the wider blocks (a
+// lone n = 2000 block: 52 ms at 16 waves, 55 at 8).
+// (profiles/r02c_big_rowbuild_ab.jsonl, profiles/r02c_big_nw_ab.jsonl)
+template <int MODE, typename F>
+int with_big_cfg(const sh_ctx *ctx, int n, int B, F &&f) {
+  const bool many = B >= ctx->n_cu;
+  if constexpr (MODE == 0) {
+    if (many && n <= 512) return f(BigCfg<2, 4, 10>{});
+  }
+  if constexpr (MODE <= 1) {
+    if (many && n > 512 && n <= 1024) return f(BigCfg<4, 4, 10>{});
+  }
+  if (n <= 512) return f(BigCfg<8, 1, 10>{});
+  if (n <= 1024) return f(BigCfg<16, 1, 10>{});
+  if (n <= 2048) return many ? f(BigCfg<8, 4, 12>{}) : f(BigCfg<16, 2, 12>{});
+  if (n <= 3072) return f(BigCfg<16, 3, 12>{});
+  return f(BigCfg<16, 4, 12>{});
+}
+
+// The overflow lists of the designs with a fallback launch (block ids, two
+// counters that alternate between calls).
+int ensure_ovf(sh_ctx *ctx, int B, hipStream_t s) {
+  if (ctx->ovf_cap < B) {
+    if (ctx->d_ovf) HIP_TRY(hipFree(ctx->d_ovf));
+    ctx->d_ovf = nullptr;
+    ctx->ovf_cap = 0;
+    const int capB = std::max(B, 4096);
+    HIP_TRY(hipMalloc(&ctx->d_ovf, (2 + 2 * (size_t)capB) * sizeof(int32_t)));
+    HIP_TRY(hipMemsetAsync(ctx->d_ovf, 0, 2 * sizeof(int32_t), s));
+    ctx->ovf_cap = capB;
+    ctx->ovf_par = 0;
+  }
+  return SH_OK;
+}
+
+// The designs with a fallback launch: `primary` appends the blocks it leaves
+// to an overflow list and `fallback` (launch_santa_vt<0, 0> or
+// launch_big_list) walks that list.  All of them share the context's two list
+// counters, which alternate between calls: the fallback launch of call k
+// resets the counter that call k + 1 appends to.
+template <typename P>
+int with_fallback(sh_ctx *ctx, SantaArgs a, int B, hipStream_t s, P &&primary,
+                  int (*fallback)(const sh_ctx *, const SantaArgs &, int, hipStream_t)) {
+  HIP_TRY_RC(ensure_ovf(ctx, B, s));
+  const int p = ctx->ovf_par;
+  a.ovf_cnt = ctx->d_ovf + p;
+  a.ovf_list = ctx->d_ovf + 2 + (size_t)p * ctx->ovf_cap;
+  a.blist = nullptr;
+  int rc = primary(a);
+  if (rc == SH_OK) {
+    SantaArgs f = a;
+    f.blist = a.ovf_list;
+    f.bcount = a.ovf_cnt;
+    f.ovf_reset = ctx->d_ovf + (p ^ 1);
+    f.undo = nullptr;
+    f.nx_rows = nullptr;
+    rc = fallback(ctx, f, B, s);
+  }
+  if (rc) {
+    // the primary launch may have appended to counter p: clear it so that a
+    // later call's fallback never walks these stale block ids
+    (void)hipMemsetAsync(ctx->d_ovf + p, 0, sizeof(int32_t), s);
+    return rc;
+  }
+  ctx->ovf_par = p ^ 1;
+  return SH_OK;
+}
+
+// santa_lb_kernel's configuration for n (NW * 64 * K >= n columns; the word's
+// table field holds 2 NW + 2 <= 63 tables)
+template <typename F>
+int with_lb_cfg(int n, F &&f) {
+  if (n <= 512) return f(BigCfg<2, 4, 0>{});
+  if (n <= 1024) return f(BigCfg<4, 4, 0>{});
+#if LB_CFG_2048 == 1
+  return f(BigCfg<4, 8, 0>{});
+#elif LB_CFG_2048 == 2
+  return f(BigCfg<16, 2, 0>{});
+#else
+  return f(BigCfg<8, 4, 0>{});
+#endif
+}
+
+size_t lb_lds_bytes(const sh_ctx *ctx, int n) {
+  return with_lb_cfg(n, [&](auto c) -> size_t {
+    using C = decltype(c);
+    return lb_lds_layout(n, ctx->ng, C::NW, C::K).total;
+  });
+}
+
+// singles blocks the staged-row lattice kernel takes: 256 < n <= 2048 whose
+// LDS fits (the tables hold ng int16 entries each), child ids below 2^20 (a
+// column's row and child share one 31-bit register)
+bool lb_eligible(const sh_ctx *ctx, int n, unsigned flags) {
+  return n > 256 && n <= LB_MAX_N && ctx->nc <= (1 << 20) && !(flags & SH_FLAG_BIG_ROWS) &&
+         lb_lds_bytes(ctx, n) <= LDS_MAX;
+}
+
+// santa_lb_kernel + santa_big_kernel over the blocks it left (out of its
+// lattice range; every block under SH_FLAG_TEST_RANGE / SH_FLAG_EXACT_ARGMIN).
+int launch_santa_lb(sh_ctx *ctx, const SantaArgs &args, int B, hipStream_t s) {
+  return with_fallback(ctx, args, B, s, [&](const SantaArgs &a) {
+    return with_lb_cfg(a.n, [&](auto c) -> int {
+      using C = decltype(c);
+      static_assert(2 * C::NW + 2 <= 63, "the step word's table field");
+      // (the slot sort's scratch: NCOL int16 slot entries in u's n int32)
+      if (C::NW * WAVE * C::K > 2 * a.n) return fail(SH_ERR_ARGS, "staged-row kernel: n too small for its config");
+      const char *too_big = "staged-row kernel: LDS above 160 KiB";
+      const size_t lds = lb_lds_layout(a.n, ctx->ng, C::NW, C::K).total;
+      return (a.flags & SH_FLAG_TIMING)
+                 ? launch_lds<santa_lb_kernel<C::NW, C::K, true>>(ctx, too_big, B, C::NW * WAVE, lds, s, a)
+                 : launch_lds<santa_lb_kernel<C::NW, C::K>>(ctx, too_big, B, C::NW * WAVE, lds, s, a);
+    });
+  }, launch_big_list);
+}
+
+template <int MODE>
+int launch_santa_big(const sh_ctx *ctx, const SantaArgs &a, int B, hipStream_t s) {
+  return with_big_cfg<MODE>(ctx, a.n, B, [&](auto c) {
+    using C = decltype(c);
+    return launch_big_cfg<MODE, C::NW, C::K, C::FB>(ctx, a, B, s);
+  });
+}
+
+// Register-tile 4-wave kernel in scaled units + the windowed-key launch over
+// the blocks it left (out of range; every block under the exact-argmin and
+// range test flags).
+int launch_santa_vt_sc(sh_ctx *ctx, const SantaArgs &args, int B, hipStream_t s) {
+  return with_fallback(ctx, args, B, s, [&](const SantaArgs &a) { return launch_santa_vt<0, 1>(ctx, a, B, s); },
+                       launch_santa_vt<0, 0>);
+}
+
+// Dense-tile one-wave kernel + the windowed-key launch over the blocks it
+// left (out of range; every block under the exact-argmin and range test
+// flags).
+int launch_santa_dt(sh_ctx *ctx, const SantaArgs &args, int B, hipStream_t s) {
+  // the tile holds rank codes (rank + 1) in uint8 with 255 the miss, and a
+  // miss's key-unit cost (n_wish + 1) << 20 | 2^11 must stay below 255 << 20:
+  // the same guard as the default dispatch, here also for the forced
+  // SH_FLAG_DT_TILE (sh_ctx_create caps n_wish at 127 today, well inside it)
+  if (ctx->n_wish > 253) return fail(SH_ERR_ARGS, "dense tile: n_wish > 253 does not fit the uint8 rank codes");
+  const size_t lds = dt_lds_layout(args.n, ctx->ng).total;
+  const char *too_big = "dense tile: too many gift types for LDS";
+  if (lds > LDS_MAX) return fail(SH_ERR_ARGS, too_big);  // (before the overflow lists are made)
+  return with_fallback(ctx, args, B, s, [&](const SantaArgs &a) {
+    return (a.flags & SH_FLAG_TIMING) ? launch_lds<santa_dt_kernel<true>>(ctx, too_big, B, SANTA_WG, lds, s, a)
+                                      : launch_lds<santa_dt_kernel<false>>(ctx, too_big, B, SANTA_WG, lds, s, a);
+  }, launch_santa_vt<0, 0>);
+}
+
+// Sparse-tile kernel + the fallback launch for blocks whose hit lists did not
+// fit.
+int launch_santa_sp(sh_ctx *ctx, SantaArgs args, int B, hipStream_t s, bool tile2) {
+  const int cap = sp_capacity(ctx);
+  const size_t lds = tile2 ? tile_lds_layout(ctx->ng).total : sp_lds_layout(ctx->ng, cap).total;
+  if (lds > LDS_NO_ATTR) return fail(SH_ERR_ARGS, "sparse-tile LDS budget above 64 KiB");
+  const bool fused = tile2 && ctx->d_wish10;  // (in-kernel build: packed wishlists only)
+  if (tile2 && !fused && ctx->rec_cap < B) {  // per-block tile records (HBM)
+    if (ctx->d_rec) HIP_TRY(hipFree(ctx->d_rec));
+    ctx->d_rec = nullptr;
+    ctx->rec_cap = 0;
+    const int capB = std::max(B, 4096);
+    HIP_TRY(hipMalloc(&ctx->d_rec, (size_t)capB * SP2_REC));
+    ctx->rec_cap = capB;
+  }
+  args.cap = cap;
+  if (tile2) {
+    // overflow capacity per block; a sparse budget set for tests lowers it
+    // (budget / 16 entries) so that some or all blocks take the fallback
+    const int ocap = fused ? SP4_OVF_CAP : SP2_OVF_CAP;
+    args.cap = ctx->sp_budget > 0 ? std::min(ocap, ctx->sp_budget / 16) : ocap;
+  }
+  const bool vec = ctx->n_wish % 4 == 0;
+  return with_fallback(ctx, args, B, s, [&](const SantaArgs &a) -> int {
+    if (fused) {  // one kernel: each wave builds its block's tile, then solves it
+      if (a.flags & SH_FLAG_TIMING)
+        hipLaunchKernelGGL((santa_sp3_kernel<true, true>), dim3(B), dim3(WAVE), 0, s, a, nullptr);
+      else
+        hipLaunchKernelGGL((santa_sp3_kernel<false, true>), dim3(B), dim3(WAVE), 0, s, a, nullptr);
+    } else if (tile2) {
+      if (vec)
+        hipLaunchKernelGGL(santa_tile_kernel<1>, dim3(B), dim3(TILE_NW * WAVE), lds, s, a, ctx->d_rec);
+      else
+        hipLaunchKernelGGL(santa_tile_kernel<0>, dim3(B), dim3(TILE_NW * WAVE), lds, s, a, ctx->d_rec);
+      HIP_TRY(hipGetLastError());
+      if (a.flags & SH_FLAG_TIMING)
+        hipLaunchKernelGGL((santa_sp3_kernel<true, false>), dim3(B), dim3(WAVE), 0, s, a,
+                           (const unsigned char *)ctx->d_rec);
+      else
+        hipLaunchKernelGGL((santa_sp3_kernel<false, false>), dim3(B), dim3(WAVE), 0, s, a,
+                           (const unsigned char *)ctx->d_rec);
+    } else if (vec)
+      hipLaunchKernelGGL(santa_sp_kernel<true>, dim3(B), dim3(WAVE), lds, s, a);
+    else
+      hipLaunchKernelGGL(santa_sp_kernel<false>, dim3(B), dim3(WAVE), lds, s, a);
+    HIP_TRY(hipGetLastError());
+    return SH_OK;
+  }, launch_santa_vt<0, 0>);
+}
+}  // namespace
+
+namespace {
+// Flags of designs that left the library: SH_FLAG_SW_TILE (the one-wave
+// register-tile kernel, round 3), SH_FLAG_SP2 (santa_sp2_kernel, round 2's
+// 64-bit-key one-wave kernel, round 4).
+int refuse_retired(unsigned flags) {
+  if (flags & SH_FLAG_SW_TILE)
+    return fail(SH_ERR_ARGS, "SH_FLAG_SW_TILE: the one-wave register-tile design is retired");
+  if (flags & SH_FLAG_SP2)
+    return fail(SH_ERR_ARGS, "SH_FLAG_SP2: the 64-bit-key one-wave design (santa_sp2_kernel) is retired");
+  return SH_OK;
+}
+
+// The mode, n and B of a solve or of a question about one.
+int check_mode_n_B(int mode, int n, int B) {
+  if (mode != SH_MODE_SINGLE && mode != SH_MODE_TWINS && mode != SH_MODE_TRIPLETS)
+    return fail(SH_ERR_ARGS, "bad mode");
+  if (n <= 0 || n > SH_MAX_N_SANTA) return fail(SH_ERR_ARGS, "n must be in [1, 4096]");
+  if (B < 0) return fail(SH_ERR_ARGS, "B < 0");
+  return SH_OK;
+}
+
+// Dense-tile one-wave blocks (singles) the device holds at once for this n;
+// cached for the last n, since pick_design asks every round.
+int dt_tile_slots(sh_ctx *ctx, int n) {
+  if (ctx->dt_slots_n != n) {
+    ctx->dt_slots = occ_blocks<santa_dt_kernel<false>>(ctx, SANTA_WG, dt_lds_layout(n, ctx->ng).total);
+    ctx->dt_slots_n = n;
+  }
+  return ctx->dt_slots;
+}
+
+int pick_design(sh_ctx *ctx, int mode, int n, int B, unsigned flags) {
+  // triplets (a few blocks per round: 1667 units) rebuild each row from the wishlists
+  if (n > 256 && mode == SH_MODE_SINGLE && lb_eligible(ctx, n, flags)) return SH_DESIGN_LARGE_LB;
+  if (n > 256 || mode == SH_MODE_TRIPLETS) return SH_DESIGN_LARGE;
+  // twins keep the LDS tile: their 128-dword register column does not stay
+  // in VGPRs (the compiler moves it to scratch), and a round has 78 blocks
+  // (a one-wave dense-tile twins kernel with 64-bit keys was built in round 4
+  // and measured 36 % slower than this 4-wave one: profiles/r04_twins_dt.jsonl)
+  if (mode == SH_MODE_TWINS) return SH_DESIGN_TWINS;
+  if (flags & SH_FLAG_LDS_TILE) return SH_DESIGN_LDS_TILE;
+  if (flags & SH_FLAG_DT_TILE) return SH_DESIGN_DT_TILE;
+  // (SH_FLAG_SW_TILE, the retired one-wave register-tile kernel, is refused
+  // by the entry points)
+  // the sparse kernel packs child ids (< 2^20) and gift types (< 1023) in one
+  // dword during its build; other instances take the register-tile kernel
+  if ((flags & SH_FLAG_VT_TILE) || ctx->nc > (1 << 20) || ctx->ng > 1022) return SH_DESIGN_VT_TILE;
+  // the register-tile sparse kernel keeps the wish value in 7 bits with one
+  // code reserved (n_wish <= 126); the LDS-list kernel takes the rest
+  const int sparse = (ctx->n_wish > 126 || (flags & SH_FLAG_SP1)) ? SH_DESIGN_SPARSE : SH_DESIGN_SPARSE3;
+  if (flags & (SH_FLAG_SP_TILE | SH_FLAG_SP1)) return sparse;
+  // few blocks (at most one resident wave of dense-tile blocks, two per CU):
+  // every block starts at once and the launch takes one block's latency,
+  // which the one-wave dense-tile kernel has lowest (round 4, MI355X, one
+  // GPU's shard of a round at 8 GPUs, 466 blocks: 1.13 ms at round 0 against
+  // 1.36 for the 4-wave LDS tile and 1.45 for the sparse kernel, 0.49 / 0.52
+  // / 0.65 ms at round 10; profiles/r04_shard_dt.jsonl).  Beyond it the
+  // sparse kernel: at 933 blocks (the shard at 4 GPUs) 1.52 ms against 1.60
+  // for the 4-wave register tile and 1.76 for two waves of dense-tile blocks.
+  if (ctx->n_wish <= 253 && B <= dt_tile_slots(ctx, n)) return SH_DESIGN_DT_TILE;
+  return sparse;
+}
+
+template <int MODE>
+int big_resident(const sh_ctx *ctx, int n, int B) {  // the configuration launch_santa_big picks
+  return with_big_cfg<MODE>(ctx, n, B, [&](auto c) {
+    using C = decltype(c);
+    return occ_blocks<santa_big_kernel<MODE, C::NW, C::K, C::FB>>(ctx, C::NW * WAVE,
+                                                                  big_lds_layout(n, MODE, ctx->ng, C::NW, C::K).total);
+  });
+}
+
+int resident_blocks(sh_ctx *ctx, int design, int mode, int n, int B) {
+  switch (design) {
+    case SH_DESIGN_LARGE:
+      return mode == SH_MODE_SINGLE ? big_resident<0>(ctx, n, B)
+             : mode == SH_MODE_TWINS ? big_resident<1>(ctx, n, B) : big_resident<2>(ctx, n, B);
+    case SH_DESIGN_LARGE_LB:
+      return with_lb_cfg(n, [&](auto c) {
+        using C = decltype(c);
+        return occ_blocks<santa_lb_kernel<C::NW, C::K>>(ctx, C::NW * WAVE, lb_lds_layout(n, ctx->ng, C::NW, C::K).total);
+      });
+    case SH_DESIGN_TWINS:
+      return occ_blocks<santa_block_kernel<1, 1>>(ctx, SANTA_WG, santa_lds_layout(n, 1, ctx->ng).total);
+    case SH_DESIGN_LDS_TILE:
+      return occ_blocks<santa_block_kernel<1, 0>>(ctx, SANTA_WG, santa_lds_layout(n, 0, ctx->ng).total);
+    case SH_DESIGN_DT_TILE: return dt_tile_slots(ctx, n);
+    case SH_DESIGN_VT_TILE: return occ_blocks<santa_vt_kernel<0, 1>>(ctx, VT_WG, vt_lds_layout(ctx->ng).total);
+    case SH_DESIGN_SPARSE3:
+      return ctx->d_wish10 ? occ_blocks<santa_sp3_kernel<false, true>>(ctx, WAVE, 0)
+                           : occ_blocks<santa_sp3_kernel<false, false>>(ctx, WAVE, 0);
+    default:
+      return occ_blocks<santa_sp_kernel<true>>(ctx, WAVE, sp_lds_layout(ctx->ng, sp_capacity(ctx)).total);
+  }
+}
+}  // namespace
+
+extern "C" {
+
+int sh_solve_blocks(sh_ctx *ctx, int mode, const int32_t *d_rows, int n, int B, int16_t *d_types,
+                    int32_t *d_col, int64_t *d_cost, int64_t *d_delta, int64_t *d_steps,
+                    unsigned flags, void *stream) {
+  return sh_solve_round(ctx, mode, d_rows, n, B, d_types, d_col, d_cost, d_delta, d_steps, nullptr, flags, stream);
+}
+
+int sh_solve_round(sh_ctx *ctx, int mode, const int32_t *d_rows, int n, int B, int16_t *d_types,
+                   int32_t *d_col, int64_t *d_cost, int64_t *d_delta, int64_t *d_steps, const sh_round_ext *ext,
+                   unsigned flags, void *stream) {
+  if (!ctx || (!d_rows && B > 0) || !d_types) return fail(SH_ERR_ARGS, "null pointer");
+  const bool sample = ext && ext->next_rows && ext->next_B > 0;
+  if (sample && (ext->next_count <= 0 || ext->next_stride <= 0 || (int64_t)n * ext->next_B > ext->next_count))
+    return fail(SH_ERR_ARGS, "bad next-round sampler arguments");
+  const bool publish = ext && ext->publish;
+  if (publish && (!d_delta || ext->publish_slot < 0 || ext->publish_slot > 1))
+    return fail(SH_ERR_ARGS, "bad mailbox arguments");
+  HIP_TRY_RC(check_mode_n_B(mode, n, B));
+  if ((int64_t)n * (mode + 1) > ctx->nc) return fail(SH_ERR_ARGS, "block larger than the instance");
+  {  // the next round's rows and the undo record are written while other
+     // workgroups still read this round's rows and types: no overlap allowed
+    auto overlap = [](const void *p, size_t np, const void *q, size_t nq) {
+      const uintptr_t a0 = (uintptr_t)p, b0 = (uintptr_t)q;
+      return p && q && np && nq && a0 < b0 + nq && b0 < a0 + np;
+    };
+    const size_t rows_b = (size_t)n * (size_t)B * 4, types_b = (size_t)ctx->nc * 2;
+    if (sample && (overlap(ext->next_rows, (size_t)n * ext->next_B * 4, d_rows, rows_b) ||
+                   overlap(ext->next_rows, (size_t)n * ext->next_B * 4, d_types, types_b)))
+      return fail(SH_ERR_ARGS, "next_rows overlaps d_rows or d_types");
+    if (ext && ext->d_undo && (overlap(ext->d_undo, (size_t)n * B * 2, d_rows, rows_b) ||
+                               overlap(ext->d_undo, (size_t)n * B * 2, d_types, types_b) ||
+                               (sample && overlap(ext->d_undo, (size_t)n * B * 2, ext->next_rows,
+                                                  (size_t)n * ext->next_B * 4))))
+      return fail(SH_ERR_ARGS, "d_undo overlaps d_rows, d_types or next_rows");
+  }
+  HIP_TRY_RC(refuse_retired(flags));
+  DeviceGuard dg(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (B == 0) {
+    if (publish) HIP_TRY_RC(sh_publish_delta(ctx, d_delta, ext->publish_slot, ext->publish_seq, stream));
+    return SH_OK;
+  }
+  SantaArgs a;
+  a.rows = d_rows; a.types = d_types; a.col = d_col; a.cost = d_cost; a.delta = d_delta;
+  a.steps = d_steps; a.wish = ctx->d_wish; a.wish10 = ctx->d_wish10; a.csr_off = ctx->d_csr_off; a.csr = ctx->d_csr;
+  a.err = ctx->d_err; a.E = ctx->E; a.n = n; a.nc = ctx->nc; a.ng = ctx->ng;
+  a.n_wish = ctx->n_wish; a.n_good = ctx->n_good; a.flags = flags;
+  a.cap = 0; a.ovf_cnt = nullptr; a.ovf_list = nullptr;
+  a.blist = nullptr; a.bcount = nullptr; a.ovf_reset = nullptr;
+  a.undo = ext ? ext->d_undo : nullptr;
+  a.nx_rows = nullptr;
+  a.nx_lo = a.nx_stride = a.nx_total = 0;
+  a.nx_f = ShFeistel{};
+  if (sample) {
+    a.nx_rows = ext->next_rows;
+    a.nx_f = sh_feistel_make(ext->next_seed, ext->next_round, (uint64_t)ext->next_count);
+    a.nx_lo = ext->next_lo;
+    a.nx_stride = ext->next_stride;
+    a.nx_total = n * ext->next_B;
+  }
+  a.pub_mail = nullptr;
+  a.pub_seq = 0;
+  a.pub_cnt = ctx->d_err + 2;
+  const int design = pick_design(ctx, mode, n, B, flags);
+  // designs whose last launch is the fallback santa_vt_kernel<0, 0>: its last
+  // workgroup publishes (one launch fewer between two rounds); the others
+  // enqueue publish_kernel after their launches
+  const bool fold = design == SH_DESIGN_SPARSE || design == SH_DESIGN_SPARSE3 || design == SH_DESIGN_DT_TILE ||
+                    design == SH_DESIGN_VT_TILE;
+  if (publish && fold) {
+    a.pub_mail = ctx->d_mail + 4 * ext->publish_slot;
+    a.pub_seq = ext->publish_seq;
+  }
+  int rc;
+  switch (design) {
+    case SH_DESIGN_LARGE:
+      rc = mode == SH_MODE_SINGLE ? launch_santa_big<0>(ctx, a, B, s)
+           : mode == SH_MODE_TWINS ? launch_santa_big<1>(ctx, a, B, s)
+                                   : launch_santa_big<2>(ctx, a, B, s);
+      break;
+    case SH_DESIGN_LARGE_LB: rc = launch_santa_lb(ctx, a, B, s); break;
+    case SH_DESIGN_TWINS:
+      rc = (flags & SH_FLAG_TIMING) ? launch_santa<1, 1, true>(ctx, a, B, s) : launch_santa<1, 1>(ctx, a, B, s);
+      break;
+    case SH_DESIGN_LDS_TILE:
+      rc = (flags & SH_FLAG_TIMING) ? launch_santa<1, 0, true>(ctx, a, B, s) : launch_santa<1, 0>(ctx, a, B, s);
+      break;
+    case SH_DESIGN_VT_TILE: rc = launch_santa_vt_sc(ctx, a, B, s); break;
+    case SH_DESIGN_DT_TILE: rc = launch_santa_dt(ctx, a, B, s); break;
+    case SH_DESIGN_SPARSE3: rc = launch_santa_sp(ctx, a, B, s, true); break;
+    default: rc = launch_santa_sp(ctx, a, B, s, false); break;
+  }
+  if (rc == SH_OK && publish && !fold) rc = sh_publish_delta(ctx, d_delta, ext->publish_slot, ext->publish_seq, stream);
+  return rc;
+}
+
+int sh_solve_design(sh_ctx *ctx, int mode, int n, int B, unsigned flags) {
+  if (!ctx) return fail(SH_ERR_ARGS, "null ctx");
+  HIP_TRY_RC(check_mode_n_B(mode, n, B));
+  HIP_TRY_RC(refuse_retired(flags));
+  DeviceGuard dg(ctx->device);
+  return pick_design(ctx, mode, n, B, flags);
+}
+
+int sh_resident_blocks(sh_ctx *ctx, int mode, int n, int B, unsigned flags) {
+  if (!ctx) return fail(SH_ERR_ARGS, "null ctx");
+  HIP_TRY_RC(check_mode_n_B(mode, n, B));
+  HIP_TRY_RC(refuse_retired(flags));
+  DeviceGuard dg(ctx->device);
+  return resident_blocks(ctx, pick_design(ctx, mode, n, B, flags), mode, n, B);
+}
+
+int sh_ctx_fallback_steps(sh_ctx *ctx, void *stream) {
+  if (!ctx) return fail(SH_ERR_ARGS, "null ctx");
+  DeviceGuard dg(ctx->device);
+  int32_t h = 0;
+  HIP_TRY(hipMemcpyAsync(&h, ctx->d_err + 1, 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  HIP_TRY(hipMemsetAsync(ctx->d_err + 1, 0, 4, (hipStream_t)stream));
+  return h;
+}
+
+int sh_score(sh_ctx *ctx, const int16_t *d_types, int64_t *d_sums, void *stream) {
+  if (!ctx || !d_types || !d_sums) return fail(SH_ERR_ARGS, "null pointer");
+  DeviceGuard dg(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(d_sums, 0, 4 * sizeof(int64_t), s));
+  ScoreArgs a;
+  a.wish = ctx->d_wish; a.csr_off = ctx->d_csr_off; a.csr = ctx->d_csr; a.types = d_types;
+  a.sums = d_sums; a.nc = ctx->nc; a.n_wish = ctx->n_wish; a.n_good = ctx->n_good;
+  const int twins = (int)ceil(0.04 * ctx->nc / 2.) * 2;
+  const int triplets = (int)ceil(0.005 * ctx->nc / 3.) * 3;
+  a.n_tri = triplets; a.n_twin = twins;
+  const int chunks = (ctx->nc + WAVE - 1) / WAVE;
+  const int grid = std::min((chunks + SCORE_WAVES - 1) / SCORE_WAVES, 2048);
+  hipLaunchKernelGGL(score_kernel, dim3(grid), dim3(WAVE * SCORE_WAVES), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return SH_OK;
+}
+
+int64_t *sh_ctx_mailbox(sh_ctx *ctx) { return ctx ? ctx->h_mail : nullptr; }
+
+int sh_publish_delta(sh_ctx *ctx, int64_t *d_delta, int slot, int64_t seq, void *stream) {
+  if (!ctx || !d_delta || slot < 0 || slot > 1) return fail(SH_ERR_ARGS, "bad mailbox arguments");
+  DeviceGuard dg(ctx->device);
+  hipLaunchKernelGGL(publish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, d_delta, ctx->d_mail + 4 * slot,
+                     seq);
+  HIP_TRY(hipGetLastError());
+  return SH_OK;
+}
+
+int sh_pack_types(const int16_t *d_types, const int32_t *d_rows, int count, int16_t *d_out,
+                  void *stream) {
+  if (count < 0) return fail(SH_ERR_ARGS, "count < 0");
+  if (count == 0) return SH_OK;
+  hipLaunchKernelGGL(pack_kernel, dim3((count + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                     d_types, d_rows, count, d_out);
+  HIP_TRY(hipGetLastError());
+  return SH_OK;
+}
+
+int sh_unpack_types(int16_t *d_types, const int32_t *d_rows, int count, const int16_t *d_in,
+                    int mode, void *stream) {
+  if (count < 0) return fail(SH_ERR_ARGS, "count < 0");
+  if (mode < SH_MODE_SINGLE || mode > SH_MODE_TRIPLETS) return fail(SH_ERR_ARGS, "bad mode");
+  if (count == 0) return SH_OK;
+  hipLaunchKernelGGL(unpack_kernel, dim3((count + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                     d_types, d_rows, count, d_in, mode);
+  HIP_TRY(hipGetLastError());
+  return SH_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// nr x nc instances (the square entries: nr == nc == n); host-side only.
+int check_lsap_args(int nr, int nc, int B, const int32_t *col) {
+  if (nr < 1 || nc > SH_MAX_N) return fail(SH_ERR_ARGS, "sizes must be in [1, 1024]");
+  if (nr > nc) return fail(SH_ERR_ARGS, "nr > nc: transpose tall input (as scipy does) and solve that");
+  if (B < 0) return fail(SH_ERR_ARGS, "B < 0");
+  if (!col && B > 0) return fail(SH_ERR_ARGS, "null col");
+  return SH_OK;
+}
+
+// The launch configuration follows the column slots nc (a thread owns K of
+// them, as in the square case); the LDS size the rows and columns.
+template <typename S, bool HASH>
+int launch_lsap_i64(const S *C, uint64_t seed, int64_t mod, int nr, int n, int B, const int32_t *shape,
+                    int32_t *col, int64_t *cost, unsigned flags, hipStream_t s) {
+  const int rc = check_lsap_args(nr, n, B, col);
+  if (rc || B == 0) return rc;
+  // The LDS sizes here and in launch_lsap_f64 mirror by hand how the kernels
+  // carve smem: lsap_i64_kernel's Sl.u / c4r / r4c / path / red lines (red
+  // sized for four waves whatever NW, plus 64 spare bytes), lsap_f64_mw_kernel's
+  // Sl.u / rv / rk / c4r / r4c / path lines, and lsap_f64_kernel's u_l and
+  // c4r_l.  A change to one side must be made on the other.
+  const size_t lds = r16((size_t)nr * 8) + r16((size_t)nr * 2) + 2 * r16((size_t)n * 2) +
+                     r16((size_t)4 * 4 * 8) + 64;
+  const bool rect = nr != n || shape;
+#define L__(NWW, KK, RR)                                                                            \
+  hipLaunchKernelGGL((lsap_i64_kernel<NWW, KK, S, HASH, RR>), dim3(B), dim3(NWW * WAVE), lds, s, C, \
+                     seed, mod, nr, n, shape, col, cost, (int32_t *)nullptr, flags)
+#define L_(NWW, KK)                \
+  do {                             \
+    if (rect) L__(NWW, KK, true);  \
+    else L__(NWW, KK, false);      \
+  } while (0)
+  // a batch that fills the chip many times over runs one wave per instance
+  // with several columns per thread (fewer waves per block, more blocks per
+  // CU: the large-block kernel's lesson): n <= 128 from 4096 instances
+  // (65536 hash-generated: 1.45 -> 2.49 M solves/s), n = 256 from 65536
+  // (397 -> 443 k/s; at 4096 it lost 17 %); n = 512 gained nothing
+  // (profiles/r02e_lsap_sweep_ab.jsonl)
+  if (n <= WAVE) L_(1, 1);
+  else if (B >= 4096 && n <= 128) L_(1, 2);
+  else if (B >= 65536 && n <= 256) L_(1, 4);
+  else if (n <= 256) L_(4, 1);
+  else if (n <= 512) L_(4, 2);
+  else L_(4, 4);
+#undef L_
+#undef L__
+  HIP_TRY(hipGetLastError());
+  return SH_OK;
+}
+
+// Whether a float batch of B instances with nc columns runs four waves per
+// instance by default (measured: DESIGN §7, profiles/lsap_float_ab.jsonl).
+// Up to 1024 instances one wave each leaves SIMDs idle and four waves won at
+// every nc measured (128: 5-9 %, 256: 17-22 %, 512: 29-36 %, 1024: 38-49 %);
+// at 4096 instances one wave each won (nc = 128, 256, 512), and nothing
+// between 1024 and 4096 was measured except nc = 256 (2048: four waves, 5 %),
+// so those batches keep the kernel they always ran.
+bool f64_mw_default(int nc, int B) { return nc > WAVE && B <= 1024; }
+
+// Floating-point costs stored as S (double, float, _Float16, sh_bf16), solved
+// in float64.  One wave per instance (lsap_f64_kernel) or, for nc > 64, four
+// (lsap_f64_mw_kernel, 1 / 2 / 4 columns per thread as the integer path's):
+// the default is f64_mw_default above, SH_FLAG_F64_MW / SH_FLAG_F64_SW force one.
+template <typename S>
+int launch_lsap_f64(const S *C, int nr, int n, int B, const int32_t *shape, int32_t *col,
+                    double *cost, unsigned flags, hipStream_t s) {
+  if (!C && B > 0) return fail(SH_ERR_ARGS, "null C");
+  const int rc = check_lsap_args(nr, n, B, col);
+  if (rc) return rc;
+  if ((flags & SH_FLAG_F64_MW) && (flags & SH_FLAG_F64_SW))
+    return fail(SH_ERR_ARGS, "SH_FLAG_F64_MW and SH_FLAG_F64_SW exclude each other");
+  if (B == 0) return SH_OK;
+  const bool mw = n > WAVE && !(flags & SH_FLAG_F64_SW) && ((flags & SH_FLAG_F64_MW) || f64_mw_default(n, B));
+  if (mw) {
+    constexpr int NW = 4;
+    const size_t lds = r16((size_t)nr * 8) + r16((size_t)2 * NW * 8) + r16((size_t)2 * NW * 4) +
+                       r16((size_t)nr * 2) + 2 * r16((size_t)n * 2);
+#define L_(KK)                                                                                     \
+  hipLaunchKernelGGL((lsap_f64_mw_kernel<NW, KK, S>), dim3(B), dim3(NW * WAVE), lds, s, C, nr, n, \
+                     shape, col, cost)
+    if (n <= 256) L_(1);
+    else if (n <= 512) L_(2);
+    else L_(4);
+#undef L_
+  } else {
+    const size_t lds = r16((size_t)nr * 8) + r16((size_t)nr * 2);
+#define L_(KK) \
+  hipLaunchKernelGGL((lsap_f64_kernel<KK, S>), dim3(B), dim3(WAVE), lds, s, C, nr, n, shape, col, cost)
+    switch (pick_k(n)) {
+      case 1: L_(1); break;
+      case 2: L_(2); break;
+      case 4: L_(4); break;
+      case 8: L_(8); break;
+      default: L_(16); break;
+    }
+#undef L_
+  }
+  HIP_TRY(hipGetLastError());
+  return SH_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int lsap_solve_batched_i64(const int64_t *d_C, int n, int B, int32_t *d_col, int64_t *d_cost,
+                           unsigned flags, void *stream) {
+  return lsap_solve_batched_rect_i64(d_C, n, n, B, nullptr, d_col, d_cost, flags, stream);
+}
+
+int lsap_solve_batched_i32(const int32_t *d_C, int n, int B, int32_t *d_col, int64_t *d_cost,
+                           unsigned flags, void *stream) {
+  return lsap_solve_batched_rect_i32(d_C, n, n, B, nullptr, d_col, d_cost, flags, stream);
+}
+
+int lsap_solve_batched_f64(const double *d_C, int n, int B, int32_t *d_col, double *d_cost,
+                           unsigned flags, void *stream) {
+  return lsap_solve_batched_rect_f64(d_C, n, n, B, nullptr, d_col, d_cost, flags, stream);
+}
+
+int lsap_solve_batched_hash(uint64_t seed, int64_t modulus, int n, int B, int32_t *d_col,
+                            int64_t *d_cost, unsigned flags, void *stream) {
+  return lsap_solve_batched_rect_hash(seed, modulus, n, n, B, d_col, d_cost, flags, stream);
+}
+
+// nr x nc instances, nr <= nc (the square entries above: nr == nc, no shapes).
+// Every check here is on the host and precedes the first device call.
+int lsap_solve_batched_rect_i64(const int64_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                int32_t *d_col, int64_t *d_cost, unsigned flags, void *stream) {
+  if (!d_C && B > 0) return fail(SH_ERR_ARGS, "null C");
+  return launch_lsap_i64<int64_t, false>(d_C, 0, 1, nr, nc, B, d_shape, d_col, d_cost, flags,
+                                         (hipStream_t)stream);
+}
+
+int lsap_solve_batched_rect_i32(const int32_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                int32_t *d_col, int64_t *d_cost, unsigned flags, void *stream) {
+  if (!d_C && B > 0) return fail(SH_ERR_ARGS, "null C");
+  return launch_lsap_i64<int32_t, false>(d_C, 0, 1, nr, nc, B, d_shape, d_col, d_cost, flags,
+                                         (hipStream_t)stream);
+}
+
+int lsap_solve_batched_rect_f64(const double *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                int32_t *d_col, double *d_cost, unsigned flags, void *stream) {
+  return launch_lsap_f64(d_C, nr, nc, B, d_shape, d_col, d_cost, flags, (hipStream_t)stream);
+}
+
+int lsap_solve_batched_rect_f32(const float *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                int32_t *d_col, double *d_cost, unsigned flags, void *stream) {
+  return launch_lsap_f64(d_C, nr, nc, B, d_shape, d_col, d_cost, flags, (hipStream_t)stream);
+}
+
+int lsap_solve_batched_rect_f16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                int32_t *d_col, double *d_cost, unsigned flags, void *stream) {
+  return launch_lsap_f64((const _Float16 *)d_C, nr, nc, B, d_shape, d_col, d_cost, flags,
+                         (hipStream_t)stream);
+}
+
+int lsap_solve_batched_rect_bf16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                 int32_t *d_col, double *d_cost, unsigned flags, void *stream) {
+  return launch_lsap_f64((const sh_bf16 *)d_C, nr, nc, B, d_shape, d_col, d_cost, flags,
+                         (hipStream_t)stream);
+}
+
+int lsap_solve_batched_rect_hash(uint64_t seed, int64_t modulus, int nr, int nc, int B,
+                                 int32_t *d_col, int64_t *d_cost, unsigned flags, void *stream) {
+  if (modulus <= 0) return fail(SH_ERR_ARGS, "modulus must be > 0");
+  return launch_lsap_i64<int64_t, true>(nullptr, seed, modulus, nr, nc, B, nullptr, d_col, d_cost,
+                                        flags, (hipStream_t)stream);
+}
+
+}  // extern "C"
