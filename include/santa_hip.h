@@ -372,6 +372,88 @@ int lsap_solve_batched_rect_hash(uint64_t seed, int64_t modulus, int nr, int nc,
                                  int32_t *d_col, int64_t *d_cost, unsigned flags, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * The same solves, returning the dual variables the shortest-augmenting-path
+ * run ends with.  Semantics, host checks, flags and launch configurations are
+ * those of the _rect_ entries; col and cost are the same bits.
+ *   d_u  [B x nr], d_v [B x nc]: int64 (i64, i32) or double (f64, f32, f16,
+ *        bf16), in the units of C with scipy's sign convention:
+ *          u[i] + v[j] <= C[i][j] on the live corner, with equality on the
+ *          chosen entries; v <= 0, and v == 0 on a column no row took;
+ *          sum u + sum v == cost.
+ *        Integer duals satisfy all of it exactly (|C| < 2^50 keeps them below
+ *        2^62).  Float duals are the bits of scipy's own float64 run, feasible
+ *        up to its rounding.  The padded rows and columns of a ragged instance
+ *        get 0, every slot of an empty or invalid-shape instance gets 0, and
+ *        the live slots of an infeasible float instance (col = -1) get NaN.
+ * Both are required: SH_ERR_ARGS for a null d_u or d_v with B > 0.
+ * ------------------------------------------------------------------------ */
+int lsap_solve_batched_duals_i64(const int64_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                 int32_t *d_col, int64_t *d_cost, int64_t *d_u, int64_t *d_v,
+                                 unsigned flags, void *stream);
+int lsap_solve_batched_duals_i32(const int32_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                 int32_t *d_col, int64_t *d_cost, int64_t *d_u, int64_t *d_v,
+                                 unsigned flags, void *stream);
+int lsap_solve_batched_duals_f64(const double *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                 int32_t *d_col, double *d_cost, double *d_u, double *d_v,
+                                 unsigned flags, void *stream);
+int lsap_solve_batched_duals_f32(const float *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                 int32_t *d_col, double *d_cost, double *d_u, double *d_v,
+                                 unsigned flags, void *stream);
+int lsap_solve_batched_duals_f16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                 int32_t *d_col, double *d_cost, double *d_u, double *d_v,
+                                 unsigned flags, void *stream);
+int lsap_solve_batched_duals_bf16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                  int32_t *d_col, double *d_cost, double *d_u, double *d_v,
+                                  unsigned flags, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * The certificate: one pass over the live corner of every instance checks
+ * (d_col, d_u, d_v) against d_C on the device.  Shapes and host checks as
+ * above (d_C, d_col, d_u, d_v, d_slack and d_flags are required for B > 0).
+ *   d_slack [B x 3], int64 (i64, i32) or double:
+ *     [0] min over live (i, j) of (C[i][j] - u[i]) - v[j], in that order of
+ *         operations (floats: -0.0 orders below +0.0, a NaN slack gives NaN;
+ *         0 when there is no live entry)
+ *     [1] max over live rows of |(C[i][col[i]] - u[i]) - v[col[i]]|
+ *     [2] (sum u + sum v) - sum C[i][col[i]]; floats in a fixed order: each
+ *         sum is taken by 256 threads, thread t adding its elements t,
+ *         t + 256, .. ascending, the 64 partial sums of a wave combined by the
+ *         xor butterfly 32, 16, .. 1 and the four waves added in order
+ *   d_flags int32 [B]: SH_CERT_* bits.  For the integer entries 0 proves the
+ *     instance optimal (integer arithmetic wraps; SH_CERT_RANGE marks every
+ *     instance in which it could have, and the other bits are then
+ *     unspecified).  Three launches on `stream`; nothing is allocated.
+ * ------------------------------------------------------------------------ */
+#define SH_CERT_COL 1    /* col is not an assignment of the live rows: a value outside
+                            [0, nc_b), a column taken twice, a live row without a column
+                            next to one with, a padded row whose col is not -1, or a
+                            shape outside the padded matrix */
+#define SH_CERT_SLACK 2  /* the minimum slack is below 0 (or NaN) */
+#define SH_CERT_TIGHT 4  /* a matched slack is not 0 */
+#define SH_CERT_SIGN 8   /* some v[j] > 0, or v[j] != 0 on a live column no row took */
+#define SH_CERT_GAP 16   /* integer entries: the gap is not 0 */
+#define SH_CERT_NONE 32  /* every live row has col == -1: nothing else is checked */
+#define SH_CERT_RANGE 64 /* integer entries: some |u|, |v| or (i64) live |C| >= 2^61 */
+int lsap_check_duals_i64(const int64_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                         const int32_t *d_col, const int64_t *d_u, const int64_t *d_v,
+                         int64_t *d_slack, int32_t *d_flags, void *stream);
+int lsap_check_duals_i32(const int32_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                         const int32_t *d_col, const int64_t *d_u, const int64_t *d_v,
+                         int64_t *d_slack, int32_t *d_flags, void *stream);
+int lsap_check_duals_f64(const double *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                         const int32_t *d_col, const double *d_u, const double *d_v,
+                         double *d_slack, int32_t *d_flags, void *stream);
+int lsap_check_duals_f32(const float *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                         const int32_t *d_col, const double *d_u, const double *d_v,
+                         double *d_slack, int32_t *d_flags, void *stream);
+int lsap_check_duals_f16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                         const int32_t *d_col, const double *d_u, const double *d_v,
+                         double *d_slack, int32_t *d_flags, void *stream);
+int lsap_check_duals_bf16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                          const int32_t *d_col, const double *d_u, const double *d_v,
+                          double *d_slack, int32_t *d_flags, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Synthetic data of the Kaggle shape (host, deterministic, seeded counter
  * PRNG).  Wishlists: n_wish distinct gift types per child; good-kids: n_good
  * distinct children per gift; baseline: a feasible assignment (triplets and

@@ -873,11 +873,15 @@ int check_lsap_args(int nr, int nc, int B, const int32_t *col) {
 
 // The launch configuration follows the column slots nc (a thread owns K of
 // them, as in the square case); the LDS size the rows and columns.
-template <typename S, bool HASH>
+// DUALS: the kernels' duals form (du, dv required), same configurations.
+template <typename S, bool HASH, bool DUALS = false>
 int launch_lsap_i64(const S *C, uint64_t seed, int64_t mod, int nr, int n, int B, const int32_t *shape,
-                    int32_t *col, int64_t *cost, unsigned flags, hipStream_t s) {
+                    int32_t *col, int64_t *cost, unsigned flags, hipStream_t s, int64_t *du = nullptr,
+                    int64_t *dv = nullptr) {
   const int rc = check_lsap_args(nr, n, B, col);
-  if (rc || B == 0) return rc;
+  if (rc) return rc;
+  if (DUALS && (!du || !dv) && B > 0) return fail(SH_ERR_ARGS, "null u or v");
+  if (B == 0) return SH_OK;
   // The LDS sizes here and in launch_lsap_f64 mirror by hand how the kernels
   // carve smem: lsap_i64_kernel's Sl.u / c4r / r4c / path / red lines (red
   // sized for four waves whatever NW, plus 64 spare bytes), lsap_f64_mw_kernel's
@@ -889,10 +893,14 @@ int launch_lsap_i64(const S *C, uint64_t seed, int64_t mod, int nr, int n, int B
 #define L__(NWW, KK, RR)                                                                            \
   hipLaunchKernelGGL((lsap_i64_kernel<NWW, KK, S, HASH, RR>), dim3(B), dim3(NWW * WAVE), lds, s, C, \
                      seed, mod, nr, n, shape, col, cost, (int32_t *)nullptr, flags)
-#define L_(NWW, KK)                \
-  do {                             \
-    if (rect) L__(NWW, KK, true);  \
-    else L__(NWW, KK, false);      \
+#define L_(NWW, KK)                                                                                  \
+  do {                                                                                               \
+    if constexpr (DUALS)                                                                             \
+      hipLaunchKernelGGL((lsap_i64_kernel<NWW, KK, S, HASH, true, int64_t *, int64_t *>), dim3(B),   \
+                         dim3(NWW * WAVE), lds, s, C, seed, mod, nr, n, shape, col, cost,            \
+                         (int32_t *)nullptr, flags, du, dv);                                         \
+    else if (rect) L__(NWW, KK, true);                                                               \
+    else L__(NWW, KK, false);                                                                        \
   } while (0)
   // a batch that fills the chip many times over runs one wave per instance
   // with several columns per thread (fewer waves per block, more blocks per
@@ -925,12 +933,14 @@ bool f64_mw_default(int nc, int B) { return nc > WAVE && B <= 1024; }
 // in float64.  One wave per instance (lsap_f64_kernel) or, for nc > 64, four
 // (lsap_f64_mw_kernel, 1 / 2 / 4 columns per thread as the integer path's):
 // the default is f64_mw_default above, SH_FLAG_F64_MW / SH_FLAG_F64_SW force one.
-template <typename S>
+template <typename S, bool DUALS = false>
 int launch_lsap_f64(const S *C, int nr, int n, int B, const int32_t *shape, int32_t *col,
-                    double *cost, unsigned flags, hipStream_t s) {
+                    double *cost, unsigned flags, hipStream_t s, double *du = nullptr,
+                    double *dv = nullptr) {
   if (!C && B > 0) return fail(SH_ERR_ARGS, "null C");
   const int rc = check_lsap_args(nr, n, B, col);
   if (rc) return rc;
+  if (DUALS && (!du || !dv) && B > 0) return fail(SH_ERR_ARGS, "null u or v");
   if ((flags & SH_FLAG_F64_MW) && (flags & SH_FLAG_F64_SW))
     return fail(SH_ERR_ARGS, "SH_FLAG_F64_MW and SH_FLAG_F64_SW exclude each other");
   if (B == 0) return SH_OK;
@@ -939,17 +949,30 @@ int launch_lsap_f64(const S *C, int nr, int n, int B, const int32_t *shape, int3
     constexpr int NW = 4;
     const size_t lds = r16((size_t)nr * 8) + r16((size_t)2 * NW * 8) + r16((size_t)2 * NW * 4) +
                        r16((size_t)nr * 2) + 2 * r16((size_t)n * 2);
-#define L_(KK)                                                                                     \
-  hipLaunchKernelGGL((lsap_f64_mw_kernel<NW, KK, S>), dim3(B), dim3(NW * WAVE), lds, s, C, nr, n, \
-                     shape, col, cost)
+#define L_(KK)                                                                                        \
+  do {                                                                                                \
+    if constexpr (DUALS)                                                                              \
+      hipLaunchKernelGGL((lsap_f64_mw_kernel<NW, KK, S, double *, double *>), dim3(B),                \
+                         dim3(NW * WAVE), lds, s, C, nr, n, shape, col, cost, du, dv);                \
+    else                                                                                              \
+      hipLaunchKernelGGL((lsap_f64_mw_kernel<NW, KK, S>), dim3(B), dim3(NW * WAVE), lds, s, C, nr, n, \
+                         shape, col, cost);                                                           \
+  } while (0)
     if (n <= 256) L_(1);
     else if (n <= 512) L_(2);
     else L_(4);
 #undef L_
   } else {
     const size_t lds = r16((size_t)nr * 8) + r16((size_t)nr * 2);
-#define L_(KK) \
-  hipLaunchKernelGGL((lsap_f64_kernel<KK, S>), dim3(B), dim3(WAVE), lds, s, C, nr, n, shape, col, cost)
+#define L_(KK)                                                                                       \
+  do {                                                                                               \
+    if constexpr (DUALS)                                                                             \
+      hipLaunchKernelGGL((lsap_f64_kernel<KK, S, double *, double *>), dim3(B), dim3(WAVE), lds, s,  \
+                         C, nr, n, shape, col, cost, du, dv);                                        \
+    else                                                                                             \
+      hipLaunchKernelGGL((lsap_f64_kernel<KK, S>), dim3(B), dim3(WAVE), lds, s, C, nr, n, shape,     \
+                         col, cost);                                                                 \
+  } while (0)
     switch (pick_k(n)) {
       case 1: L_(1); break;
       case 2: L_(2); break;
@@ -959,6 +982,36 @@ int launch_lsap_f64(const S *C, int nr, int n, int B, const int32_t *shape, int3
     }
 #undef L_
   }
+  HIP_TRY(hipGetLastError());
+  return SH_OK;
+}
+
+// The certificate (lsap_cert_kernel, lsap_slack_kernel, lsap_cert_final_kernel):
+// S the stored cost type, T int64_t or double.  The pass over the corners
+// reads 16 bytes per load when every row starts 16-byte aligned; a batch too
+// small to fill the chip with one workgroup per instance is split by rows.
+template <typename S, typename T>
+int launch_lsap_check(const S *C, int nr, int n, int B, const int32_t *shape, const int32_t *col,
+                      const T *u, const T *v, T *slack, int32_t *flg, hipStream_t s) {
+  const int rc = check_lsap_args(nr, n, B, col);
+  if (rc) return rc;
+  if (B > 0 && (!C || !u || !v || !slack || !flg)) return fail(SH_ERR_ARGS, "null C, u, v, slack or flags");
+  if (B == 0) return SH_OK;
+  hipLaunchKernelGGL((lsap_cert_kernel<S, T>), dim3(B), dim3(CERT_WG), 0, s, C, nr, n, shape, col, u, v,
+                     slack, flg);
+  // at least 8 rows per workgroup, about 2048 workgroups when the batch allows
+  const int chunks = std::min(std::max(1, 2048 / B), (nr + 7) / 8);
+  const int rows_per = (nr + chunks - 1) / chunks;
+  const dim3 grid(B, (nr + rows_per - 1) / rows_per);
+  constexpr int VEC = 16 / (int)sizeof(S);
+  if ((uintptr_t)C % 16 == 0 && n % VEC == 0)
+    hipLaunchKernelGGL((lsap_slack_kernel<S, T, VEC>), grid, dim3(CERT_WG), 0, s, C, nr, n, shape, u, v,
+                       slack, flg, rows_per);
+  else
+    hipLaunchKernelGGL((lsap_slack_kernel<S, T, 1>), grid, dim3(CERT_WG), 0, s, C, nr, n, shape, u, v,
+                       slack, flg, rows_per);
+  hipLaunchKernelGGL((lsap_cert_final_kernel<T>), dim3((B + CERT_WG - 1) / CERT_WG), dim3(CERT_WG), 0, s,
+                     B, slack, flg);
   HIP_TRY(hipGetLastError());
   return SH_OK;
 }
@@ -1029,6 +1082,89 @@ int lsap_solve_batched_rect_hash(uint64_t seed, int64_t modulus, int nr, int nc,
   if (modulus <= 0) return fail(SH_ERR_ARGS, "modulus must be > 0");
   return launch_lsap_i64<int64_t, true>(nullptr, seed, modulus, nr, nc, B, nullptr, d_col, d_cost,
                                         flags, (hipStream_t)stream);
+}
+
+// The duals forms of the six entries above (the same checks and launches).
+int lsap_solve_batched_duals_i64(const int64_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                 int32_t *d_col, int64_t *d_cost, int64_t *d_u, int64_t *d_v,
+                                 unsigned flags, void *stream) {
+  if (!d_C && B > 0) return fail(SH_ERR_ARGS, "null C");
+  return launch_lsap_i64<int64_t, false, true>(d_C, 0, 1, nr, nc, B, d_shape, d_col, d_cost, flags,
+                                               (hipStream_t)stream, d_u, d_v);
+}
+
+int lsap_solve_batched_duals_i32(const int32_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                 int32_t *d_col, int64_t *d_cost, int64_t *d_u, int64_t *d_v,
+                                 unsigned flags, void *stream) {
+  if (!d_C && B > 0) return fail(SH_ERR_ARGS, "null C");
+  return launch_lsap_i64<int32_t, false, true>(d_C, 0, 1, nr, nc, B, d_shape, d_col, d_cost, flags,
+                                               (hipStream_t)stream, d_u, d_v);
+}
+
+int lsap_solve_batched_duals_f64(const double *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                 int32_t *d_col, double *d_cost, double *d_u, double *d_v,
+                                 unsigned flags, void *stream) {
+  return launch_lsap_f64<double, true>(d_C, nr, nc, B, d_shape, d_col, d_cost, flags, (hipStream_t)stream,
+                                       d_u, d_v);
+}
+
+int lsap_solve_batched_duals_f32(const float *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                 int32_t *d_col, double *d_cost, double *d_u, double *d_v,
+                                 unsigned flags, void *stream) {
+  return launch_lsap_f64<float, true>(d_C, nr, nc, B, d_shape, d_col, d_cost, flags, (hipStream_t)stream,
+                                      d_u, d_v);
+}
+
+int lsap_solve_batched_duals_f16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                 int32_t *d_col, double *d_cost, double *d_u, double *d_v,
+                                 unsigned flags, void *stream) {
+  return launch_lsap_f64<_Float16, true>((const _Float16 *)d_C, nr, nc, B, d_shape, d_col, d_cost, flags,
+                                         (hipStream_t)stream, d_u, d_v);
+}
+
+int lsap_solve_batched_duals_bf16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                                  int32_t *d_col, double *d_cost, double *d_u, double *d_v,
+                                  unsigned flags, void *stream) {
+  return launch_lsap_f64<sh_bf16, true>((const sh_bf16 *)d_C, nr, nc, B, d_shape, d_col, d_cost, flags,
+                                        (hipStream_t)stream, d_u, d_v);
+}
+
+int lsap_check_duals_i64(const int64_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                         const int32_t *d_col, const int64_t *d_u, const int64_t *d_v,
+                         int64_t *d_slack, int32_t *d_flags, void *stream) {
+  return launch_lsap_check(d_C, nr, nc, B, d_shape, d_col, d_u, d_v, d_slack, d_flags, (hipStream_t)stream);
+}
+
+int lsap_check_duals_i32(const int32_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                         const int32_t *d_col, const int64_t *d_u, const int64_t *d_v,
+                         int64_t *d_slack, int32_t *d_flags, void *stream) {
+  return launch_lsap_check(d_C, nr, nc, B, d_shape, d_col, d_u, d_v, d_slack, d_flags, (hipStream_t)stream);
+}
+
+int lsap_check_duals_f64(const double *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                         const int32_t *d_col, const double *d_u, const double *d_v,
+                         double *d_slack, int32_t *d_flags, void *stream) {
+  return launch_lsap_check(d_C, nr, nc, B, d_shape, d_col, d_u, d_v, d_slack, d_flags, (hipStream_t)stream);
+}
+
+int lsap_check_duals_f32(const float *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                         const int32_t *d_col, const double *d_u, const double *d_v,
+                         double *d_slack, int32_t *d_flags, void *stream) {
+  return launch_lsap_check(d_C, nr, nc, B, d_shape, d_col, d_u, d_v, d_slack, d_flags, (hipStream_t)stream);
+}
+
+int lsap_check_duals_f16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                         const int32_t *d_col, const double *d_u, const double *d_v,
+                         double *d_slack, int32_t *d_flags, void *stream) {
+  return launch_lsap_check((const _Float16 *)d_C, nr, nc, B, d_shape, d_col, d_u, d_v, d_slack, d_flags,
+                           (hipStream_t)stream);
+}
+
+int lsap_check_duals_bf16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                          const int32_t *d_col, const double *d_u, const double *d_v,
+                          double *d_slack, int32_t *d_flags, void *stream) {
+  return launch_lsap_check((const sh_bf16 *)d_C, nr, nc, B, d_shape, d_col, d_u, d_v, d_slack, d_flags,
+                           (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -113,8 +113,18 @@ __device__ __forceinline__ A pick(const A (&arr)[K], int k) {
 // (infeasible: only possible for float64 with +inf entries; with nr < n a
 // Dijkstra can run dry -- no finite path length left -- while columns are
 // still unassigned, which is the same test).
+//
+// DUALS (the duals form of the LSAP kernels only; a flag, as RECT is one of
+// sap_solve_mw): on success lane l stores the duals v of its columns to ld.dv
+// (the instance's global v row; a loader wrapped in WithDuals).  u stays in
+// u_l for the caller.
 // ---------------------------------------------------------------------------
-template <int K, typename T, typename Loader>
+template <typename L, typename T>
+struct WithDuals : L {
+  T *dv;  // the instance's column duals (global, n live entries)
+};
+
+template <int K, typename T, bool DUALS = false, typename Loader>
 __device__ int sap_solve(const int nr, const int n, Loader &ld, T *__restrict__ u_l,
                          int16_t *__restrict__ c4r_l, int64_t &steps_out) {
   const int lane = threadIdx.x;
@@ -225,6 +235,13 @@ __device__ int sap_solve(const int nr, const int n, Loader &ld, T *__restrict__ 
       __syncthreads();
       j = t;
       if (pi == cur) break;
+    }
+  }
+  if constexpr (DUALS) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int j = lane + WAVE * k;
+      if (j < n) ld.dv[j] = v[k];
     }
   }
   steps_out = steps;
@@ -475,12 +492,14 @@ __device__ __forceinline__ int mw_col(int w, int k, int lane) {
 // mask rm goes to ~0 (a removed column's relaxation r >= minVal >= its spc
 // never updates it; its key's high word is ~0), the mover's position bits
 // flip.  The sink step needs none of it.
-template <int NW, int K, typename Loader, int FB = 10, bool RECT = false, typename... LA>
+template <int NW, int K, typename Loader, int FB = 10, bool RECT = false, bool DUALS = false, typename... LA>
 __device__ __forceinline__ void sap_solve_mw(const int n, const Loader &ld, const SolveLds &S, int64_t &steps_out,
                              int &fallbacks, const bool exact, const LA &...la) {
   // RECT (the generic LSAP kernels only; a flag, so that the square
   // instantiations of the Santa kernels compile as they always did): ld.nr
   // rows (S.u, S.c4r) over n >= ld.nr columns (S.r4c, S.path, `remaining`)
+  // DUALS (the same kernels' duals form, a flag for the same reason): at the
+  // end every thread stores v = -nv of its columns to ld.dv (WithDuals)
   int nr = n;
   if constexpr (RECT) nr = ld.nr;
   // key fields: FB bits of position and of row/column (n <= 2^FB), 1 class bit
@@ -681,6 +700,13 @@ __device__ __forceinline__ void sap_solve_mw(const int n, const Loader &ld, cons
       }
     }
     __syncthreads();
+  }
+  if constexpr (DUALS) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int j = mw_col<NW, K>(w, k, lane);
+      if (j < n) ld.dv[j] = -nv[k];
+    }
   }
   steps_out = steps;
 }
@@ -5338,6 +5364,7 @@ struct GlobalLoaderF64MW {
 // `remaining`, and an empty `remaining` ends the instance as infeasible (only
 // input the caller should have rejected, NaN or -inf, gets there).
 // Returns 0, or -1 for an infeasible instance (block-uniform).
+// DUALS: on success every thread stores v of its columns to ld.dv (WithDuals).
 // ---------------------------------------------------------------------------
 struct SolveLdsF64 {
   double *u;       // [nr]  row duals
@@ -5367,7 +5394,7 @@ __device__ __forceinline__ double wave_min_f64_dpp(double x) {
   return __longlong_as_double((long long)readlane_u64((uint64_t)__double_as_longlong(x), 63));
 }
 
-template <int NW, int K, typename Loader>
+template <int NW, int K, bool DUALS = false, typename Loader>
 __device__ __forceinline__ int sap_solve_mw_f64(const int nr, const int n, const Loader &ld,
                                                 const SolveLdsF64 &S) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -5494,6 +5521,13 @@ __device__ __forceinline__ int sap_solve_mw_f64(const int nr, const int n, const
     }
     __syncthreads();
   }
+  if constexpr (DUALS) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int j = mw_col<NW, K>(w, k, lane);
+      if (j < n) ld.dv[j] = v[k];
+    }
+  }
   return 0;
 }
 
@@ -5515,11 +5549,44 @@ __device__ __forceinline__ bool lsap_shape(const int32_t *shape, int b, int NR, 
 // RECT = false is the square launch (NR == NC, no shapes): one size throughout,
 // the code the square entries always ran (A/B profiles/lsap_rect_ab.jsonl: the
 // general form cost 512 x 512 instances 0.8 %).
-template <int NW, int K, typename S, bool HASH, bool RECT>
+//
+// The duals form of the three LSAP kernels is the same kernel with two more
+// arguments, `T *du, T *dv` as a trailing parameter pack (DU...): an empty
+// pack is the kernel as it always was, argument list and code.  du [B x NR]
+// and dv [B x NC] receive the solver's final duals in the units of C, u[i] +
+// v[j] <= C[i][j]; 0 in the padded rows and columns and in every slot of an
+// empty or invalid-shape instance; the float kernels write NaN in the live
+// slots of an infeasible instance.
+template <typename T> __device__ __forceinline__ T *duals_u(T *u, T *) { return u; }
+template <typename T> __device__ __forceinline__ T *duals_v(T *, T *v) { return v; }
+
+template <typename T, int WG>
+__device__ __forceinline__ void duals_fill(T *du, T *dv, int b, int NR, int NC, int r0, int c0, T x) {
+  for (int i = r0 + (int)threadIdx.x; i < NR; i += WG) du[(size_t)b * NR + i] = x;
+  for (int j = c0 + (int)threadIdx.x; j < NC; j += WG) dv[(size_t)b * NC + j] = x;
+}
+
+// After a float solve: u from LDS, or NaN in the live slots of u and v for an
+// infeasible instance (the solver stored no v then); 0 in the padding.
+template <int WG>
+__device__ __forceinline__ void duals_store_f64(double *du, double *dv, const double *u_l, int st, int b,
+                                                int NR, int NC, int nr, int n) {
+  if (st == 0) {
+    for (int i = threadIdx.x; i < nr; i += WG) du[(size_t)b * NR + i] = u_l[i];
+  } else {
+    for (int i = threadIdx.x; i < nr; i += WG) du[(size_t)b * NR + i] = __builtin_nan("");
+    for (int j = threadIdx.x; j < n; j += WG) dv[(size_t)b * NC + j] = __builtin_nan("");
+  }
+  duals_fill<double, WG>(du, dv, b, NR, NC, nr, n, 0.0);
+}
+
+template <int NW, int K, typename S, bool HASH, bool RECT, typename... DU>
 __global__ __launch_bounds__(NW * WAVE) void lsap_i64_kernel(const S *C, uint64_t seed, int64_t mod,
                                                              int NR_, int NC, const int32_t *shape,
                                                              int32_t *col, int64_t *cost,
-                                                             int32_t *fb, unsigned flags) {
+                                                             int32_t *fb, unsigned flags, DU... duals) {
+  constexpr bool DUALS = sizeof...(DU) == 2;
+  static_assert(DUALS ? (RECT && !HASH) : sizeof...(DU) == 0, "duals: du, dv, the general form, costs from C");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int b = blockIdx.x;
   const int tid = threadIdx.x;
@@ -5529,6 +5596,8 @@ __global__ __launch_bounds__(NW * WAVE) void lsap_i64_kernel(const S *C, uint64_
     if (!lsap_shape(shape, b, NR, NC, nr, n)) {
       for (int i = tid; i < NR; i += NW * WAVE) col[(size_t)b * NR + i] = -1;
       if (tid == 0 && cost) cost[b] = 0;
+      if constexpr (DUALS)
+        duals_fill<int64_t, NW * WAVE>(duals_u(duals...), duals_v(duals...), b, NR, NC, 0, 0, 0);
       return;
     }
   }
@@ -5552,7 +5621,13 @@ __global__ __launch_bounds__(NW * WAVE) void lsap_i64_kernel(const S *C, uint64_
   int fallbacks = 0;
   const bool exact = (flags & SH_FLAG_EXACT_ARGMIN) != 0;
   const size_t base = (size_t)b * NR * NC;
-  if constexpr (HASH) {
+  if constexpr (DUALS) {
+    using LD = WithDuals<GlobalLoader<NW, K, S>, int64_t>;
+    const LD ld{{C + base, n, NC, nr}, duals_v(duals...) + (size_t)b * NC};
+    sap_solve_mw<NW, K, LD, 10, RECT, true>(n, ld, Sl, steps, fallbacks, exact);
+    for (int i = tid; i < nr; i += NW * WAVE) duals_u(duals...)[(size_t)b * NR + i] = Sl.u[i];
+    duals_fill<int64_t, NW * WAVE>(duals_u(duals...), duals_v(duals...), b, NR, NC, nr, n, 0);
+  } else if constexpr (HASH) {
     const HashLoader<NW, K> ld{seed, mod, (uint64_t)b, n, nr};
     sap_solve_mw<NW, K, HashLoader<NW, K>, 10, RECT>(n, ld, Sl, steps, fallbacks, exact);
   } else {
@@ -5581,10 +5656,12 @@ __global__ __launch_bounds__(NW * WAVE) void lsap_i64_kernel(const S *C, uint64_
   }
 }
 
-template <int K, typename S>
+template <int K, typename S, typename... DU>
 __global__ __launch_bounds__(WAVE) void lsap_f64_kernel(const S *C, int NR, int NC,
                                                         const int32_t *shape, int32_t *col,
-                                                        double *cost) {
+                                                        double *cost, DU... duals) {
+  constexpr bool DUALS = sizeof...(DU) == 2;
+  static_assert(DUALS || sizeof...(DU) == 0, "duals: du, dv");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int b = blockIdx.x;
   const int lane = threadIdx.x;
@@ -5592,6 +5669,7 @@ __global__ __launch_bounds__(WAVE) void lsap_f64_kernel(const S *C, int NR, int 
   if (!lsap_shape(shape, b, NR, NC, nr, n)) {
     for (int i = lane; i < NR; i += WAVE) col[(size_t)b * NR + i] = -1;
     if (lane == 0 && cost) cost[b] = 0;
+    if constexpr (DUALS) duals_fill<double, WAVE>(duals_u(duals...), duals_v(duals...), b, NR, NC, 0, 0, 0.0);
     return;
   }
   double *u_l = (double *)smem;
@@ -5603,9 +5681,13 @@ __global__ __launch_bounds__(WAVE) void lsap_f64_kernel(const S *C, int NR, int 
   __syncthreads();
   int64_t steps = 0;
   const size_t base = (size_t)b * NR * NC;
-  GlobalLoaderF64<K, S> ld{C + base, n, NC};
-  const int st = sap_solve<K, double>(nr, n, ld, u_l, c4r_l, steps);
+  using GL = GlobalLoaderF64<K, S>;
+  std::conditional_t<DUALS, WithDuals<GL, double>, GL> ld{GL{C + base, n, NC}};
+  if constexpr (DUALS) ld.dv = duals_v(duals...) + (size_t)b * NC;
+  const int st = sap_solve<K, double, DUALS>(nr, n, ld, u_l, c4r_l, steps);
   __syncthreads();
+  if constexpr (DUALS)
+    duals_store_f64<WAVE>(duals_u(duals...), duals_v(duals...), u_l, st, b, NR, NC, nr, n);
   double acc = 0;
   for (int i = lane; i < NR; i += WAVE) {
     const bool live = st == 0 && i < nr;
@@ -5623,10 +5705,12 @@ __global__ __launch_bounds__(WAVE) void lsap_f64_kernel(const S *C, int NR, int 
 
 // The same instance on NW waves (sap_solve_mw_f64).  Wave 0 sums the chosen
 // cost in lsap_f64_kernel's order, so both designs return the same bits.
-template <int NW, int K, typename S>
+template <int NW, int K, typename S, typename... DU>
 __global__ __launch_bounds__(NW * WAVE) void lsap_f64_mw_kernel(const S *C, int NR, int NC,
                                                                 const int32_t *shape, int32_t *col,
-                                                                double *cost) {
+                                                                double *cost, DU... duals) {
+  constexpr bool DUALS = sizeof...(DU) == 2;
+  static_assert(DUALS || sizeof...(DU) == 0, "duals: du, dv");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int WG = NW * WAVE;
   const int b = blockIdx.x;
@@ -5635,6 +5719,7 @@ __global__ __launch_bounds__(NW * WAVE) void lsap_f64_mw_kernel(const S *C, int 
   if (!lsap_shape(shape, b, NR, NC, nr, n)) {
     for (int i = tid; i < NR; i += WG) col[(size_t)b * NR + i] = -1;
     if (tid == 0 && cost) cost[b] = 0;
+    if constexpr (DUALS) duals_fill<double, WG>(duals_u(duals...), duals_v(duals...), b, NR, NC, 0, 0, 0.0);
     return;
   }
   size_t off = 0;
@@ -5655,9 +5740,13 @@ __global__ __launch_bounds__(NW * WAVE) void lsap_f64_mw_kernel(const S *C, int 
   }
   __syncthreads();
   const size_t base = (size_t)b * NR * NC;
-  const GlobalLoaderF64MW<NW, K, S> ld{C + base, n, NC};
-  const int st = sap_solve_mw_f64<NW, K>(nr, n, ld, Sl);
+  using GL = GlobalLoaderF64MW<NW, K, S>;
+  std::conditional_t<DUALS, WithDuals<GL, double>, GL> ld{GL{C + base, n, NC}};
+  if constexpr (DUALS) ld.dv = duals_v(duals...) + (size_t)b * NC;
+  const int st = sap_solve_mw_f64<NW, K, DUALS>(nr, n, ld, Sl);
   __syncthreads();
+  if constexpr (DUALS)
+    duals_store_f64<WG>(duals_u(duals...), duals_v(duals...), Sl.u, st, b, NR, NC, nr, n);
   for (int i = tid; i < NR; i += WG) col[(size_t)b * NR + i] = (st == 0 && i < nr) ? Sl.c4r[i] : -1;
   if (cost && tid < WAVE) {
     double acc = 0;
@@ -5667,6 +5756,248 @@ __global__ __launch_bounds__(NW * WAVE) void lsap_f64_mw_kernel(const S *C, int 
     for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, WAVE);
     if (tid == 0) cost[b] = acc;
   }
+}
+
+// ---------------------------------------------------------------------------
+// Dual certificate of a batch: three launches on one stream.
+//   lsap_cert_kernel   one workgroup per instance, O(nr + nc): is col an
+//     assignment (LDS bitmap of the columns), the matched slacks, the signs of
+//     v, the sums; writes slack[1], slack[2] and the flag bits, and arms
+//     slack[0] with the identity of the minimum below.
+//   lsap_slack_kernel  the pass over the live corner: the minimum of
+//     (C[i][j] - u[i]) - v[j].  A workgroup takes `rows_per` rows of one
+//     instance (small batches are split across workgroups so that the chip is
+//     busy), a thread keeps the v of its columns in registers and reads each
+//     row with 16-byte loads (VEC elements) where the rows are 16-byte aligned,
+//     narrow floats widened in registers.  The partial minima meet in slack[0]
+//     with one 64-bit atomic min per workgroup on an order-preserving integer
+//     image of the value (cert_key), so the result does not depend on the
+//     order of arrival.
+//   lsap_cert_final_kernel  decodes slack[0] and sets SH_CERT_SLACK.
+// Integer arithmetic wraps (unsigned); SH_CERT_RANGE marks every instance in
+// which a slack could have wrapped (|u|, |v| or, int64 costs, |C| >= 2^61).
+// Float sums (the gap) are taken in a fixed order: thread t of 256 adds its
+// elements t, t + 256, ... ascending, the 64 partial sums of a wave meet in
+// the xor butterfly 32, 16, .. 1, and the four waves' sums are added 0..3;
+// gap = (sum u + sum v) - sum C[i][col[i]].  In the minimum -0.0 orders below
+// +0.0 and a NaN slack makes the minimum NaN.
+// ---------------------------------------------------------------------------
+constexpr int CERT_WG = 256;
+
+__device__ __forceinline__ int64_t cert_sub(int64_t a, int64_t b) { return (int64_t)((uint64_t)a - (uint64_t)b); }
+__device__ __forceinline__ double cert_sub(double a, double b) { return a - b; }
+__device__ __forceinline__ int64_t cert_add(int64_t a, int64_t b) { return (int64_t)((uint64_t)a + (uint64_t)b); }
+__device__ __forceinline__ double cert_add(double a, double b) { return a + b; }
+__device__ __forceinline__ int64_t cert_abs(int64_t a) { return a < 0 ? cert_sub(0, a) : a; }
+__device__ __forceinline__ double cert_abs(double a) { return __builtin_fabs(a); }
+__device__ __forceinline__ uint64_t cert_key(int64_t x) { return (uint64_t)x ^ SIGN64; }
+__device__ __forceinline__ uint64_t cert_key(double x) {
+  const uint64_t bits = (uint64_t)__double_as_longlong(x);
+  if (x != x) return 0;  // below every number: a NaN slack wins the minimum
+  return (bits & SIGN64) ? ~bits : (bits | SIGN64);
+}
+__device__ __forceinline__ bool cert_out_of_range(int64_t x) {
+  return (uint64_t)x + (1ull << 61) >= (1ull << 62);
+}
+__device__ __forceinline__ bool cert_out_of_range(double) { return false; }
+template <typename T, typename S>
+__device__ __forceinline__ T cert_widen(S x) {
+  if constexpr (std::is_same<T, double>::value) return widen_f64(x);
+  else return (int64_t)x;
+}
+template <typename T>
+__device__ __forceinline__ T cert_max(T m, T y) {  // (a NaN sticks)
+  return (y > m || y != y) ? y : m;
+}
+
+template <typename S, typename T>
+__global__ __launch_bounds__(CERT_WG) void lsap_cert_kernel(const S *C, int NR, int NC, const int32_t *shape,
+                                                            const int32_t *col, const T *u, const T *v,
+                                                            T *slack, int32_t *flags) {
+  constexpr bool INT = std::is_same<T, int64_t>::value;
+  __shared__ uint32_t bits[SH_MAX_N / 32];
+  __shared__ T part[4][CERT_WG / WAVE];
+  __shared__ int s_flags, s_none;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  T *out = slack + 3 * (size_t)b;
+  int nr, nc;
+  if (!lsap_shape(shape, b, NR, NC, nr, nc)) {
+    const bool empty = nr == 0 && nc >= 0 && nc <= NC;
+    if (!empty) {  // not a shape of this tensor
+      if (tid == 0) {
+        *(uint64_t *)out = ~0ull;  // (lsap_cert_final_kernel: no live entry, 0)
+        out[1] = out[2] = 0;
+        flags[b] = SH_CERT_COL;
+      }
+      return;
+    }
+  }
+  if (tid < SH_MAX_N / 32) bits[tid] = 0;
+  if (tid == 0) s_flags = s_none = 0;
+  __syncthreads();
+  int f = 0, none = 0;
+  T tmax = 0, su = 0, sv = 0, sc = 0;
+  for (int i = tid; i < NR; i += CERT_WG) {
+    const int c = col[(size_t)b * NR + i];
+    if (i >= nr) {
+      if (c != -1) f |= SH_CERT_COL;
+      continue;
+    }
+    const T ui = u[(size_t)b * NR + i];
+    su = cert_add(su, ui);
+    if (cert_out_of_range(ui)) f |= SH_CERT_RANGE;
+    if (c == -1) {
+      ++none;
+      continue;
+    }
+    if (c < 0 || c >= nc) {
+      f |= SH_CERT_COL;
+      continue;
+    }
+    const uint32_t bit = 1u << (c & 31);
+    if (atomicOr(&bits[c >> 5], bit) & bit) f |= SH_CERT_COL;
+    const T cc = cert_widen<T>(C[((size_t)b * NR + i) * NC + c]);
+    if (cert_out_of_range(cc)) f |= SH_CERT_RANGE;
+    tmax = cert_max(tmax, cert_abs(cert_sub(cert_sub(cc, ui), v[(size_t)b * NC + c])));
+    sc = cert_add(sc, cc);
+  }
+  if (none) atomicAdd(&s_none, none);
+  __syncthreads();
+  const int n_none = s_none;
+  if (nr >= 1 && n_none == nr) {  // no assignment at all (an infeasible solve): nothing to certify
+    if (tid == 0) {
+      *(uint64_t *)out = ~0ull;
+      out[1] = out[2] = 0;
+      flags[b] = SH_CERT_NONE;
+    }
+    return;
+  }
+  if (n_none) f |= SH_CERT_COL;
+  for (int j = tid; j < nc; j += CERT_WG) {
+    const T vj = v[(size_t)b * NC + j];
+    sv = cert_add(sv, vj);
+    if (cert_out_of_range(vj)) f |= SH_CERT_RANGE;
+    const bool taken = (bits[j >> 5] >> (j & 31)) & 1u;
+    if (vj > 0 || (!taken && vj != 0)) f |= SH_CERT_SIGN;
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    su = cert_add(su, __shfl_xor(su, o, WAVE));
+    sv = cert_add(sv, __shfl_xor(sv, o, WAVE));
+    sc = cert_add(sc, __shfl_xor(sc, o, WAVE));
+    tmax = cert_max(tmax, __shfl_xor(tmax, o, WAVE));
+  }
+  if ((tid & 63) == 0) {
+    part[0][tid >> 6] = su;
+    part[1][tid >> 6] = sv;
+    part[2][tid >> 6] = sc;
+    part[3][tid >> 6] = tmax;
+  }
+  if (f) atomicOr(&s_flags, f);
+  __syncthreads();
+  if (tid == 0) {
+    su = part[0][0], sv = part[1][0], sc = part[2][0], tmax = part[3][0];
+    for (int q = 1; q < CERT_WG / WAVE; ++q) {
+      su = cert_add(su, part[0][q]);
+      sv = cert_add(sv, part[1][q]);
+      sc = cert_add(sc, part[2][q]);
+      tmax = cert_max(tmax, part[3][q]);
+    }
+    const T gap = cert_sub(cert_add(su, sv), sc);
+    f = s_flags;
+    if (!(tmax == 0)) f |= SH_CERT_TIGHT;
+    if (INT && gap != 0) f |= SH_CERT_GAP;
+    *(uint64_t *)out = ~0ull;  // the identity of lsap_slack_kernel's minimum
+    out[1] = tmax;
+    out[2] = gap;
+    flags[b] = f;
+  }
+}
+
+template <typename S, int VEC>
+struct alignas(sizeof(S) * VEC) CertPack {
+  S e[VEC];
+};
+
+template <typename S, typename T, int VEC>
+__global__ __launch_bounds__(CERT_WG) void lsap_slack_kernel(const S *C, int NR, int NC, const int32_t *shape,
+                                                             const T *u, const T *v, T *slack,
+                                                             int32_t *flags, int rows_per) {
+  // thread (ty, tx): columns (tx + TX q) VEC + e, rows r0 + ty, r0 + ty + TY, ..
+  constexpr int QMAX = (SH_MAX_N + CERT_WG * VEC - 1) / (CERT_WG * VEC);
+  __shared__ uint64_t part[CERT_WG / WAVE];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  int nr, nc;
+  if (!lsap_shape(shape, b, NR, NC, nr, nc)) return;
+  if (flags[b] & SH_CERT_NONE) return;
+  const int r0 = blockIdx.y * rows_per, r1 = min(nr, r0 + rows_per);
+  if (r0 >= r1) return;
+  const int groups = (nc + VEC - 1) / VEC;
+  int lx = 0;
+  while ((1 << lx) < groups && lx < 8) ++lx;
+  const int TX = 1 << lx, TY = CERT_WG >> lx;
+  const int tx = tid & (TX - 1), ty = tid >> lx;
+  T vv[QMAX][VEC];
+#pragma unroll
+  for (int q = 0; q < QMAX; ++q)
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      const int j = (tx + TX * q) * VEC + e;
+      vv[q][e] = (j < nc) ? v[(size_t)b * NC + j] : (T)0;
+    }
+  uint64_t best = ~0ull;
+  bool bad = false;
+  for (int i = r0 + ty; i < r1; i += TY) {
+    const T ui = u[(size_t)b * NR + i];
+    const S *row = C + ((size_t)b * NR + i) * NC;
+    CertPack<S, VEC> p[QMAX];
+#pragma unroll
+    for (int q = 0; q < QMAX; ++q) {
+      const int j0 = (tx + TX * q) * VEC;  // (j0 + VEC <= NC: NC is a multiple of VEC when VEC > 1)
+      if (j0 < nc) p[q] = *(const CertPack<S, VEC> *)(row + j0);
+    }
+#pragma unroll
+    for (int q = 0; q < QMAX; ++q)
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        const int j = (tx + TX * q) * VEC + e;
+        if (j < nc) {
+          const T c = cert_widen<T>(p[q].e[e]);
+          if (std::is_same<S, int64_t>::value) bad |= cert_out_of_range(c);
+          const uint64_t k = cert_key(cert_sub(cert_sub(c, ui), vv[q][e]));
+          best = umin64(best, k);
+        }
+      }
+  }
+  best = wave_min_u64_dpp(best);
+  if ((tid & 63) == 0) part[tid >> 6] = best;
+  __syncthreads();
+  if (tid == 0) {
+    for (int q = 1; q < CERT_WG / WAVE; ++q) best = umin64(best, part[q]);
+    if (best != ~0ull) atomicMin((unsigned long long *)(slack + 3 * (size_t)b), (unsigned long long)best);
+  }
+  if (bad) atomicOr(flags + b, SH_CERT_RANGE);
+}
+
+template <typename T>
+__global__ __launch_bounds__(CERT_WG) void lsap_cert_final_kernel(int B, T *slack, int32_t *flags) {
+  const int b = blockIdx.x * CERT_WG + threadIdx.x;
+  if (b >= B) return;
+  const int f = flags[b];
+  T *out = slack + 3 * (size_t)b;
+  const uint64_t k = *(const uint64_t *)out;
+  if (k == ~0ull) {  // nothing certified, or no live entry
+    out[0] = 0;
+    return;
+  }
+  T x;
+  if constexpr (std::is_same<T, double>::value) {
+    x = (k == 0) ? __builtin_nan("") : __longlong_as_double((long long)((k & SIGN64) ? (k ^ SIGN64) : ~k));
+  } else {
+    x = (int64_t)(k ^ SIGN64);
+  }
+  out[0] = x;
+  if (!(x >= 0)) flags[b] = f | SH_CERT_SLACK;
 }
 
 // ---------------------------------------------------------------------------

@@ -35,6 +35,14 @@ SH_FLAG_DT_TILE = 4096  # force the dense-tile one-wave kernel (santa_dt_kernel)
 SH_FLAG_BIG_ROWS = 8192  # singles n > 256: force the row-rebuild kernel (santa_big_kernel)
 SH_FLAG_F64_MW = 16384  # float LSAP entries, nc > 64: force the four-wave kernel (lsap_f64_mw_kernel)
 SH_FLAG_F64_SW = 32768  # float LSAP entries: force the one-wave kernel (lsap_f64_kernel)
+# lsap_check_duals_*: the certificate's per-instance bits (include/santa_hip.h)
+SH_CERT_COL = 1
+SH_CERT_SLACK = 2
+SH_CERT_TIGHT = 4
+SH_CERT_SIGN = 8
+SH_CERT_GAP = 16
+SH_CERT_NONE = 32
+SH_CERT_RANGE = 64
 SH_ERRF_ROWS = 1
 SH_ERRF_INFEASIBLE = 2
 SH_ERRF_TYPE = 4
@@ -111,6 +119,18 @@ SIGNATURES = {
     "lsap_solve_batched_rect_f16": (_I, [_P, _I, _I, _I, _P, _P, _P, _U, _P]),
     "lsap_solve_batched_rect_bf16": (_I, [_P, _I, _I, _I, _P, _P, _P, _U, _P]),
     "lsap_solve_batched_rect_hash": (_I, [_U64, _I64, _I, _I, _I, _P, _P, _U, _P]),
+    "lsap_solve_batched_duals_i64": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _U, _P]),
+    "lsap_solve_batched_duals_i32": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _U, _P]),
+    "lsap_solve_batched_duals_f64": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _U, _P]),
+    "lsap_solve_batched_duals_f32": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _U, _P]),
+    "lsap_solve_batched_duals_f16": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _U, _P]),
+    "lsap_solve_batched_duals_bf16": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _U, _P]),
+    "lsap_check_duals_i64": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "lsap_check_duals_i32": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "lsap_check_duals_f64": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "lsap_check_duals_f32": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "lsap_check_duals_f16": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "lsap_check_duals_bf16": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "sh_gen_synthetic": (_I, [_U64, _I, _I, _I, _I, _I, _P, _P, _P]),
 }
 

@@ -10,6 +10,9 @@ own float64 arithmetic, so even the permutation on ties is scipy's.  Tall
 input is solved as its transpose and inverted, as scipy does internally.
 solve_batched also takes float32, float16 and bfloat16 device tensors: read at
 their own width, widened in registers (exact) and solved as float64.
+solve_batched(duals=True) and linear_sum_assignment_duals also return the dual
+variables (u, v) the solve ends with, and check_duals certifies (col, u, v)
+against the costs on the device: for integer costs flags == 0 proves optimality.
 """
 from __future__ import annotations
 
@@ -31,6 +34,9 @@ EXACT_INT_LIMIT = 1 << 53   # float64 holds every integer below this exactly
 # floating-point cost dtypes of solve_batched and their C-ABI entries
 FLOAT_ENTRIES = {torch.float64: "lsap_solve_batched_rect_f64", torch.float32: "lsap_solve_batched_rect_f32",
                  torch.float16: "lsap_solve_batched_rect_f16", torch.bfloat16: "lsap_solve_batched_rect_bf16"}
+# every cost dtype -> the suffix of its lsap_solve_batched_duals_ / lsap_check_duals_ entry
+DTYPE_SUFFIX = {torch.int64: "i64", torch.int32: "i32", torch.float64: "f64", torch.float32: "f32",
+                torch.float16: "f16", torch.bfloat16: "bf16"}
 
 
 # ---------------------------------------------------------------------------
@@ -72,6 +78,22 @@ def invert_tall(col_t: torch.Tensor, nr: int) -> torch.Tensor:
     return out[:, :nr].contiguous()
 
 
+def invert_col(col: torch.Tensor, n: int):
+    """col int32 [B, m] with entries in [0, n) or -1 -> (inv int32 [B, n], bad
+    bool [B]): inv[b, col[b, i]] = i and -1 where no row points.  bad marks the
+    instances whose col is no partial assignment (an entry outside [-1, n), or
+    two rows on one column), whose inverse means nothing."""
+    B, m = col.shape
+    ok = (col >= 0) & (col < n)
+    inv = torch.full((B, n + 1), -1, dtype=torch.int32, device=col.device)
+    idx = torch.where(ok, col, torch.full_like(col, n)).long()  # (anything else -> the spare slot)
+    src = torch.arange(m, dtype=torch.int32, device=col.device).expand(B, m)
+    inv.scatter_(1, idx, src)
+    inv = inv[:, :n].contiguous()
+    bad = ((~ok) & (col != -1)).any(1) | ((inv >= 0).sum(1) != ok.sum(1))
+    return inv, bad
+
+
 def tall_result(col_t):
     """scipy's (row_ind, col_ind) of a tall matrix from the solution col_t of
     its transpose: rows sorted ascending, each with its column."""
@@ -95,6 +117,24 @@ def exact_int64_route(C: np.ndarray) -> bool:
 
 
 # ---------------------------------------------------------------------------
+def _solve_wide_duals(C: torch.Tensor, with_cost: bool, fl: int, shape_dev):
+    """_solve_wide through the lsap_solve_batched_duals_ entries: (col, cost, u, v)."""
+    B, nr, nc = C.shape
+    dev = C.device
+    if C.dtype == torch.int64 and C.numel() and max(int(C.max()), -int(C.min())) >= INT64_COST_LIMIT:
+        raise ValueError("int64 costs must satisfy |C| < 2**50; pass float64 instead")
+    ddt = torch.float64 if C.dtype in FLOAT_ENTRIES else torch.int64
+    col = torch.empty((B, nr), dtype=torch.int32, device=dev)
+    cost = torch.empty(B, dtype=ddt, device=dev) if with_cost else None
+    u = torch.empty((B, nr), dtype=ddt, device=dev)
+    v = torch.empty((B, nc), dtype=ddt, device=dev)
+    entry = getattr(_lib.lib(), "lsap_solve_batched_duals_" + DTYPE_SUFFIX[C.dtype])
+    rc = entry(_p(C), nr, nc, B, _p(shape_dev), _p(col), _p(cost), _p(u), _p(v), fl,
+               current_stream_handle(dev))
+    _lib.check(rc, "lsap_solve_batched_duals")
+    return col, cost, u, v
+
+
 def _solve_wide(C: torch.Tensor, with_cost: bool, fl: int, shape_dev):
     """C contiguous [B, nr, nc], 1 <= nr <= nc (the square C-ABI entries are
     the rect ones with nr == nc and no shapes)."""
@@ -123,9 +163,20 @@ def _solve_wide(C: torch.Tensor, with_cost: bool, fl: int, shape_dev):
 
 
 def solve_batched(C: torch.Tensor, with_cost: bool = True, flags: int = 0, shapes=None,
-                  maximize: bool = False):
+                  maximize: bool = False, duals: bool = False):
     """C: device tensor [B, NR, NC] (int64 / int32 / float64 / float32 /
-    float16 / bfloat16) -> (col int32 [B, NR], cost [B]).
+    float16 / bfloat16) -> (col int32 [B, NR], cost [B]), or with duals=True
+    (col, cost, u [B, NR], v [B, NC]).
+
+    The duals are the ones the shortest-augmenting-path run ends with, int64
+    for integer costs and float64 otherwise, in the units of C:
+    u[i] + v[j] <= C[i, j] on the live corner with equality on the chosen
+    entries, v <= 0 with v == 0 on a column no row took, sum(u) + sum(v) ==
+    cost.  Integer duals satisfy this exactly; float duals are bit for bit
+    scipy's own and feasible up to its rounding.  A tall batch swaps the roles
+    (u <= 0, 0 on the rows left out); maximize returns the negated duals of
+    the negated problem (u[i] + v[j] >= C[i, j], v >= 0).  Padding gets 0, an
+    infeasible instance NaN in its live slots.
 
     Floating-point costs are read at their own width and solved in float64
     (the widening is exact, and scipy converts to float64 before it solves):
@@ -158,11 +209,23 @@ def solve_batched(C: torch.Tensor, with_cost: bool = True, flags: int = 0, shape
         shape_dev = torch.from_numpy(check_shapes(shapes, B, NR, NC)).to(dev)
     if B == 0 or NR == 0 or NC == 0:
         cdt = torch.float64 if C.dtype in FLOAT_ENTRIES else torch.int64
-        return (torch.full((B, NR), -1, dtype=torch.int32, device=dev),
-                torch.zeros(B, dtype=cdt, device=dev) if with_cost else None)
+        out = (torch.full((B, NR), -1, dtype=torch.int32, device=dev),
+               torch.zeros(B, dtype=cdt, device=dev) if with_cost else None)
+        if duals:
+            out += (torch.zeros((B, NR), dtype=cdt, device=dev), torch.zeros((B, NC), dtype=cdt, device=dev))
+        return out
     if maximize:  # (int32: -INT32_MIN wraps, so widen; the int64 bound covers int64)
         C = -(C.to(torch.int64) if C.dtype == torch.int32 else C)
     fl = _lib.SH_COMPAT_TIEBREAK | flags
+    if duals:
+        if NR > NC:  # the transposed solve's row duals belong to the columns
+            col_t, cost, v, u = _solve_wide_duals(C.transpose(1, 2).contiguous(), with_cost, fl, None)
+            col = invert_tall(col_t, NR)
+        else:
+            col, cost, u, v = _solve_wide_duals(C.contiguous(), with_cost, fl, shape_dev)
+        if maximize:
+            cost, u, v = (-cost if cost is not None else None), -u, -v
+        return col, cost, u, v
     if NR > NC:
         col_t, cost = _solve_wide(C.transpose(1, 2).contiguous(), with_cost, fl, None)
         col = invert_tall(col_t, NR)
@@ -193,24 +256,75 @@ def solve_hash(seed: int, modulus: int, n: int, B: int, device: int | str = 0, w
     return col, cost
 
 
-def linear_sum_assignment(cost_matrix, maximize: bool = False, device: int | str = 0):
-    """scipy.optimize.linear_sum_assignment for one matrix, solved on the GPU.
+def check_duals(C: torch.Tensor, col: torch.Tensor, u: torch.Tensor, v: torch.Tensor, shapes=None,
+                maximize: bool = False):
+    """Certify (col, u, v) -- as solve_batched(duals=True) returns them, for the
+    same C, shapes and maximize -- in one pass over the costs on the device.
 
-    Any shape up to SH_MAX_N on the longer side: wide input returns
-    (arange(nr), col), tall input the rows scipy keeps, sorted, with their
-    columns.  Integer matrices whose sums stay below 2^53 are solved in exact
-    int64 (where scipy's float64 arithmetic is exact too); anything else in
-    float64 with scipy's operation order, so the permutation is scipy's
-    either way."""
+    Returns (slack_min [B], tight_max [B], gap [B], flags int32 [B]); the
+    first three are int64 for integer costs, float64 otherwise:
+      slack_min  min over the live corner of (C[i, j] - u[i]) - v[j]
+      tight_max  max over the live rows of |(C[i, col[i]] - u[i]) - v[col[i]]|
+      gap        (sum u + sum v) - sum C[i, col[i]]
+      flags      SH_CERT_* bits (santa_hip.h); for integer costs 0 proves the
+                 instance optimal.
+    maximize certifies the negated problem (-C, -u, -v), so the same signs
+    hold.  A tall batch is checked as its transpose (a contiguous copy) with
+    the duals swapped and col inverted."""
+    require_gpu()
+    if C.dim() != 3:
+        raise ValueError("expected [B, NR, NC]")
+    B, NR, NC = C.shape
+    if max(NR, NC) > _lib.SH_MAX_N:
+        raise ValueError(f"max(NR, NC) = {max(NR, NC)} > {_lib.SH_MAX_N}")
+    if C.dtype not in DTYPE_SUFFIX:
+        raise TypeError(f"unsupported dtype {C.dtype}")
+    ddt = torch.float64 if C.dtype in FLOAT_ENTRIES else torch.int64
+    if tuple(col.shape) != (B, NR) or tuple(u.shape) != (B, NR) or tuple(v.shape) != (B, NC):
+        raise ValueError(f"expected col and u of shape [{B}, {NR}] and v of shape [{B}, {NC}]")
+    if u.dtype != ddt or v.dtype != ddt:
+        raise TypeError(f"the duals of {C.dtype} costs are {ddt}")
+    dev = C.device
+    shape_dev = None
+    if shapes is not None:
+        if NR > NC:
+            raise ValueError(f"a ragged batch must be padded wide, got [{NR}, {NC}]: "
+                             "transpose the batch so that every instance has nr <= nc")
+        shape_dev = torch.from_numpy(check_shapes(shapes, B, NR, NC)).to(dev)
+    flags = torch.zeros(B, dtype=torch.int32, device=dev)
+    slack = torch.zeros((B, 3), dtype=ddt, device=dev)
+    if B == 0 or NR == 0 or NC == 0:
+        return slack[:, 0], slack[:, 1], slack[:, 2], flags
+    col = col.to(torch.int32)
+    if maximize:
+        C, u, v = -(C.to(torch.int64) if C.dtype == torch.int32 else C), -u, -v
+    bad = None
+    if NR > NC:
+        C, u, v = C.transpose(1, 2), v, u
+        col, bad = invert_col(col, NC)
+        NR, NC = NC, NR
+    C, col, u, v = C.contiguous(), col.contiguous(), u.contiguous(), v.contiguous()
+    entry = getattr(_lib.lib(), "lsap_check_duals_" + DTYPE_SUFFIX[C.dtype])
+    rc = entry(_p(C), NR, NC, B, _p(shape_dev), _p(col), _p(u), _p(v), _p(slack), _p(flags),
+               current_stream_handle(dev))
+    _lib.check(rc, "lsap_check_duals")
+    if bad is not None:  # a tall col that was no assignment before its inversion
+        flags = flags | (bad.to(torch.int32) * _lib.SH_CERT_COL)
+    return slack[:, 0], slack[:, 1], slack[:, 2], flags
+
+
+def _route(cost_matrix, maximize: bool, dev):
+    """linear_sum_assignment's host side: the wide device matrix to minimise
+    (int64 on the exact route, float64 otherwise) and whether the input was
+    tall; None for an empty matrix."""
     C = np.asarray(cost_matrix)
     if C.ndim != 2:
         raise ValueError("expected a matrix (2-D array), got a %r array" % (C.shape,))
     nr, nc = C.shape
     if nr == 0 or nc == 0:
-        return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+        return None, False
     if max(nr, nc) > _lib.SH_MAX_N:
         raise ValueError(f"max(nr, nc) = {max(nr, nc)} > {_lib.SH_MAX_N}")
-    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
     if C.dtype == np.bool_:
         C = C.astype(np.int64)
     if np.issubdtype(C.dtype, np.unsignedinteger):
@@ -232,10 +346,50 @@ def linear_sum_assignment(cost_matrix, maximize: bool = False, device: int | str
         if np.isnan(Cf).any() or np.isneginf(Cf).any():
             raise ValueError("matrix contains invalid numeric entries")
         Ct = torch.from_numpy(Cf).to(dev)
+    return Ct, tall
+
+
+def linear_sum_assignment_duals(cost_matrix, maximize: bool = False, device: int | str = 0):
+    """linear_sum_assignment that also returns the dual variables:
+    (row_ind, col_ind, u [nr], v [nc]), u and v numpy arrays, int64 on the
+    exact integer route and float64 on the float64 route (the routing is
+    linear_sum_assignment's).  u[i] + v[j] <= C[i, j] with equality on the
+    returned pairs (>= with maximize), in the sense of solve_batched."""
+    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    Ct, tall = _route(cost_matrix, maximize, dev)
+    if Ct is None:
+        nr, nc = np.asarray(cost_matrix).shape
+        z = np.zeros(0, dtype=np.int64)
+        return z, z.copy(), np.zeros(nr, dtype=np.int64), np.zeros(nc, dtype=np.int64)
+    col, _, u, v = solve_batched(Ct.unsqueeze(0), with_cost=False, duals=True)
+    col = col[0].cpu().numpy().astype(np.int64)
+    if (col < 0).any():
+        raise ValueError("cost matrix is infeasible")
+    u, v = u[0].cpu().numpy(), v[0].cpu().numpy()
+    if maximize:
+        u, v = -u, -v
+    if tall:
+        return tall_result(col) + (v, u)
+    return np.arange(col.size, dtype=np.int64), col, u, v
+
+
+def linear_sum_assignment(cost_matrix, maximize: bool = False, device: int | str = 0):
+    """scipy.optimize.linear_sum_assignment for one matrix, solved on the GPU.
+
+    Any shape up to SH_MAX_N on the longer side: wide input returns
+    (arange(nr), col), tall input the rows scipy keeps, sorted, with their
+    columns.  Integer matrices whose sums stay below 2^53 are solved in exact
+    int64 (where scipy's float64 arithmetic is exact too); anything else in
+    float64 with scipy's operation order, so the permutation is scipy's
+    either way."""
+    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    Ct, tall = _route(cost_matrix, maximize, dev)
+    if Ct is None:
+        return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
     col, _ = solve_batched(Ct.unsqueeze(0), with_cost=False)
     col = col[0].cpu().numpy().astype(np.int64)
     if (col < 0).any():
         raise ValueError("cost matrix is infeasible")
     if tall:
         return tall_result(col)
-    return np.arange(nr, dtype=np.int64), col
+    return np.arange(col.size, dtype=np.int64), col

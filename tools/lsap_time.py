@@ -1,10 +1,12 @@
 """dev: time the batched LSAP for a few cases on the library SANTA_HIP_LIB selects (A/B).
-    python tools/lsap_time.py [--dtype hash|f64|f32|f16|bf16] [--flags N] [--ties] [--tag TEXT]
+    python tools/lsap_time.py [--dtype hash|i64|f64|f32|f16|bf16] [--flags N] [--ties] [--duals] [--tag TEXT]
                               [NxB | NRxNCxB ...]     (default: 256x512 512x256 1024x256 256x4096)
 NxB: B square n x n instances; NRxNCxB: B instances of nr x nc.
 --dtype hash (the default): lsap_solve_batched_hash / _rect_hash, costs generated in the kernel.
 --dtype f64 / f32 / f16 / bf16: solve_batched on a device tensor of that dtype, generated on the
   device from seed 7: torch.rand * 2^16, or with --ties the tie-heavy randint(0, 3) * 0.5.
+--dtype i64: solve_batched on an int64 device tensor, randint(0, 2^16) from seed 7.
+--duals: solve_batched(duals=True), the lsap_solve_batched_duals_ entries (not with hash).
 --flags: C-ABI flags passed on (SH_FLAG_F64_MW = 16384, SH_FLAG_F64_SW = 32768).
 Both take comma-separated lists (every combination is timed, per case).  SANTA_HIP_PKG names the
 directory that holds the santa_hip package of another checkout (an older commit, with
@@ -25,12 +27,14 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--dtype", default="hash")
 ap.add_argument("--flags", default="0")
 ap.add_argument("--ties", action="store_true")
+ap.add_argument("--duals", action="store_true")
 ap.add_argument("--tag", default=None)
 ap.add_argument("cases", nargs="*", default=["256x512", "512x256", "1024x256", "256x4096"])
 args = ap.parse_args()
-DT = {"f64": torch.float64, "f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
+DT = {"i64": torch.int64, "f64": torch.float64, "f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
 dtypes, flag_list = args.dtype.split(","), [int(f) for f in args.flags.split(",")]
-assert all(d == "hash" or d in DT for d in dtypes), "--dtype: hash, f64, f32, f16 or bf16"
+assert all(d == "hash" or d in DT for d in dtypes), "--dtype: hash, i64, f64, f32, f16 or bf16"
+assert not (args.duals and "hash" in dtypes), "--duals needs a cost tensor"
 
 for case, dtype, flags in [(tuple(int(x) for x in c.split("x")), d, f)
                            for c in args.cases for d in dtypes for f in flag_list]:
@@ -44,13 +48,18 @@ for case, dtype, flags in [(tuple(int(x) for x in c.split("x")), d, f)
     else:
         g = torch.Generator(device="cuda").manual_seed(7)
         shape = (B, n if nr is None else nr, n)
-        if args.ties:
+        if dtype == "i64":
+            C = torch.randint(0, 3 if args.ties else 65536, shape, generator=g, device="cuda")
+        elif args.ties:
             C = torch.randint(0, 3, shape, generator=g, device="cuda").to(DT[dtype]) * 0.5
         else:
             C = (torch.rand(shape, generator=g, device="cuda", dtype=torch.float64) * 65536.0).to(DT[dtype])
 
         def solve():
-            santa_hip.solve_batched(C, with_cost=False, flags=flags)
+            if args.duals:
+                santa_hip.solve_batched(C, with_cost=False, flags=flags, duals=True)
+            else:
+                santa_hip.solve_batched(C, with_cost=False, flags=flags)
 
     solve()
     torch.cuda.synchronize()
@@ -67,6 +76,8 @@ for case, dtype, flags in [(tuple(int(x) for x in c.split("x")), d, f)
         out = {"nr": nr, "nc": n, "B": B, "ms": min(ts)}
     if dtype != "hash" or flags or args.tag:
         out.update(dtype=dtype, flags=flags, ties=args.ties, median_ms=statistics.median(ts))
+    if args.duals:
+        out["duals"] = True
     if args.tag:
         out["tag"] = args.tag
     print(json.dumps(out))
