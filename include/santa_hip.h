@@ -144,7 +144,11 @@ int sh_version(void);
  *              only the score's normalisation uses nq).
  * Each wishlist row must hold distinct gift ids in [0, ng) and each good-kids
  * row distinct child ids in [0, nc) (true of the Kaggle data); otherwise
- * SH_ERR_ARGS.  n_wish <= 127, n_good <= 32767.
+ * SH_ERR_ARGS.  1 <= n_wish <= min(127, ng), n_good <= min(32767, nc),
+ * ng <= 8192 (the kernels keep ng chain heads in LDS), nc * n_wish < 2^31.
+ * Every such context is solved by the default dispatch (flags = 0) in every
+ * mode and block size; a forced design may be refused where its tile does not
+ * fit (SH_ERR_ARGS, nothing written).
  * ------------------------------------------------------------------------ */
 int sh_ctx_create(sh_ctx **out, int device, const int16_t *h_wish, int n_wish,
                   const int32_t *h_goodkids, int n_good, int nc, int ng, int nq);
@@ -281,6 +285,14 @@ int sh_ctx_set_sparse_budget(sh_ctx *ctx, int bytes);
  * two-pass argmin (cost spreads beyond the packed key's 2^42-unit window, or
  * SH_FLAG_EXACT_ARGMIN) since the last call.  Synchronises; clears.        */
 int sh_ctx_fallback_steps(sh_ctx *ctx, void *stream);
+
+/* Profiling counter: blocks of the last sh_solve_blocks / sh_solve_round call
+ * that its design's primary launch left to the fallback launch (out of the
+ * 32-bit lattice range -- every singles block at n_wish = 1 --, hit lists over
+ * capacity, SH_FLAG_TEST_RANGE / SH_FLAG_EXACT_ARGMIN); 0 for a design without
+ * a fallback launch.  Not the same as sh_ctx_fallback_steps: the fallback
+ * launch's windowed keys rarely need the exact argmin.  Synchronises.       */
+int sh_ctx_fallback_blocks(sh_ctx *ctx, void *stream);
 
 /* ---------------------------------------------------------------------------
  * Multi-GPU exchange helpers (the reference's comm.send/recv + comm.bcast of

@@ -89,6 +89,7 @@ struct sh_ctx {
   unsigned char *d_rec = nullptr;
   int rec_cap = 0;
   int ovf_par = 0;
+  int ovf_last = -1;     // the list counter the last solve's primary launch appended to; -1: a design without a fallback launch
   int n_cu = 0;          // compute units
   int dt_slots = 0, dt_slots_n = -1;    // cached dt_tile_slots for one n (pick_design asks every round)
   int64_t *h_mail = nullptr;             // host mailbox (sh_publish_delta): coherent, mapped
@@ -313,12 +314,26 @@ int raise_lds(const sh_ctx *ctx, size_t lds) {
   return SH_OK;
 }
 
-// Launches Kern with `lds` bytes of dynamic LDS; above LDS_MAX the launch is
+// Dynamic LDS a launch of Kern may ask for: a workgroup's LDS less the
+// kernel's static part (256 bytes in the kernels that call __syncthreads_or;
+// the runtime refuses a dynamic size that does not leave room for it).
+template <auto Kern>
+size_t lds_room() {
+  static thread_local size_t room = 0;
+  if (!room) {
+    hipFuncAttributes fa;
+    if (hipFuncGetAttributes(&fa, (const void *)Kern) != hipSuccess) return LDS_MAX;  // (no device: the launch says so)
+    room = fa.sharedSizeBytes < LDS_MAX ? LDS_MAX - fa.sharedSizeBytes : 1;
+  }
+  return room;
+}
+
+// Launches Kern with `lds` bytes of dynamic LDS; above lds_room the launch is
 // refused with `too_big`.
 template <auto Kern, typename... Args>
 int launch_lds(const sh_ctx *ctx, const char *too_big, int grid, int block, size_t lds, hipStream_t s,
                const Args &...args) {
-  if (lds > LDS_MAX) return fail(SH_ERR_ARGS, too_big);
+  if (lds > lds_room<Kern>()) return fail(SH_ERR_ARGS, too_big);
   HIP_TRY_RC(raise_lds<Kern>(ctx, lds));
   hipLaunchKernelGGL(Kern, dim3(grid), dim3(block), lds, s, args...);
   HIP_TRY(hipGetLastError());
@@ -329,7 +344,7 @@ int launch_lds(const sh_ctx *ctx, const char *too_big, int grid, int block, size
 template <auto Kern>
 int occ_blocks(const sh_ctx *ctx, int threads, size_t lds) {
   int per_cu = 0;
-  if (lds > LDS_MAX) return 0;
+  if (lds > lds_room<Kern>()) return 0;
   (void)raise_lds<Kern>(ctx, lds);
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, Kern, threads, lds) != hipSuccess) return 0;
   return per_cu * ctx->n_cu;
@@ -453,6 +468,7 @@ int with_fallback(sh_ctx *ctx, SantaArgs a, int B, hipStream_t s, P &&primary,
     return rc;
   }
   ctx->ovf_par = p ^ 1;
+  ctx->ovf_last = p;  // (counter p keeps this call's count until the next call's fallback launch resets it)
   return SH_OK;
 }
 
@@ -471,10 +487,10 @@ int with_lb_cfg(int n, F &&f) {
 #endif
 }
 
-size_t lb_lds_bytes(const sh_ctx *ctx, int n) {
-  return with_lb_cfg(n, [&](auto c) -> size_t {
+bool lb_lds_fits(const sh_ctx *ctx, int n) {
+  return with_lb_cfg(n, [&](auto c) -> bool {
     using C = decltype(c);
-    return lb_lds_layout(n, ctx->ng, C::NW, C::K).total;
+    return lb_lds_layout(n, ctx->ng, C::NW, C::K).total <= lds_room<santa_lb_kernel<C::NW, C::K>>();
   });
 }
 
@@ -483,7 +499,7 @@ size_t lb_lds_bytes(const sh_ctx *ctx, int n) {
 // column's row and child share one 31-bit register)
 bool lb_eligible(const sh_ctx *ctx, int n, unsigned flags) {
   return n > 256 && n <= LB_MAX_N && ctx->nc <= (1 << 20) && !(flags & SH_FLAG_BIG_ROWS) &&
-         lb_lds_bytes(ctx, n) <= LDS_MAX;
+         lb_lds_fits(ctx, n);
 }
 
 // santa_lb_kernel + santa_big_kernel over the blocks it left (out of its
@@ -531,7 +547,7 @@ int launch_santa_dt(sh_ctx *ctx, const SantaArgs &args, int B, hipStream_t s) {
   if (ctx->n_wish > 253) return fail(SH_ERR_ARGS, "dense tile: n_wish > 253 does not fit the uint8 rank codes");
   const size_t lds = dt_lds_layout(args.n, ctx->ng).total;
   const char *too_big = "dense tile: too many gift types for LDS";
-  if (lds > LDS_MAX) return fail(SH_ERR_ARGS, too_big);  // (before the overflow lists are made)
+  if (lds > lds_room<santa_dt_kernel<false>>()) return fail(SH_ERR_ARGS, too_big);  // (before the overflow lists are made)
   return with_fallback(ctx, args, B, s, [&](const SantaArgs &a) {
     return (a.flags & SH_FLAG_TIMING) ? launch_lds<santa_dt_kernel<true>>(ctx, too_big, B, SANTA_WG, lds, s, a)
                                       : launch_lds<santa_dt_kernel<false>>(ctx, too_big, B, SANTA_WG, lds, s, a);
@@ -628,7 +644,12 @@ int pick_design(sh_ctx *ctx, int mode, int n, int B, unsigned flags) {
   // in VGPRs (the compiler moves it to scratch), and a round has 78 blocks
   // (a one-wave dense-tile twins kernel with 64-bit keys was built in round 4
   // and measured 36 % slower than this 4-wave one: profiles/r04_twins_dt.jsonl)
-  if (mode == SH_MODE_TWINS) return SH_DESIGN_TWINS;
+  // (the code-pair tile, 2 n r16(n) bytes, and the ng chain heads share the
+  // workgroup's LDS: where they do not fit lds_room -- n = 256 from ng = 6569
+  // -- the row-rebuild kernel takes the block, as it does for n > 256)
+  if (mode == SH_MODE_TWINS)
+    return santa_lds_layout(n, 1, ctx->ng).total <= lds_room<santa_block_kernel<1, 1>>() ? SH_DESIGN_TWINS
+                                                                                             : SH_DESIGN_LARGE;
   if (flags & SH_FLAG_LDS_TILE) return SH_DESIGN_LDS_TILE;
   if (flags & SH_FLAG_DT_TILE) return SH_DESIGN_DT_TILE;
   // (SH_FLAG_SW_TILE, the retired one-wave register-tile kernel, is refused
@@ -725,6 +746,7 @@ int sh_solve_round(sh_ctx *ctx, int mode, const int32_t *d_rows, int n, int B, i
   HIP_TRY_RC(refuse_retired(flags));
   DeviceGuard dg(ctx->device);
   hipStream_t s = (hipStream_t)stream;
+  ctx->ovf_last = -1;
   if (B == 0) {
     if (publish) HIP_TRY_RC(sh_publish_delta(ctx, d_delta, ext->publish_slot, ext->publish_seq, stream));
     return SH_OK;
@@ -806,6 +828,16 @@ int sh_ctx_fallback_steps(sh_ctx *ctx, void *stream) {
   HIP_TRY(hipMemcpyAsync(&h, ctx->d_err + 1, 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
   HIP_TRY(hipMemsetAsync(ctx->d_err + 1, 0, 4, (hipStream_t)stream));
+  return h;
+}
+
+int sh_ctx_fallback_blocks(sh_ctx *ctx, void *stream) {
+  if (!ctx) return fail(SH_ERR_ARGS, "null ctx");
+  if (ctx->ovf_last < 0 || !ctx->d_ovf) return 0;
+  DeviceGuard dg(ctx->device);
+  int32_t h = 0;
+  HIP_TRY(hipMemcpyAsync(&h, ctx->d_ovf + ctx->ovf_last, 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
   return h;
 }
 

@@ -230,6 +230,12 @@ class SantaGPU:
         return _lib.check(_lib.lib().sh_ctx_fallback_steps(self._h, self.stream),
                           "sh_ctx_fallback_steps")
 
+    def fallback_blocks(self) -> int:
+        """Blocks of the last solve that its design's primary launch left to
+        the fallback launch (0 for a design without one)."""
+        return _lib.check(_lib.lib().sh_ctx_fallback_blocks(self._h, self.stream),
+                          "sh_ctx_fallback_blocks")
+
     # -- A7 score ---------------------------------------------------------------
     def score_sums_async(self, types: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         out = out if out is not None else self._sums

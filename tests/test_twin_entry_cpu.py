@@ -4,7 +4,8 @@ decode to the cost the reference computes, float32(h1 + h2) for the two
 twins' happiness values (mpi_twins.py:99-101), in units of 2^-31.  The
 context runs the same check in C++ at creation (sh_ctx_create); this test
 restates the encoding in Python and pins it against numpy's float32 sums for
-the synthetic shape (n_wish = 100) and the small wishlists the GPU tests use."""
+every wishlist length the context accepts (n_wish = 1 .. 127: the synthetic
+shape's 100, the small wishlists and the edge shapes of tests/ctx_shapes.py)."""
 import numpy as np
 import pytest
 
@@ -58,7 +59,7 @@ def decode_r3(e: int, E: int) -> int:
     return m - (a << 32)
 
 
-@pytest.mark.parametrize("n_wish", [100, 10, 7, 12, 126])
+@pytest.mark.parametrize("n_wish", range(1, 128))  # (every length sh_ctx_create accepts)
 def test_twin_entries_decode_to_float32_sums(n_wish):
     E = miss_units(n_wish)
     miss = np.float32(1.0 / (2.0 * n_wish))
