@@ -76,7 +76,7 @@ struct sh_ctx {
   int nc, ng, nq, n_wish, n_good;
   int64_t E;
   int16_t *d_wish = nullptr;
-  uint32_t *d_wish10 = nullptr;  // packed copy for the tile build (santa_tile_kernel<2>), or null
+  uint32_t *d_wish10 = nullptr;  // packed copy for the in-kernel tile builds (santa_sp3_kernel FUSED, fast_tile_build), or null
   int32_t *d_csr_off = nullptr;
   uint32_t *d_csr = nullptr;
   int32_t *d_err = nullptr;
@@ -478,13 +478,7 @@ template <typename F>
 int with_lb_cfg(int n, F &&f) {
   if (n <= 512) return f(BigCfg<2, 4, 0>{});
   if (n <= 1024) return f(BigCfg<4, 4, 0>{});
-#if LB_CFG_2048 == 1
-  return f(BigCfg<4, 8, 0>{});
-#elif LB_CFG_2048 == 2
-  return f(BigCfg<16, 2, 0>{});
-#else
   return f(BigCfg<8, 4, 0>{});
-#endif
 }
 
 bool lb_lds_fits(const sh_ctx *ctx, int n) {

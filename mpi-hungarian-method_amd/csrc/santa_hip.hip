@@ -28,11 +28,7 @@
 #include "sh_common.h"
 
 // (Variants measured and not kept are in git history and DESIGN.md, with
-// their A/B records under profiles/; the only build switch left selects the
-// santa_lb_kernel shape for 1024 < n <= 2048.)
-#ifndef LB_CFG_2048
-#define LB_CFG_2048 0  // 1024 < n <= 2048: 0 = 8 waves x 4 columns, 1 = 4 x 8, 2 = 16 x 2
-#endif
+// their A/B records under profiles/; no build switch is left.)
 
 namespace {
 
@@ -713,8 +709,8 @@ __device__ __forceinline__ void sap_solve_mw(const int n, const Loader &ld, cons
 
 // ---------------------------------------------------------------------------
 // sap_solve_mw in scaled units (Santa blocks, n <= 256, one column per
-// thread, NW waves): the decisions of sap_solve_mw with santa_sp2_kernel's
-// key.  Every cost, dual and path length is held times 2^SC_SH, so
+// thread, NW waves): the decisions of sap_solve_mw with the 64-bit scaled key
+// of round 2's one-wave kernel (retired).  Every cost, dual and path length is held times 2^SC_SH, so
 // sb = spc + SC_BIAS has its low SC_SH bits zero and the argmin key is
 // sb | tie bits (class 1 | position key 8 | row-or-column 8): no per-step
 // clamp/align, no saturated band, no exact re-decision.  Exact while every
@@ -1349,6 +1345,14 @@ __device__ __forceinline__ void round_prologue(const SantaArgs &a, const int b, 
   }
 }
 
+// Leave block b untouched for the fallback launch: append it to the overflow
+// list that launch loops over.  One lane or thread per block calls it (the
+// caller's guard; santa_tile_kernel also sets its record's status there).
+__device__ __forceinline__ void leave_to_fallback(const SantaArgs &a, const int b) {
+  const int p = atomicAdd(a.ovf_cnt, 1);
+  a.ovf_list[p] = b;
+}
+
 __device__ __forceinline__ int64_t gift_happy(const SantaArgs &a, int child, int t) {
   const int e0 = a.csr_off[child], e1 = a.csr_off[child + 1];
   for (int e = e0; e < e1; ++e) {
@@ -1360,6 +1364,152 @@ __device__ __forceinline__ int64_t gift_happy(const SantaArgs &a, int child, int
 
 __device__ __forceinline__ int64_t child_happy(uint32_t code, int nw1) {
   return code ? 2 * (int64_t)(nw1 - (int)code) : -1;
+}
+
+// -- the column sort by gift type (counting sort) of the tile builds ----------
+// thead[t] holds type t's column count << 16 (the callers' atomicAdds).  The
+// scans below put each type's start in the sorted column list into the low
+// half, the fill cursor of the scatter that follows; after the scatter
+// thead[t] = count << 16 | end of the type's run.
+
+// One wave scans all types.  Returns this lane's `big`: one of its types has
+// 255+ columns, which neither a uint8 column list nor the head word's count
+// byte holds (the caller leaves such a block to the fallback launch).
+__device__ __forceinline__ int type_scan_wave(uint32_t *thead, const int ng, const int lane) {
+  const int per = (ng + WAVE - 1) / WAVE;
+  const int t0s = lane * per, t1s = min(ng, t0s + per);
+  uint32_t sum = 0;
+  for (int t = t0s; t < t1s; ++t) sum += thead[t] >> 16;
+  uint32_t run = wave_incl_scan_u32(sum) - sum;
+  int big = 0;
+  for (int t = t0s; t < t1s; ++t) {
+    const uint32_t h = thead[t];
+    thead[t] = h | run;  // low half: fill cursor
+    big |= (h >> 16) >= 255u;
+    run += h >> 16;
+  }
+  return big;
+}
+
+// The same scan by a workgroup of WG threads, the waves' totals carried
+// through wsum (WG / 64 words of LDS).  All threads call it (it holds a
+// barrier).  U8 (uint8 column lists): true, before any cursor is written,
+// when the block has a `big` type; else (uint16 lists) no limit, false.
+template <int WG, bool U8>
+__device__ __forceinline__ bool type_scan_block(uint32_t *thead, const int ng, uint32_t *wsum) {
+  const int tid = threadIdx.x;
+  const int per = (ng + WG - 1) / WG;
+  const int t0 = tid * per, t1 = min(ng, t0 + per);
+  uint32_t sum = 0;
+  int big = 0;
+  for (int t = t0; t < t1; ++t) {
+    const uint32_t c = thead[t] >> 16;
+    sum += c;
+    big |= U8 && c >= 255u;
+  }
+  const uint32_t incl = wave_incl_scan_u32(sum);
+  if ((tid & 63) == 63) wsum[tid >> 6] = incl;
+  if constexpr (U8) {
+    if (__syncthreads_or(big)) return true;
+  } else {
+    __syncthreads();
+  }
+  uint32_t run = incl - sum;
+  for (int w = 0; w < (tid >> 6); ++w) run += wsum[w];
+  for (int t = t0; t < t1; ++t) {
+    const uint32_t h = thead[t];
+    thead[t] = h | run;  // low half: fill cursor
+    run += h >> 16;
+  }
+  return false;
+}
+
+// A type's head word from its thead word h after the scatter:
+// c0 | c1 << 8 | (count <= 3 ? c2 : start in csort) << 16 | count << 24, with
+// c0 .. c2 the type's first columns; 0 for a type without columns.
+// (min(c, 255u) keeps the count in its byte.  Every caller rejects a block
+// with a count of 255+ -- the scans' `big` -- before it reads a head word, so
+// wherever the word is used min(c, 255u) == c.)
+__device__ __forceinline__ uint32_t type_head_word(const uint32_t h, const uint8_t *csort) {
+  const uint32_t c = h >> 16, e = (h & 0xFFFFu) - c;  // start in csort
+  const uint32_t x2 = c <= 3u ? (uint32_t)csort[e + 2] : e;
+  return c ? ((uint32_t)csort[e] | ((uint32_t)csort[e + 1] << 8) | (x2 << 16) | (min(c, 255u) << 24)) : 0u;
+}
+
+// -- the output tails ----------------------------------------------------------
+// One reassignment's happiness delta terms, as values (an output by
+// reference moved the callers' accumulators in the register allocation).
+// Child side, from the new and the old rank code: singles, and twins (codes
+// n1, n2 / o1, o2 of the two twins).
+__device__ __forceinline__ int64_t child_delta(const int nw1, const uint32_t cn, const uint32_t co) {
+  return child_happy(cn, nw1) - child_happy(co, nw1);
+}
+__device__ __forceinline__ int64_t child_delta_twin(const int nw1, const uint32_t n1, const uint32_t n2,
+                                                    const uint32_t o1, const uint32_t o2) {
+  return child_happy(n1, nw1) + child_happy(n2, nw1) - child_happy(o1, nw1) - child_happy(o2, nw1);
+}
+// Gift side (CSR walks: the callers guard it on a.delta, but see
+// santa_block_kernel's twins), from the new (child, type) pair and the old
+// one -- a row's view has one child and two types, a column owner's two
+// children and one type.  MODE 1: the twins chn, chn + 1 / cho, cho + 1.
+template <int MODE>
+__device__ __forceinline__ int64_t gift_delta(const SantaArgs &a, const int chn, const int tn, const int cho,
+                                              const int to) {
+  static_assert(MODE == 0 || MODE == 1, "singles or twins");
+  if constexpr (MODE == 0)
+    return gift_happy(a, chn, tn) - gift_happy(a, cho, to);
+  else
+    return gift_happy(a, chn, tn) + gift_happy(a, chn + 1, tn) - gift_happy(a, cho, to) - gift_happy(a, cho + 1, to);
+}
+
+// A block's sums out, by one thread: cost, steps, the round's delta sums and
+// the count of exact-argmin fallback steps.
+__device__ __forceinline__ void store_outputs(const SantaArgs &a, const int b, const int64_t cost, const int64_t dch,
+                                              const int64_t dgh, const int64_t steps, const int fallbacks) {
+  if (a.cost) a.cost[b] = cost;
+  if (a.steps) a.steps[b] = steps;
+  if (a.delta) {
+    atomicAdd((unsigned long long *)&a.delta[0], (unsigned long long)dch);
+    atomicAdd((unsigned long long *)&a.delta[1], (unsigned long long)dgh);
+  }
+  if (fallbacks) atomicAdd(a.err + 1, fallbacks);
+}
+
+// One-wave lattice kernels (no exact-argmin steps): the wave's sums, stored
+// by lane 0.  (TIMED: the kernel's segment words follow the call, into col.)
+__device__ __forceinline__ void wave_outputs(const SantaArgs &a, const int b, const int lane, int64_t cost,
+                                             int64_t dch, int64_t dgh, const int64_t steps) {
+  cost = wave_sum_i64(cost);
+  dch = wave_sum_i64(dch);
+  dgh = wave_sum_i64(dgh);
+  if (lane == 0) store_outputs(a, b, cost, dch, dgh, steps, 0);
+}
+
+// Multi-wave kernels, in two halves around the kernel's in-place apply and
+// barrier: every wave's sums into part (NW x 3 int64 of LDS) ...
+__device__ __forceinline__ void block_sums_put(int64_t *part, int64_t cost, int64_t dch, int64_t dgh) {
+  cost = wave_sum_i64(cost);
+  dch = wave_sum_i64(dch);
+  dgh = wave_sum_i64(dgh);
+  const int w = (int)threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    part[3 * w + 0] = cost;
+    part[3 * w + 1] = dch;
+    part[3 * w + 2] = dgh;
+  }
+}
+
+// ... and, after the barrier, the NW partials summed and stored by one thread.
+template <int NW>
+__device__ __forceinline__ void block_sums_store(const SantaArgs &a, const int b, const int64_t *part,
+                                                 const int64_t steps, const int fallbacks) {
+  int64_t tc = 0, td0 = 0, td1 = 0;
+  for (int q = 0; q < NW; ++q) {
+    tc += part[3 * q];
+    td0 += part[3 * q + 1];
+    td1 += part[3 * q + 2];
+  }
+  store_outputs(a, b, tc, td0, td1, steps, fallbacks);
 }
 
 __host__ __device__ __forceinline__ size_t r16(size_t x) { return (x + 15) & ~(size_t)15; }
@@ -1550,39 +1700,14 @@ __device__ __forceinline__ bool fast_tile_build(const SantaArgs &a, const int b,
   }
   if (live) atomicAdd(&thead[ty], 1u << 16);
   __syncthreads();
-  {  // exclusive scan of the counts over types -> start of each type in csort
-    const int per = (a.ng + SANTA_WG - 1) / SANTA_WG;
-    const int t0 = tid * per, t1 = min(a.ng, t0 + per);
-    uint32_t sum = 0;
-    int big = 0;
-    for (int t = t0; t < t1; ++t) {
-      const uint32_t c = thead[t] >> 16;
-      sum += c;
-      big |= c >= 255u;
-    }
-    const uint32_t incl = wave_incl_scan_u32(sum);
-    if ((tid & 63) == 63) wsum[tid >> 6] = incl;
-    if (__syncthreads_or(big)) {
-      decline = true;
-      return false;
-    }
-    uint32_t run = incl - sum;
-    for (int w = 0; w < (tid >> 6); ++w) run += wsum[w];
-    for (int t = t0; t < t1; ++t) {
-      const uint32_t h = thead[t];
-      thead[t] = h | run;  // low half: fill cursor
-      run += h >> 16;
-    }
+  if (type_scan_block<SANTA_WG, true>(thead, a.ng, wsum)) {  // start of each type in csort
+    decline = true;
+    return false;
   }
   __syncthreads();
   if (live) csort[atomicAdd(&thead[ty], 1u) & 0xFFFFu] = (uint8_t)j;
   __syncthreads();
-  for (int t = tid; t < a.ng; t += SANTA_WG) {
-    const uint32_t h = thead[t];
-    const uint32_t c = h >> 16, e = (h & 0xFFFFu) - c;
-    const uint32_t x2 = c <= 3u ? (uint32_t)csort[e + 2] : e;
-    thead[t] = c ? ((uint32_t)csort[e] | ((uint32_t)csort[e + 1] << 8) | (x2 << 16) | (c << 24)) : 0u;
-  }
+  for (int t = tid; t < a.ng; t += SANTA_WG) thead[t] = type_head_word(thead[t], csort);
   __syncthreads();
   if (live) {
     const int nw = a.n_wish;
@@ -1729,8 +1854,8 @@ __global__ __launch_bounds__(SANTA_WG) void santa_block_kernel(SantaArgs a) {
       const uint32_t cn = tile8[(size_t)i * RS + col];
       const uint32_t co = tile8[(size_t)i * RS + i];
       cost += single_cost(cn, nw1, a.E);
-      dch += child_happy(cn, nw1) - child_happy(co, nw1);
-      if (a.delta) dgh += gift_happy(a, child, tnew) - gift_happy(a, child, told);
+      dch += child_delta(nw1, cn, co);
+      if (a.delta) dgh += gift_delta<0>(a, child, tnew, child, told);
     } else {
       const uint16_t *t16 = (const uint16_t *)tile8;
       const uint32_t cn = t16[(size_t)i * RS + col];
@@ -1739,19 +1864,10 @@ __global__ __launch_bounds__(SANTA_WG) void santa_block_kernel(SantaArgs a) {
       dch += twin_entry_happy(cn) - twin_entry_happy(co);
       // (unconditional: guarding these reads on a.delta, as the other kernels do,
       // made this kernel 2 % slower in A/B bench runs -- code generation)
-      dgh += gift_happy(a, child, tnew) + gift_happy(a, child + 1, tnew) -
-             gift_happy(a, child, told) - gift_happy(a, child + 1, told);
+      dgh += gift_delta<1>(a, child, tnew, child, told);
     }
   }
-  cost = wave_sum_i64(cost);
-  dch = wave_sum_i64(dch);
-  dgh = wave_sum_i64(dgh);
-  const int w = tid >> 6;
-  if ((tid & 63) == 0) {
-    part[3 * w + 0] = cost;
-    part[3 * w + 1] = dch;
-    part[3 * w + 2] = dgh;
-  }
+  block_sums_put(part, cost, dch, dgh);
   // Apply: this block owns rows_l[*] (and rows_l[*]+1 for twins); it read
   // every old type into ctype before this point, so in-place is race-free.
   for (int i = tid; i < n; i += SANTA_WG) {
@@ -1761,19 +1877,7 @@ __global__ __launch_bounds__(SANTA_WG) void santa_block_kernel(SantaArgs a) {
   }
   __syncthreads();
   if (tid == 0) {
-    int64_t tc = 0, td0 = 0, td1 = 0;
-    for (int q = 0; q < SANTA_NW; ++q) {
-      tc += part[3 * q];
-      td0 += part[3 * q + 1];
-      td1 += part[3 * q + 2];
-    }
-    if (a.cost) a.cost[b] = tc;
-    if (a.steps) a.steps[b] = steps;
-    if (a.delta) {
-      atomicAdd((unsigned long long *)&a.delta[0], (unsigned long long)td0);
-      atomicAdd((unsigned long long *)&a.delta[1], (unsigned long long)td1);
-    }
-    if (fallbacks) atomicAdd(a.err + 1, fallbacks);
+    block_sums_store<SANTA_NW>(a, b, part, steps, fallbacks);
     if (TIMED && a.col && n >= 5)  // (wave 0's segment cycles, see sap_solve_mw_l32 / _sc)
       for (int q = 0; q < 5; ++q) a.col[(size_t)b * n + q] = (int32_t)min(seg[q], (uint64_t)INT32_MAX);
   }
@@ -1933,7 +2037,7 @@ __host__ __device__ __forceinline__ VtLds vt_lds_layout(int ng) {
 template <int MODE, int SV>
 __device__ __forceinline__ void santa_vt_block(const SantaArgs &a, const int b) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int tid = threadIdx.x;
   const int n = a.n;
   const VtLds L = vt_lds_layout(a.ng);
   uint8_t *stage = smem + L.stage;
@@ -2086,10 +2190,7 @@ __device__ __forceinline__ void santa_vt_block(const SantaArgs &a, const int b) 
                                      T.a, T.b);
     }
     if (redo) {  // (block-uniform) left untouched for the windowed-key launch
-      if (tid == 0) {
-        const int q = atomicAdd(a.ovf_cnt, 1);
-        a.ovf_list[q] = b;
-      }
+      if (tid == 0) leave_to_fallback(a, b);
       return;
     }
   } else {
@@ -2117,24 +2218,15 @@ __device__ __forceinline__ void santa_vt_block(const SantaArgs &a, const int b) 
     const int tn = ctype[j];
     if (MODE == 0) {
       cost += single_cost(vn, nw1, a.E);
-      dch += child_happy(vn, nw1) - child_happy(vo, nw1);
-      if (a.delta) dgh += gift_happy(a, rows_l[rn], tn) - gift_happy(a, rows_l[j], tn);
+      dch += child_delta(nw1, vn, vo);
+      if (a.delta) dgh += gift_delta<0>(a, rows_l[rn], tn, rows_l[j], tn);
     } else {
       cost += twin_cost(vn, nw1, a.E);
-      dch += child_happy(vn & 0xFF, nw1) + child_happy(vn >> 8, nw1) -
-             child_happy(vo & 0xFF, nw1) - child_happy(vo >> 8, nw1);
-      if (a.delta) dgh += gift_happy(a, rows_l[rn], tn) + gift_happy(a, rows_l[rn] + 1, tn) -
-             gift_happy(a, rows_l[j], tn) - gift_happy(a, rows_l[j] + 1, tn);
+      dch += child_delta_twin(nw1, vn & 0xFF, vn >> 8, vo & 0xFF, vo >> 8);
+      if (a.delta) dgh += gift_delta<1>(a, rows_l[rn], tn, rows_l[j], tn);
     }
   }
-  cost = wave_sum_i64(cost);
-  dch = wave_sum_i64(dch);
-  dgh = wave_sum_i64(dgh);
-  if (lane == 0) {
-    part[3 * w + 0] = cost;
-    part[3 * w + 1] = dch;
-    part[3 * w + 2] = dgh;
-  }
+  block_sums_put(part, cost, dch, dgh);
   // apply: row i's child receives the type of column col[i] (all read from
   // LDS copies taken before any store, so the in-place update is race-free)
   if (live) {
@@ -2145,21 +2237,7 @@ __device__ __forceinline__ void santa_vt_block(const SantaArgs &a, const int b) 
     if (MODE && !(a.flags & SH_FLAG_NO_APPLY)) a.types[rows_l[j] + 1] = tnew;
   }
   __syncthreads();
-  if (tid == 0) {
-    int64_t tc = 0, td0 = 0, td1 = 0;
-    for (int q = 0; q < VT_NW; ++q) {
-      tc += part[3 * q];
-      td0 += part[3 * q + 1];
-      td1 += part[3 * q + 2];
-    }
-    if (a.cost) a.cost[b] = tc;
-    if (a.steps) a.steps[b] = steps;
-    if (a.delta) {
-      atomicAdd((unsigned long long *)&a.delta[0], (unsigned long long)td0);
-      atomicAdd((unsigned long long *)&a.delta[1], (unsigned long long)td1);
-    }
-    if (fallbacks) atomicAdd(a.err + 1, fallbacks);
-  }
+  if (tid == 0) block_sums_store<VT_NW>(a, b, part, steps, fallbacks);
 }
 
 // The round's delta sums d[0..1] into a host mailbox slot (coherent mapped
@@ -2361,36 +2439,16 @@ __global__ __launch_bounds__(WAVE, 2) void santa_sp_kernel(SantaArgs a) {
     }
   }
   __syncthreads();
-  int big = 0;
-  {  // exclusive scan of the counts over types -> start of each type in csort
-    const int per = (a.ng + WAVE - 1) / WAVE;
-    const int t0s = lane * per, t1s = min(a.ng, t0s + per);
-    uint32_t sum = 0;
-    for (int t = t0s; t < t1s; ++t) sum += tcnt[t] >> 16;
-    uint32_t run = wave_incl_scan_u32(sum) - sum;
-    for (int t = t0s; t < t1s; ++t) {
-      const uint32_t h = tcnt[t];
-      tcnt[t] = h | run;  // low half: fill cursor
-      big |= (h >> 16) >= 255u;
-      run += h >> 16;
-    }
-  }
+  const int big = type_scan_wave(tcnt, a.ng, lane);  // start of each type in csort
   __syncthreads();
 #pragma unroll
   for (int k = 0; k < 4; ++k)
     if (myt[k] >= 0) csort[atomicAdd(&tcnt[myt[k]], 1u) & 0xFFFFu] = (uint8_t)rowc_slot(4 * lane + k);
   __syncthreads();
-  {  // per type: c0 | c1 << 8 | (count <= 3 ? c2 : start in csort) << 16 | count << 24
+  {  // the types' head words
     const int per = (a.ng + WAVE - 1) / WAVE;
     const int t0s = lane * per, t1s = min(a.ng, t0s + per);
-    for (int t = t0s; t < t1s; ++t) {
-      const uint32_t h = tcnt[t];
-      const uint32_t c = h >> 16, e = (h & 0xFFFFu) - c;  // start in csort
-      const uint32_t x2 = c <= 3u ? (uint32_t)csort[e + 2] : e;
-      thead[t] = c ? ((uint32_t)csort[e] | ((uint32_t)csort[e + 1] << 8) | (x2 << 16) |
-                      (min(c, 255u) << 24))
-                   : 0u;
-    }
+    for (int t = t0s; t < t1s; ++t) thead[t] = type_head_word(tcnt[t], csort);
   }
   __syncthreads();
   const uint64_t tc = (a.flags & SH_FLAG_TIMING) ? wall_clock64() : 0;
@@ -2530,10 +2588,7 @@ __global__ __launch_bounds__(WAVE, 2) void santa_sp_kernel(SantaArgs a) {
 #pragma unroll
     for (int x = 0; x < 3; ++x) asm volatile("" ::"v"(warm[k][x]));
   if (!fits) {  // does not fit: leave the block to the fallback kernel
-    if (lane == 0) {
-      const int p = atomicAdd(a.ovf_cnt, 1);
-      a.ovf_list[p] = b;
-    }
+    if (lane == 0) leave_to_fallback(a, b);
     return;
   }
   if (lane == 0) off[n] = (uint16_t)base;
@@ -2776,13 +2831,15 @@ __global__ __launch_bounds__(WAVE, 2) void santa_sp_kernel(SantaArgs a) {
         const int64_t cij = u_l[i] + vcol;  // = C[i][col] (tight matched edge)
         const uint32_t cn = (cij == E) ? 0u : (uint32_t)((cij >> 32) + nw1);
         cost += cij;
-        dch += child_happy(cn, nw1) - child_happy(co, nw1);
-        if (a.delta) dgh += gift_happy(a, child, tnew) - gift_happy(a, child, told);
+        dch += child_delta(nw1, cn, co);
+        if (a.delta) dgh += gift_delta<0>(a, child, tnew, child, told);
       }
       if (a.col) a.col[(size_t)b * n + i] = col;
       if (!(a.flags & SH_FLAG_NO_APPLY)) a.types[child] = (int16_t)tnew;  // this block owns child; ctype holds old types
     }
   }
+  // (wave_outputs with the timing words between its stores: with them moved
+  // behind it the compiler laid out the whole kernel anew, the step loop too)
   cost = wave_sum_i64(cost);
   dch = wave_sum_i64(dch);
   dgh = wave_sum_i64(dgh);
@@ -2816,8 +2873,10 @@ __global__ __launch_bounds__(WAVE, 2) void santa_sp_kernel(SantaArgs a) {
 //                      through a small LDS list) and stores it to a per-block
 //                      record in HBM (~18 KB per block, ~70 MB per 3730-block
 //                      round: ~25 us of HBM time against ~2 ms of solving);
-//   santa_sp2_kernel   loads the tile into VGPRs (coalesced 16-byte loads)
-//                      and runs the solve with the build's registers free.
+//   santa_sp3_kernel   (FUSED = false; round 2's santa_sp2_kernel, retired,
+//                      was the first) loads the tile into VGPRs (coalesced
+//                      16-byte loads) and runs the solve with the build's
+//                      registers free.
 // Tile layout: two u32x32 vectors T0, T1 (64 VGPRs); row i lives in VGPR
 // q = i >> 2 (T0 for q < 32, else T1), lanes 32L..32L+31 with
 // L = (i >> 1) & 1, 16-bit half H = i & 1; the row's entry x is in lane
@@ -2988,37 +3047,18 @@ __global__ __launch_bounds__(TILE_NW * WAVE) __attribute__((amdgpu_waves_per_eu(
   if (myt >= 0) atomicAdd(&tcnt[myt], 1u << 16);
   __syncthreads();
   int big = 0;
-  if (tid < WAVE) {  // exclusive scan of the counts over types -> start of each type in csort
-    const int per = (a.ng + WAVE - 1) / WAVE;
-    const int t0s = lane * per, t1s = min(a.ng, t0s + per);
-    uint32_t sum = 0;
-    for (int t = t0s; t < t1s; ++t) sum += tcnt[t] >> 16;
-    uint32_t run = wave_incl_scan_u32(sum) - sum;
-    for (int t = t0s; t < t1s; ++t) {
-      const uint32_t h = tcnt[t];
-      tcnt[t] = h | run;  // low half: fill cursor
-      big |= (h >> 16) >= 255u;
-      run += h >> 16;
-    }
-  }
+  if (tid < WAVE) big = type_scan_wave(tcnt, a.ng, lane);  // start of each type in csort
   if (__syncthreads_or(big)) {  // a type with 255+ columns: leave the block to the fallback
     if (tid == 0) {
       *status = 1;
-      const int p = atomicAdd(a.ovf_cnt, 1);
-      a.ovf_list[p] = b;
+      leave_to_fallback(a, b);
     }
     return;
   }
   if (myt >= 0) csort[atomicAdd(&tcnt[myt], 1u) & 0xFFFFu] = (uint8_t)rowc_slot(tid);
   __syncthreads();
-  // per type, in place: c0 | c1 << 8 | (count <= 3 ? c2 : start in csort) << 16 | count << 24
-  for (int t = tid; t < a.ng; t += TILE_NW * WAVE) {
-    const uint32_t h = tcnt[t];
-    const uint32_t c = h >> 16, e = (h & 0xFFFFu) - c;  // start in csort
-    const uint32_t x2 = c <= 3u ? (uint32_t)csort[e + 2] : e;
-    thead[t] = c ? ((uint32_t)csort[e] | ((uint32_t)csort[e + 1] << 8) | (x2 << 16) | (min(c, 255u) << 24))
-                 : 0u;
-  }
+  // the types' head words, in place
+  for (int t = tid; t < a.ng; t += TILE_NW * WAVE) thead[t] = type_head_word(tcnt[t], csort);
   __syncthreads();
 
   // -- pass 1: the row's hit count and its own gift's code -----------------------------
@@ -3120,8 +3160,7 @@ __global__ __launch_bounds__(TILE_NW * WAVE) __attribute__((amdgpu_waves_per_eu(
   if (__syncthreads_or(!fits)) {  // does not fit: leave the block to the fallback kernel
     if (tid == 0) {
       *status = 1;
-      const int p = atomicAdd(a.ovf_cnt, 1);
-      a.ovf_list[p] = b;
+      leave_to_fallback(a, b);
     }
     return;
   }
@@ -3375,25 +3414,8 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
     for (int k = 0; k < 4; ++k)
       if (tk[k] >= 0) atomicAdd(&thead[tk[k]], 1u << 16);
     __syncthreads();
-    int big = 0;
-    {  // exclusive scan of the counts over types -> start of each type in csort
-      const int per = (a.ng + WAVE - 1) / WAVE;
-      const int t0s = lane * per, t1s = min(a.ng, t0s + per);
-      uint32_t sum = 0;
-      for (int t = t0s; t < t1s; ++t) sum += thead[t] >> 16;
-      uint32_t run = wave_incl_scan_u32(sum) - sum;
-      for (int t = t0s; t < t1s; ++t) {
-        const uint32_t h = thead[t];
-        thead[t] = h | run;  // low half: fill cursor
-        big |= (h >> 16) >= 255u;
-        run += h >> 16;
-      }
-    }
-    if (__any(big)) {  // a type with 255+ columns: leave the block to the fallback
-      if (lane == 0) {
-        const int p = atomicAdd(a.ovf_cnt, 1);
-        a.ovf_list[p] = b;
-      }
+    if (__any(type_scan_wave(thead, a.ng, lane))) {  // a type with 255+ columns: leave the block to the fallback
+      if (lane == 0) leave_to_fallback(a, b);
       return;
     }
     __syncthreads();
@@ -3401,14 +3423,8 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
     for (int k = 0; k < 4; ++k)
       if (tk[k] >= 0) csort[atomicAdd(&thead[tk[k]], 1u) & 0xFFFFu] = (uint8_t)rowc_slot(4 * lane + k);
     __syncthreads();
-    // per type, in place: c0 | c1 << 8 | (count <= 3 ? c2 : start in csort) << 16 | count << 24
-    for (int t = lane; t < a.ng; t += WAVE) {
-      const uint32_t h = thead[t];
-      const uint32_t c = h >> 16, e = (h & 0xFFFFu) - c;
-      const uint32_t x2 = c <= 3u ? (uint32_t)csort[e + 2] : e;
-      thead[t] = c ? ((uint32_t)csort[e] | ((uint32_t)csort[e + 1] << 8) | (x2 << 16) | (min(c, 255u) << 24))
-                   : 0u;
-    }
+    // the types' head words, in place
+    for (int t = lane; t < a.ng; t += WAVE) thead[t] = type_head_word(thead[t], csort);
     __syncthreads();
     // -- four batches of 64 rows: pass 1 (hit count, own code), pass 2 (entries) -----
     const int nw = a.n_wish;
@@ -3519,10 +3535,7 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
         }
       }
       if (__any(!fits)) {  // does not fit: leave the block to the fallback kernel
-        if (lane == 0) {
-          const int p = atomicAdd(a.ovf_cnt, 1);
-          a.ovf_list[p] = b;
-        }
+        if (lane == 0) leave_to_fallback(a, b);
         return;
       }
       __syncthreads();
@@ -4020,10 +4033,7 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
     for (int k = 0; k < 4; ++k)  // (the output decode's u)
       if (4 * lq + k < n) big |= (((uint32_t)u_l[4 * lq + k] + LR.CU) & LR.MU) != 0;
     if (__builtin_expect(__any(big), 0)) {
-      if (lane == 0) {
-        const int p = atomicAdd(a.ovf_cnt, 1);
-        a.ovf_list[p] = b;
-      }
+      if (lane == 0) leave_to_fallback(a, b);
       return;
     }
   }
@@ -4064,27 +4074,17 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
         const int64_t cij = (int64_t)ac * 4294967296LL + (int64_t)mc * E;
         const uint32_t cn = mc ? 0u : (uint32_t)(ac + nw1);
         cost += cij;
-        dch += child_happy(cn, nw1) - child_happy(co, nw1);
-        if (a.delta) dgh += gift_happy(a, chd, tnew) - gift_happy(a, chd, told);
+        dch += child_delta(nw1, cn, co);
+        if (a.delta) dgh += gift_delta<0>(a, chd, tnew, chd, told);
       }
       if (a.col && !TIMED) a.col[(size_t)b * n + i] = col;
       if (!(a.flags & SH_FLAG_NO_APPLY)) a.types[chd] = (int16_t)tnew;  // this block owns chd
     }
   }
-  cost = wave_sum_i64(cost);
-  dch = wave_sum_i64(dch);
-  dgh = wave_sum_i64(dgh);
-  if (lane == 0) {
-    if (a.cost) a.cost[b] = cost;
-    if (a.steps) a.steps[b] = steps;
-    if (TIMED && a.col && n >= 7) {
-      const uint64_t seg[7] = {tA, tB, tC, tD, tA1, tD1, tD2};
-      for (int q = 0; q < 7; ++q) a.col[(size_t)b * n + q] = (int32_t)min(seg[q], (uint64_t)INT32_MAX);
-    }
-    if (a.delta) {
-      atomicAdd((unsigned long long *)&a.delta[0], (unsigned long long)dch);
-      atomicAdd((unsigned long long *)&a.delta[1], (unsigned long long)dgh);
-    }
+  wave_outputs(a, b, lane, cost, dch, dgh, steps);
+  if (TIMED && lane == 0 && a.col && n >= 7) {
+    const uint64_t seg[7] = {tA, tB, tC, tD, tA1, tD1, tD2};
+    for (int q = 0; q < 7; ++q) a.col[(size_t)b * n + q] = (int32_t)min(seg[q], (uint64_t)INT32_MAX);
   }
 }
 
@@ -4402,10 +4402,7 @@ __global__ __launch_bounds__(SANTA_WG) void santa_dt_kernel(SantaArgs a) {
   // the lattice range (see santa_sp3_kernel): leave the block to the fallback
   // launch (the outputs come from the tile, so the final duals need no check)
   if (__builtin_expect(__any(bad || ((accU & LR.MU) | (accW & LR.MW)) != 0), 0)) {
-    if (lane == 0) {
-      const int p = atomicAdd(a.ovf_cnt, 1);
-      a.ovf_list[p] = b;
-    }
+    if (lane == 0) leave_to_fallback(a, b);
     return;
   }
   int64_t cost = 0, dch = 0, dgh = 0;
@@ -4419,26 +4416,16 @@ __global__ __launch_bounds__(SANTA_WG) void santa_dt_kernel(SantaArgs a) {
       const int told = ctype[i], tnew = ctype[col];
       const int chd = rows_l[i];
       cost += single_cost(cn, nw1, E);
-      dch += child_happy(cn, nw1) - child_happy(co, nw1);
-      if (a.delta) dgh += gift_happy(a, chd, tnew) - gift_happy(a, chd, told);
+      dch += child_delta(nw1, cn, co);
+      if (a.delta) dgh += gift_delta<0>(a, chd, tnew, chd, told);
       if (a.col && !TIMED) a.col[(size_t)b * n + i] = col;
       if (!(a.flags & SH_FLAG_NO_APPLY)) a.types[chd] = (int16_t)tnew;  // this block owns chd
     }
   }
-  cost = wave_sum_i64(cost);
-  dch = wave_sum_i64(dch);
-  dgh = wave_sum_i64(dgh);
-  if (lane == 0) {
-    if (a.cost) a.cost[b] = cost;
-    if (a.steps) a.steps[b] = steps;
-    if (TIMED && a.col && n >= 4) {
-      const uint64_t seg[4] = {tA, tB, tC, tD};
-      for (int q = 0; q < 4; ++q) a.col[(size_t)b * n + q] = (int32_t)min(seg[q], (uint64_t)INT32_MAX);
-    }
-    if (a.delta) {
-      atomicAdd((unsigned long long *)&a.delta[0], (unsigned long long)dch);
-      atomicAdd((unsigned long long *)&a.delta[1], (unsigned long long)dgh);
-    }
+  wave_outputs(a, b, lane, cost, dch, dgh, steps);
+  if (TIMED && lane == 0 && a.col && n >= 4) {
+    const uint64_t seg[4] = {tA, tB, tC, tD};
+    for (int q = 0; q < 4; ++q) a.col[(size_t)b * n + q] = (int32_t)min(seg[q], (uint64_t)INT32_MAX);
   }
 }
 
@@ -4581,7 +4568,7 @@ __device__ __forceinline__ void big_block_outputs(const SantaArgs &a, const int 
                                                   const int16_t *ctype, const int32_t *rows_l, int64_t *part,
                                                   const int64_t steps, const int fallbacks) {
   constexpr int WG = NW * WAVE;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int tid = threadIdx.x;
   const int nw1 = a.n_wish + 1;
   int64_t cost = 0, dch = 0, dgh = 0;
   for (int i = tid; i < n; i += WG) {
@@ -4591,8 +4578,8 @@ __device__ __forceinline__ void big_block_outputs(const SantaArgs &a, const int 
     const uint32_t n1 = wish_code(a, child, tnew), o1 = wish_code(a, child, told);
     if (MODE == 0) {
       cost += single_cost(n1, nw1, a.E);
-      dch += child_happy(n1, nw1) - child_happy(o1, nw1);
-      if (a.delta) dgh += gift_happy(a, child, tnew) - gift_happy(a, child, told);
+      dch += child_delta(nw1, n1, o1);
+      if (a.delta) dgh += gift_delta<0>(a, child, tnew, child, told);
     } else if (MODE == 2) {
       const uint32_t n2 = wish_code(a, child + 1, tnew), o2 = wish_code(a, child + 1, told);
       const uint32_t n3 = wish_code(a, child + 2, tnew), o3 = wish_code(a, child + 2, told);
@@ -4604,47 +4591,25 @@ __device__ __forceinline__ void big_block_outputs(const SantaArgs &a, const int 
     } else {
       const uint32_t n2 = wish_code(a, child + 1, tnew), o2 = wish_code(a, child + 1, told);
       cost += twin_cost(n1 | (n2 << 8), nw1, a.E);
-      dch += child_happy(n1, nw1) + child_happy(n2, nw1) - child_happy(o1, nw1) - child_happy(o2, nw1);
-      if (a.delta) dgh += gift_happy(a, child, tnew) + gift_happy(a, child + 1, tnew) -
-             gift_happy(a, child, told) - gift_happy(a, child + 1, told);
+      dch += child_delta_twin(nw1, n1, n2, o1, o2);
+      if (a.delta) dgh += gift_delta<1>(a, child, tnew, child, told);
     }
     if (a.col) a.col[(size_t)b * n + i] = col;
   }
-  cost = wave_sum_i64(cost);
-  dch = wave_sum_i64(dch);
-  dgh = wave_sum_i64(dgh);
-  if (lane == 0) {
-    part[3 * w + 0] = cost;
-    part[3 * w + 1] = dch;
-    part[3 * w + 2] = dgh;
-  }
+  block_sums_put(part, cost, dch, dgh);
   __syncthreads();  // every old type was read from ctype (LDS): apply in place
   for (int i = tid; i < n; i += WG) {
     const int16_t tnew = ctype[c4r[i]];
     if (!(a.flags & SH_FLAG_NO_APPLY)) for (int m = 0; m <= MODE; ++m) a.types[rows_l[i] + m] = tnew;
   }
-  if (tid == 0) {
-    int64_t tc = 0, t0 = 0, t1 = 0;
-    for (int q = 0; q < NW; ++q) {
-      tc += part[3 * q];
-      t0 += part[3 * q + 1];
-      t1 += part[3 * q + 2];
-    }
-    if (a.cost) a.cost[b] = tc;
-    if (a.steps) a.steps[b] = steps;
-    if (a.delta) {
-      atomicAdd((unsigned long long *)&a.delta[0], (unsigned long long)t0);
-      atomicAdd((unsigned long long *)&a.delta[1], (unsigned long long)t1);
-    }
-    if (fallbacks) atomicAdd(a.err + 1, fallbacks);
-  }
+  if (tid == 0) block_sums_store<NW>(a, b, part, steps, fallbacks);
 }
 
 template <int MODE, int NW, int K, int FB>
 __device__ __forceinline__ void santa_big_block(const SantaArgs &a, const int b) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int WG = NW * WAVE;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int tid = threadIdx.x;
   const int n = a.n;
   const BigLds L = big_lds_layout(n, MODE, a.ng, NW, K);
   SolveLds S{(int64_t *)(smem + L.u), (int16_t *)(smem + L.c4r), (int16_t *)(smem + L.r4c),
@@ -4692,23 +4657,7 @@ __device__ __forceinline__ void santa_big_block(const SantaArgs &a, const int b)
   }
   for (int j = tid; j < n; j += WG) atomicAdd(&thead[ctype[j]], 1u << 16);
   __syncthreads();
-  {  // block-wide exclusive scan of the counts over types
-    const int per = (a.ng + WG - 1) / WG;
-    const int t0 = tid * per, t1 = min(a.ng, t0 + per);
-    uint32_t sum = 0;
-    for (int t = t0; t < t1; ++t) sum += thead[t] >> 16;
-    const uint32_t incl = wave_incl_scan_u32(sum);
-    if (lane == 63) scan[w] = incl;
-    __syncthreads();
-    uint32_t wbase = 0;
-    for (int q = 0; q < w; ++q) wbase += scan[q];
-    uint32_t run = wbase + incl - sum;
-    for (int t = t0; t < t1; ++t) {
-      const uint32_t h = thead[t];
-      thead[t] = h | run;  // low half: fill cursor from the type's start
-      run += h >> 16;
-    }
-  }
+  type_scan_block<WG, false>(thead, a.ng, scan);  // (uint16 column lists)
   __syncthreads();
   for (int j = tid; j < n; j += WG) csort[atomicAdd(&thead[ctype[j]], 1u) & 0xFFFFu] = (uint16_t)j;
   __syncthreads();  // thead = end of the type's run | count << 16
@@ -5248,7 +5197,7 @@ __global__ __launch_bounds__(NW * WAVE) void santa_lb_kernel(SantaArgs a) {
     for (int i = tid; i < n; i += WG) c4r[i] = (int16_t)i;
   }
   if (__syncthreads_or(big)) {  // left untouched: solved by the fallback launch
-    if (tid == 0) a.ovf_list[atomicAdd(a.ovf_cnt, 1)] = b;
+    if (tid == 0) leave_to_fallback(a, b);
     return;
   }
   if (!(a.flags & SH_FLAG_BUILD_ONLY)) {  // c4r: slots -> columns (path_l: the slot -> column table)
@@ -5288,17 +5237,21 @@ __device__ __forceinline__ double widen_f64(sh_bf16 x) {
   return (double)__uint_as_float((uint32_t)x.bits << 16);
 }
 
-template <int K, typename S>
+// The float solvers' rows from global memory.  Thread (w, lane) loads its
+// mw_col columns: mw_col<NW, K>(w, k, lane) = threadIdx.x + 64 NW k.  NW = 1
+// is sap_solve<K, double>'s one wave (columns lane + 64 k).
+template <int NW, int K, typename S>
 struct GlobalLoaderF64 {
   const S *base;
   int n;   // live columns: j >= n is never read
   int ld;  // row stride (elements)
   __device__ __forceinline__ void load(int i, double (&c)[K]) const {
     const S *row = base + (size_t)i * ld;
+    const int j0 = threadIdx.x;
     if constexpr (std::is_same<S, double>::value) {
 #pragma unroll
       for (int k = 0; k < K; ++k) {
-        const int j = threadIdx.x + WAVE * k;
+        const int j = j0 + WAVE * NW * k;
         c[k] = (j < n) ? row[j] : 0.0;
       }
     } else {
@@ -5310,34 +5263,9 @@ struct GlobalLoaderF64 {
       // (measured: 2.6x on 1024-column float32 rows).
       S raw[K];
 #pragma unroll
-      for (int k = 0; k < K; ++k) raw[k] = row[min((int)threadIdx.x + WAVE * k, n - 1)];
+      for (int k = 0; k < K; ++k) raw[k] = row[min(j0 + WAVE * NW * k, n - 1)];
 #pragma unroll
-      for (int k = 0; k < K; ++k) c[k] = ((int)threadIdx.x + WAVE * k < n) ? widen_f64(raw[k]) : 0.0;
-    }
-  }
-};
-
-// The same rows for sap_solve_mw_f64: thread (w, lane) loads its mw_col columns.
-template <int NW, int K, typename S>
-struct GlobalLoaderF64MW {
-  const S *base;
-  int n;   // live columns: j >= n is never read
-  int ld;  // row stride (elements)
-  __device__ __forceinline__ void load(int i, double (&c)[K]) const {
-    const S *row = base + (size_t)i * ld;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if constexpr (std::is_same<S, double>::value) {
-#pragma unroll
-      for (int k = 0; k < K; ++k) {
-        const int j = mw_col<NW, K>(w, k, lane);
-        c[k] = (j < n) ? row[j] : 0.0;
-      }
-    } else {  // (branch-free loads, widened after all K are issued: see GlobalLoaderF64)
-      S raw[K];
-#pragma unroll
-      for (int k = 0; k < K; ++k) raw[k] = row[min(mw_col<NW, K>(w, k, lane), n - 1)];
-#pragma unroll
-      for (int k = 0; k < K; ++k) c[k] = (mw_col<NW, K>(w, k, lane) < n) ? widen_f64(raw[k]) : 0.0;
+      for (int k = 0; k < K; ++k) c[k] = (j0 + WAVE * NW * k < n) ? widen_f64(raw[k]) : 0.0;
     }
   }
 };
@@ -5566,6 +5494,14 @@ __device__ __forceinline__ void duals_fill(T *du, T *dv, int b, int NR, int NC, 
   for (int j = c0 + (int)threadIdx.x; j < NC; j += WG) dv[(size_t)b * NC + j] = x;
 }
 
+// An empty or invalid-shape instance (see lsap_shape): -1s, cost 0, zero duals.
+template <int WG, typename T, typename... DU>
+__device__ __forceinline__ void lsap_no_instance(int32_t *col, T *cost, int b, int NR, int NC, DU... duals) {
+  for (int i = threadIdx.x; i < NR; i += WG) col[(size_t)b * NR + i] = -1;
+  if (threadIdx.x == 0 && cost) cost[b] = 0;
+  if constexpr (sizeof...(DU) == 2) duals_fill<T, WG>(duals_u(duals...), duals_v(duals...), b, NR, NC, 0, 0, (T)0);
+}
+
 // After a float solve: u from LDS, or NaN in the live slots of u and v for an
 // infeasible instance (the solver stored no v then); 0 in the padding.
 template <int WG>
@@ -5594,10 +5530,7 @@ __global__ __launch_bounds__(NW * WAVE) void lsap_i64_kernel(const S *C, uint64_
   int nr = NC, n = NC;  // live rows and columns
   if constexpr (RECT) {
     if (!lsap_shape(shape, b, NR, NC, nr, n)) {
-      for (int i = tid; i < NR; i += NW * WAVE) col[(size_t)b * NR + i] = -1;
-      if (tid == 0 && cost) cost[b] = 0;
-      if constexpr (DUALS)
-        duals_fill<int64_t, NW * WAVE>(duals_u(duals...), duals_v(duals...), b, NR, NC, 0, 0, 0);
+      lsap_no_instance<NW * WAVE>(col, cost, b, NR, NC, duals...);
       return;
     }
   }
@@ -5667,9 +5600,7 @@ __global__ __launch_bounds__(WAVE) void lsap_f64_kernel(const S *C, int NR, int 
   const int lane = threadIdx.x;
   int nr, n;  // live rows and columns (see lsap_i64_kernel)
   if (!lsap_shape(shape, b, NR, NC, nr, n)) {
-    for (int i = lane; i < NR; i += WAVE) col[(size_t)b * NR + i] = -1;
-    if (lane == 0 && cost) cost[b] = 0;
-    if constexpr (DUALS) duals_fill<double, WAVE>(duals_u(duals...), duals_v(duals...), b, NR, NC, 0, 0, 0.0);
+    lsap_no_instance<WAVE>(col, cost, b, NR, NC, duals...);
     return;
   }
   double *u_l = (double *)smem;
@@ -5681,7 +5612,7 @@ __global__ __launch_bounds__(WAVE) void lsap_f64_kernel(const S *C, int NR, int 
   __syncthreads();
   int64_t steps = 0;
   const size_t base = (size_t)b * NR * NC;
-  using GL = GlobalLoaderF64<K, S>;
+  using GL = GlobalLoaderF64<1, K, S>;
   std::conditional_t<DUALS, WithDuals<GL, double>, GL> ld{GL{C + base, n, NC}};
   if constexpr (DUALS) ld.dv = duals_v(duals...) + (size_t)b * NC;
   const int st = sap_solve<K, double, DUALS>(nr, n, ld, u_l, c4r_l, steps);
@@ -5717,9 +5648,7 @@ __global__ __launch_bounds__(NW * WAVE) void lsap_f64_mw_kernel(const S *C, int 
   const int tid = threadIdx.x;
   int nr, n;  // live rows and columns (see lsap_i64_kernel)
   if (!lsap_shape(shape, b, NR, NC, nr, n)) {
-    for (int i = tid; i < NR; i += WG) col[(size_t)b * NR + i] = -1;
-    if (tid == 0 && cost) cost[b] = 0;
-    if constexpr (DUALS) duals_fill<double, WG>(duals_u(duals...), duals_v(duals...), b, NR, NC, 0, 0, 0.0);
+    lsap_no_instance<WG>(col, cost, b, NR, NC, duals...);
     return;
   }
   size_t off = 0;
@@ -5740,7 +5669,7 @@ __global__ __launch_bounds__(NW * WAVE) void lsap_f64_mw_kernel(const S *C, int 
   }
   __syncthreads();
   const size_t base = (size_t)b * NR * NC;
-  using GL = GlobalLoaderF64MW<NW, K, S>;
+  using GL = GlobalLoaderF64<NW, K, S>;
   std::conditional_t<DUALS, WithDuals<GL, double>, GL> ld{GL{C + base, n, NC}};
   if constexpr (DUALS) ld.dv = duals_v(duals...) + (size_t)b * NC;
   const int st = sap_solve_mw_f64<NW, K, DUALS>(nr, n, ld, Sl);
