@@ -119,6 +119,9 @@ extern "C" {
  * reference's own sizes are 2000 singles and 3000 pairs.  n <= 256 runs the
  * on-chip tile kernels, larger blocks rebuild each row from the wishlist. */
 #define SH_MAX_N_SANTA 4096
+/* Largest rows or columns of the lsap_solve_large_ and lsap_check_duals_large_
+ * entries (the dense solver at the reference's own block sizes, 2000 and 3000). */
+#define SH_MAX_N_LARGE 4096
 
 typedef struct sh_ctx sh_ctx;
 
@@ -464,6 +467,76 @@ int lsap_check_duals_f16(const uint16_t *d_C, int nr, int nc, int B, const int32
 int lsap_check_duals_bf16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
                           const int32_t *d_col, const double *d_u, const double *d_v,
                           double *d_slack, int32_t *d_flags, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * The batched solver and its certificate up to SH_MAX_N_LARGE = 4096 rows or
+ * columns: 1 <= nr <= nc <= SH_MAX_N_LARGE.  A surface beside the entries above,
+ * which keep their limit SH_MAX_N.
+ *
+ * lsap_solve_large_*: the argument list of lsap_solve_batched_duals_*, with
+ * d_u and d_v nullable, both or neither (one null and one not: SH_ERR_ARGS);
+ * d_cost nullable.  lsap_check_duals_large_*: the argument list and meaning of
+ * lsap_check_duals_*.
+ *
+ * The contract is the one stated above for the _rect_, _duals_ and
+ * check_duals entries: d_col is scipy's col_ind, ties included; d_cost the sum
+ * of the chosen entries, floats in the fixed summation order; a ragged
+ * d_shape instance reads nothing outside its corner; an empty or invalid shape
+ * gives -1, cost 0 and zero duals; an infeasible float instance -1 everywhere
+ * and NaN duals; the duals carry the signs and equalities of the _duals_
+ * entries, integer duals exact, float duals the bits of scipy's own run;
+ * SH_FLAG_EXACT_ARGMIN works on the integer entries.  Up to SH_MAX_N columns
+ * the entries run the kernels of the entries above (the same bits); beyond,
+ * the integer solver's packed key has 12-bit fields and its window is
+ * d in [2^32 - 2^38, 2^38 - 2^32) (steps outside it take the exact two-pass
+ * argmin), and the float solver runs 8 waves per instance with 4, 6 or 8
+ * columns per thread.
+ *
+ * i64: exact for |C| < 2^50 when nc <= 1024 and for |C| < 2^48 above (the same
+ * factor 4n below 2^62).
+ *
+ * Checked on the host before any device call, SH_ERR_ARGS for: nr < 1,
+ * nr > nc, nc > SH_MAX_N_LARGE, B < 0; with B > 0 a null d_C or d_col (check:
+ * or d_u, d_v, d_slack, d_flags); on the float solve entries SH_FLAG_F64_MW
+ * with SH_FLAG_F64_SW, and SH_FLAG_F64_SW with nc > SH_MAX_N (there is no
+ * one-wave float kernel above that size).  B == 0 is a no-op after the checks.
+ * ------------------------------------------------------------------------ */
+int lsap_solve_large_i64(const int64_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                         int32_t *d_col, int64_t *d_cost, int64_t *d_u, int64_t *d_v, unsigned flags,
+                         void *stream);
+int lsap_solve_large_i32(const int32_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                         int32_t *d_col, int64_t *d_cost, int64_t *d_u, int64_t *d_v, unsigned flags,
+                         void *stream);
+int lsap_solve_large_f64(const double *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                         int32_t *d_col, double *d_cost, double *d_u, double *d_v, unsigned flags,
+                         void *stream);
+int lsap_solve_large_f32(const float *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                         int32_t *d_col, double *d_cost, double *d_u, double *d_v, unsigned flags,
+                         void *stream);
+int lsap_solve_large_f16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                         int32_t *d_col, double *d_cost, double *d_u, double *d_v, unsigned flags,
+                         void *stream);
+int lsap_solve_large_bf16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                         int32_t *d_col, double *d_cost, double *d_u, double *d_v, unsigned flags,
+                         void *stream);
+int lsap_check_duals_large_i64(const int64_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                               const int32_t *d_col, const int64_t *d_u, const int64_t *d_v,
+                               int64_t *d_slack, int32_t *d_flags, void *stream);
+int lsap_check_duals_large_i32(const int32_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                               const int32_t *d_col, const int64_t *d_u, const int64_t *d_v,
+                               int64_t *d_slack, int32_t *d_flags, void *stream);
+int lsap_check_duals_large_f64(const double *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                               const int32_t *d_col, const double *d_u, const double *d_v,
+                               double *d_slack, int32_t *d_flags, void *stream);
+int lsap_check_duals_large_f32(const float *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                               const int32_t *d_col, const double *d_u, const double *d_v,
+                               double *d_slack, int32_t *d_flags, void *stream);
+int lsap_check_duals_large_f16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                               const int32_t *d_col, const double *d_u, const double *d_v,
+                               double *d_slack, int32_t *d_flags, void *stream);
+int lsap_check_duals_large_bf16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                               const int32_t *d_col, const double *d_u, const double *d_v,
+                               double *d_slack, int32_t *d_flags, void *stream);
 
 /* ---------------------------------------------------------------------------
  * Synthetic data of the Kaggle shape (host, deterministic, seeded counter

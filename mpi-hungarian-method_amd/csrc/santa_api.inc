@@ -889,8 +889,10 @@ int sh_unpack_types(int16_t *d_types, const int32_t *d_rows, int count, const in
 
 namespace {
 // nr x nc instances (the square entries: nr == nc == n); host-side only.
-int check_lsap_args(int nr, int nc, int B, const int32_t *col) {
-  if (nr < 1 || nc > SH_MAX_N) return fail(SH_ERR_ARGS, "sizes must be in [1, 1024]");
+// (cap: SH_MAX_N, or SH_MAX_N_LARGE for the lsap_*_large_ entries)
+int check_lsap_args(int nr, int nc, int B, const int32_t *col, int cap = SH_MAX_N) {
+  if (nr < 1 || nc > cap)
+    return fail(SH_ERR_ARGS, cap == SH_MAX_N ? "sizes must be in [1, 1024]" : "sizes must be in [1, 4096]");
   if (nr > nc) return fail(SH_ERR_ARGS, "nr > nc: transpose tall input (as scipy does) and solve that");
   if (B < 0) return fail(SH_ERR_ARGS, "B < 0");
   if (!col && B > 0) return fail(SH_ERR_ARGS, "null col");
@@ -917,13 +919,13 @@ int launch_lsap_i64(const S *C, uint64_t seed, int64_t mod, int nr, int n, int B
                      r16((size_t)4 * 4 * 8) + 64;
   const bool rect = nr != n || shape;
 #define L__(NWW, KK, RR)                                                                            \
-  hipLaunchKernelGGL((lsap_i64_kernel<NWW, KK, S, HASH, RR>), dim3(B), dim3(NWW * WAVE), lds, s, C, \
+  hipLaunchKernelGGL((lsap_i64_kernel<NWW, KK, S, HASH, RR, 10>), dim3(B), dim3(NWW * WAVE), lds, s, C, \
                      seed, mod, nr, n, shape, col, cost, (int32_t *)nullptr, flags)
 #define L_(NWW, KK)                                                                                  \
   do {                                                                                               \
     if constexpr (DUALS)                                                                             \
-      hipLaunchKernelGGL((lsap_i64_kernel<NWW, KK, S, HASH, true, int64_t *, int64_t *>), dim3(B),   \
-                         dim3(NWW * WAVE), lds, s, C, seed, mod, nr, n, shape, col, cost,            \
+      hipLaunchKernelGGL((lsap_i64_kernel<NWW, KK, S, HASH, true, 10, int64_t *, int64_t *>),        \
+                         dim3(B), dim3(NWW * WAVE), lds, s, C, seed, mod, nr, n, shape, col, cost,   \
                          (int32_t *)nullptr, flags, du, dv);                                         \
     else if (rect) L__(NWW, KK, true);                                                               \
     else L__(NWW, KK, false);                                                                        \
@@ -978,11 +980,11 @@ int launch_lsap_f64(const S *C, int nr, int n, int B, const int32_t *shape, int3
 #define L_(KK)                                                                                        \
   do {                                                                                                \
     if constexpr (DUALS)                                                                              \
-      hipLaunchKernelGGL((lsap_f64_mw_kernel<NW, KK, S, double *, double *>), dim3(B),                \
+      hipLaunchKernelGGL((lsap_f64_mw_kernel<NW, KK, S, 10, double *, double *>), dim3(B),            \
                          dim3(NW * WAVE), lds, s, C, nr, n, shape, col, cost, du, dv);                \
     else                                                                                              \
-      hipLaunchKernelGGL((lsap_f64_mw_kernel<NW, KK, S>), dim3(B), dim3(NW * WAVE), lds, s, C, nr, n, \
-                         shape, col, cost);                                                           \
+      hipLaunchKernelGGL((lsap_f64_mw_kernel<NW, KK, S, 10>), dim3(B), dim3(NW * WAVE), lds, s, C,    \
+                         nr, n, shape, col, cost);                                                    \
   } while (0)
     if (n <= 256) L_(1);
     else if (n <= 512) L_(2);
@@ -1016,14 +1018,15 @@ int launch_lsap_f64(const S *C, int nr, int n, int B, const int32_t *shape, int3
 // S the stored cost type, T int64_t or double.  The pass over the corners
 // reads 16 bytes per load when every row starts 16-byte aligned; a batch too
 // small to fill the chip with one workgroup per instance is split by rows.
-template <typename S, typename T>
+// NCAP: the kernels' column capacity, SH_MAX_N or SH_MAX_N_LARGE.
+template <typename S, typename T, int NCAP = SH_MAX_N>
 int launch_lsap_check(const S *C, int nr, int n, int B, const int32_t *shape, const int32_t *col,
                       const T *u, const T *v, T *slack, int32_t *flg, hipStream_t s) {
-  const int rc = check_lsap_args(nr, n, B, col);
+  const int rc = check_lsap_args(nr, n, B, col, NCAP);
   if (rc) return rc;
   if (B > 0 && (!C || !u || !v || !slack || !flg)) return fail(SH_ERR_ARGS, "null C, u, v, slack or flags");
   if (B == 0) return SH_OK;
-  hipLaunchKernelGGL((lsap_cert_kernel<S, T>), dim3(B), dim3(CERT_WG), 0, s, C, nr, n, shape, col, u, v,
+  hipLaunchKernelGGL((lsap_cert_kernel<S, T, NCAP>), dim3(B), dim3(CERT_WG), 0, s, C, nr, n, shape, col, u, v,
                      slack, flg);
   // at least 8 rows per workgroup, about 2048 workgroups when the batch allows
   const int chunks = std::min(std::max(1, 2048 / B), (nr + 7) / 8);
@@ -1031,19 +1034,142 @@ int launch_lsap_check(const S *C, int nr, int n, int B, const int32_t *shape, co
   const dim3 grid(B, (nr + rows_per - 1) / rows_per);
   constexpr int VEC = 16 / (int)sizeof(S);
   if ((uintptr_t)C % 16 == 0 && n % VEC == 0)
-    hipLaunchKernelGGL((lsap_slack_kernel<S, T, VEC>), grid, dim3(CERT_WG), 0, s, C, nr, n, shape, u, v,
+    hipLaunchKernelGGL((lsap_slack_kernel<S, T, VEC, NCAP>), grid, dim3(CERT_WG), 0, s, C, nr, n, shape, u, v,
                        slack, flg, rows_per);
   else
-    hipLaunchKernelGGL((lsap_slack_kernel<S, T, 1>), grid, dim3(CERT_WG), 0, s, C, nr, n, shape, u, v,
+    hipLaunchKernelGGL((lsap_slack_kernel<S, T, 1, NCAP>), grid, dim3(CERT_WG), 0, s, C, nr, n, shape, u, v,
                        slack, flg, rows_per);
   hipLaunchKernelGGL((lsap_cert_final_kernel<T>), dim3((B + CERT_WG - 1) / CERT_WG), dim3(CERT_WG), 0, s,
                      B, slack, flg);
   HIP_TRY(hipGetLastError());
   return SH_OK;
 }
+
+// ---------------------------------------------------------------------------
+// The lsap_*_large_ entries: up to SH_MAX_N_LARGE columns.  Every check is made
+// on the host before any device call; up to SH_MAX_N columns they forward to
+// the launchers above (the same kernels, the same bits), beyond that to the
+// FB = 12 instantiations below.
+// ---------------------------------------------------------------------------
+template <typename T>
+int check_large_solve(const void *C, int nr, int nc, int B, const int32_t *col, const T *du, const T *dv) {
+  const int rc = check_lsap_args(nr, nc, B, col, SH_MAX_N_LARGE);
+  if (rc) return rc;
+  if (!C && B > 0) return fail(SH_ERR_ARGS, "null C");
+  if ((du == nullptr) != (dv == nullptr)) return fail(SH_ERR_ARGS, "u and v: both or neither");
+  return SH_OK;
+}
+
+// The (NW, K) of a large launch by its column slots, handed to f as a
+// BigCfg<NW, K, 12> tag.  Integer costs take with_big_cfg's table for a batch
+// that fills the chip: four columns per thread up to 2048 columns on 8 waves,
+// 16 waves beyond with three columns where they cover the instance (16 x 2 at
+// 2000 columns: 5 % faster up to 256 instances, equal at 1024; not taken).
+// Float costs stay on 8 waves with more columns per thread: every wave folds
+// the NW (value, key, row) slots of a step, and 16 of them cost more than the
+// columns spread over them save (2000 columns, 16 x 2 against 8 x 4: 25 %
+// slower, 2x at 1024 instances; 3000 columns, 8 x 6 against 16 x 3: 14 - 18 %
+// faster; 4096, 8 x 8 against 16 x 4: 3 - 10 %; DESIGN §7,
+// profiles/lsap_large.jsonl).
+template <typename F>
+int with_large_cfg(int nc, F &&f) {
+  if (nc <= 2048) return f(BigCfg<8, 4, 12>{});
+  if (nc <= 3072) return f(BigCfg<16, 3, 12>{});
+  return f(BigCfg<16, 4, 12>{});
+}
+
+template <typename F>
+int with_large_f64_cfg(int nc, F &&f) {
+  if (nc <= 2048) return f(BigCfg<8, 4, 12>{});
+  if (nc <= 3072) return f(BigCfg<8, 6, 12>{});
+  return f(BigCfg<8, 8, 12>{});
+}
+
+template <typename S>
+int launch_lsap_i64_large(const S *C, int nr, int n, int B, const int32_t *shape, int32_t *col, int64_t *cost,
+                          int64_t *du, int64_t *dv, unsigned flags, hipStream_t s) {
+  const int rc = check_large_solve(C, nr, n, B, col, du, dv);
+  if (rc) return rc;
+  if (B == 0) return SH_OK;
+  if (n <= SH_MAX_N)
+    return du ? launch_lsap_i64<S, false, true>(C, 0, 1, nr, n, B, shape, col, cost, flags, s, du, dv)
+              : launch_lsap_i64<S, false>(C, 0, 1, nr, n, B, shape, col, cost, flags, s);
+  return with_large_cfg(n, [&](auto cfg) {
+    using C_ = decltype(cfg);
+    // lsap_i64_kernel's carve-up: u, c4r, r4c, path, red (4 NW words), part (NW words)
+    const size_t lds = r16((size_t)nr * 8) + r16((size_t)nr * 2) + 2 * r16((size_t)n * 2) +
+                       r16((size_t)4 * C_::NW * 8) + r16((size_t)C_::NW * 8);
+    if (du)
+      hipLaunchKernelGGL((lsap_i64_kernel<C_::NW, C_::K, S, false, true, C_::FB, int64_t *, int64_t *>), dim3(B),
+                         dim3(C_::NW * WAVE), lds, s, C, (uint64_t)0, (int64_t)1, nr, n, shape, col, cost,
+                         (int32_t *)nullptr, flags, du, dv);
+    else
+      hipLaunchKernelGGL((lsap_i64_kernel<C_::NW, C_::K, S, false, true, C_::FB>), dim3(B), dim3(C_::NW * WAVE),
+                         lds, s, C, (uint64_t)0, (int64_t)1, nr, n, shape, col, cost, (int32_t *)nullptr, flags);
+    HIP_TRY(hipGetLastError());
+    return (int)SH_OK;
+  });
+}
+
+template <typename S>
+int launch_lsap_f64_large(const S *C, int nr, int n, int B, const int32_t *shape, int32_t *col, double *cost,
+                          double *du, double *dv, unsigned flags, hipStream_t s) {
+  const int rc = check_large_solve(C, nr, n, B, col, du, dv);
+  if (rc) return rc;
+  if ((flags & SH_FLAG_F64_MW) && (flags & SH_FLAG_F64_SW))
+    return fail(SH_ERR_ARGS, "SH_FLAG_F64_MW and SH_FLAG_F64_SW exclude each other");
+  if ((flags & SH_FLAG_F64_SW) && n > SH_MAX_N)
+    return fail(SH_ERR_ARGS, "SH_FLAG_F64_SW: no one-wave float kernel above 1024 columns");
+  if (B == 0) return SH_OK;
+  if (n <= SH_MAX_N)
+    return du ? launch_lsap_f64<S, true>(C, nr, n, B, shape, col, cost, flags, s, du, dv)
+              : launch_lsap_f64<S>(C, nr, n, B, shape, col, cost, flags, s);
+  return with_large_f64_cfg(n, [&](auto cfg) {
+    using C_ = decltype(cfg);
+    // lsap_f64_mw_kernel's carve-up: u, rv, rk (key and row: 8 bytes a slot), c4r, r4c, path
+    const size_t lds = r16((size_t)nr * 8) + r16((size_t)2 * C_::NW * 8) + r16((size_t)2 * C_::NW * 8) +
+                       r16((size_t)nr * 2) + 2 * r16((size_t)n * 2);
+    if (du)
+      hipLaunchKernelGGL((lsap_f64_mw_kernel<C_::NW, C_::K, S, C_::FB, double *, double *>), dim3(B),
+                         dim3(C_::NW * WAVE), lds, s, C, nr, n, shape, col, cost, du, dv);
+    else
+      hipLaunchKernelGGL((lsap_f64_mw_kernel<C_::NW, C_::K, S, C_::FB>), dim3(B), dim3(C_::NW * WAVE), lds, s, C,
+                         nr, n, shape, col, cost);
+    HIP_TRY(hipGetLastError());
+    return (int)SH_OK;
+  });
+}
+
+template <typename S, typename T>
+int launch_lsap_check_large(const S *C, int nr, int n, int B, const int32_t *shape, const int32_t *col,
+                            const T *u, const T *v, T *slack, int32_t *flg, hipStream_t s) {
+  const int rc = check_lsap_args(nr, n, B, col, SH_MAX_N_LARGE);
+  if (rc) return rc;
+  if (n <= SH_MAX_N) return launch_lsap_check<S, T>(C, nr, n, B, shape, col, u, v, slack, flg, s);
+  return launch_lsap_check<S, T, SH_MAX_N_LARGE>(C, nr, n, B, shape, col, u, v, slack, flg, s);
+}
 }  // namespace
 
 extern "C" {
+
+#define SH_LARGE_ENTRIES(SUF, CT, KT, T, SOLVE)                                                                 \
+  int lsap_solve_large_##SUF(const CT *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,      \
+                             T *d_cost, T *d_u, T *d_v, unsigned flags, void *stream) {                         \
+    return SOLVE((const KT *)d_C, nr, nc, B, d_shape, d_col, d_cost, d_u, d_v, flags, (hipStream_t)stream);     \
+  }                                                                                                             \
+  int lsap_check_duals_large_##SUF(const CT *d_C, int nr, int nc, int B, const int32_t *d_shape,                \
+                                   const int32_t *d_col, const T *d_u, const T *d_v, T *d_slack,                \
+                                   int32_t *d_flags, void *stream) {                                            \
+    return launch_lsap_check_large((const KT *)d_C, nr, nc, B, d_shape, d_col, d_u, d_v, d_slack, d_flags,      \
+                                   (hipStream_t)stream);                                                        \
+  }
+SH_LARGE_ENTRIES(i64, int64_t, int64_t, int64_t, launch_lsap_i64_large)
+SH_LARGE_ENTRIES(i32, int32_t, int32_t, int64_t, launch_lsap_i64_large)
+SH_LARGE_ENTRIES(f64, double, double, double, launch_lsap_f64_large)
+SH_LARGE_ENTRIES(f32, float, float, double, launch_lsap_f64_large)
+SH_LARGE_ENTRIES(f16, uint16_t, _Float16, double, launch_lsap_f64_large)
+SH_LARGE_ENTRIES(bf16, uint16_t, sh_bf16, double, launch_lsap_f64_large)
+#undef SH_LARGE_ENTRIES
 
 int lsap_solve_batched_i64(const int64_t *d_C, int n, int B, int32_t *d_col, int64_t *d_cost,
                            unsigned flags, void *stream) {

@@ -5288,6 +5288,18 @@ struct GlobalLoaderF64 {
 // every wave reaches after its reads of step t - 1.  The pair carries the
 // winning column's own spc, so minVal has the sign of zero scipy's has.
 //
+// FB is the width of the key's position and column fields (n <= 2^FB).  With
+// FB = 10 the key is sap_solve's word, row4col included (1 + 10 + 10 + 10
+// bits).  Wider fields (FB = 12, n <= 4096) leave no room for the row: the key
+// is class, position, column (1 + 12 + 12 bits) and the row rides beside it --
+// the lane that owns the wave's winner writes row4col of that column (one of
+// its K, found by the key's column field) next to the key (S.rk is then
+// [2 * NW][2]: key, row) and every wave reads the pair with one 8-byte load in
+// the fold it does anyway.  That leaves the wave fold as it is and adds no LDS
+// round trip to the step's dependent chain (a 64-bit key would widen every DPP
+// level of the wave fold, a read of S.r4c[jstar] after the fold would put one
+// more LDS round trip in front of the next row's loads).
+//
 // The step loop is bounded by construction: each step removes one column from
 // `remaining`, and an empty `remaining` ends the instance as infeasible (only
 // input the caller should have rejected, NaN or -inf, gets there).
@@ -5300,7 +5312,7 @@ struct SolveLdsF64 {
   int16_t *r4c;    // [n]   row4col
   int16_t *path;   // [n]   path dump of the visited columns
   double *rv;      // [2 * NW]  the waves' step minima, by step parity
-  uint32_t *rk;    // [2 * NW]  and their tie keys
+  uint32_t *rk;    // [2 * NW]  and their tie keys (FB > 10: [2 * NW][2], key and row4col)
 };
 
 template <int CTRL, int ROWMASK>
@@ -5322,9 +5334,14 @@ __device__ __forceinline__ double wave_min_f64_dpp(double x) {
   return __longlong_as_double((long long)readlane_u64((uint64_t)__double_as_longlong(x), 63));
 }
 
-template <int NW, int K, bool DUALS = false, typename Loader>
+template <int NW, int K, bool DUALS = false, int FB = 10, typename Loader>
 __device__ __forceinline__ int sap_solve_mw_f64(const int nr, const int n, const Loader &ld,
                                                 const SolveLdsF64 &S) {
+  static_assert(FB >= 10 && FB <= 15, "1 + 2 FB key bits in 32, rows in int16");
+  constexpr bool ROWKEY = FB == 10;  // row4col inside the key (sap_solve's word)
+  constexpr int PSH = ROWKEY ? 2 * FB : FB;  // the position field's shift; the class bit sits above it
+  constexpr int FM = (1 << FB) - 1;
+  constexpr int RK = ROWKEY ? 1 : 2;  // words of a wave's slot in S.rk
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const double INF = VT<double>::inf();
   double spc[K], v[K];
@@ -5364,9 +5381,9 @@ __device__ __forceinline__ int sap_solve_mw_f64(const int nr, const int n, const
           }
           const uint32_t sec =
               (r4c[k] < 0)
-                  ? (((uint32_t)(1023 - pos[k]) << 20) | (uint32_t)j)
-                  : ((1u << 30) | ((uint32_t)pos[k] << 20) |
-                     ((uint32_t)r4c[k] << 10) | (uint32_t)j);
+                  ? (((uint32_t)(FM - pos[k]) << PSH) | (uint32_t)j)
+                  : ((1u << (PSH + FB)) | ((uint32_t)pos[k] << PSH) |
+                     (ROWKEY ? ((uint32_t)r4c[k] << FB) : 0u) | (uint32_t)j);
           if (spc[k] < best || (spc[k] == best && sec < bsec)) {
             best = spc[k];
             bsec = sec;
@@ -5379,18 +5396,37 @@ __device__ __forceinline__ int sap_solve_mw_f64(const int nr, const int n, const
       const uint32_t wk = wave_min_u32_dpp((best == wm) ? bsec : SEC_NONE);
       if (best == wm && bsec == wk && (wk != SEC_NONE || lane == 0)) {
         S.rv[par * NW + w] = best;
-        S.rk[par * NW + w] = wk;
+        S.rk[RK * (par * NW + w)] = wk;
+        if constexpr (!ROWKEY) {  // row4col of the column wk names, beside the key
+          int brow = -1;
+#pragma unroll
+          for (int k = 0; k < K; ++k) brow = (mw_col<NW, K>(w, k, lane) == (int)(wk & (uint32_t)FM)) ? r4c[k] : brow;
+          S.rk[RK * (par * NW + w) + 1] = (uint32_t)brow;
+        }
       }
       __syncthreads();
+      // (RK words a slot: the key, and beside it the row unless the key holds
+      // it; that row folds into i -- row i is done with, and the FB = 10
+      // instantiations keep the locals, and so the code, they always had)
       double m = S.rv[par * NW];
-      uint32_t s = S.rk[par * NW];
+      uint32_t s = S.rk[RK * (par * NW)];
+      if constexpr (!ROWKEY) i = (int)S.rk[RK * (par * NW) + 1];
 #pragma unroll
       for (int q = 1; q < NW; ++q) {
         const double mq = S.rv[par * NW + q];
-        const uint32_t sq = S.rk[par * NW + q];
-        if (mq < m || (mq == m && sq < s)) {
-          m = mq;
-          s = sq;
+        const uint32_t sq = S.rk[RK * (par * NW + q)];
+        if constexpr (ROWKEY) {
+          if (mq < m || (mq == m && sq < s)) {
+            m = mq;
+            s = sq;
+          }
+        } else {
+          const int rq = (int)S.rk[RK * (par * NW + q) + 1];
+          if (mq < m || (mq == m && sq < s)) {
+            m = mq;
+            s = sq;
+            i = rq;
+          }
         }
       }
       par ^= 1;
@@ -5400,10 +5436,10 @@ __device__ __forceinline__ int sap_solve_mw_f64(const int nr, const int n, const
       // minVal = spc of the chosen column (scipy: lowest = spc[j]), sign of
       // zero included: the pair carried that column's own spc
       minVal = m;
-      const int jstar = (int)(s & 1023u);
-      const bool assigned = (s >> 30) & 1u;
-      const int pfield = (int)((s >> 20) & 1023u);
-      const int prem = assigned ? pfield : 1023 - pfield;
+      const int jstar = (int)(s & (uint32_t)FM);
+      const bool assigned = (s >> (PSH + FB)) & 1u;
+      const int pfield = (int)((s >> PSH) & (uint32_t)FM);
+      const int prem = assigned ? pfield : FM - pfield;
       const int last = nrem - 1;
 #pragma unroll
       for (int k = 0; k < K; ++k) {
@@ -5417,7 +5453,10 @@ __device__ __forceinline__ int sap_solve_mw_f64(const int nr, const int n, const
         sink = jstar;
         break;
       }
-      i = (int)((s >> 10) & 1023u);
+      if constexpr (ROWKEY)
+        i = (int)((s >> FB) & (uint32_t)FM);
+      else
+        i = __builtin_amdgcn_readfirstlane(i);
     }
     if (sink < 0) return -1;  // `remaining` ran empty
     // Dual update (scipy: u[cur] += minVal; u[i] += minVal - spc[col4row[i]]
@@ -5516,7 +5555,9 @@ __device__ __forceinline__ void duals_store_f64(double *du, double *dv, const do
   duals_fill<double, WG>(du, dv, b, NR, NC, nr, n, 0.0);
 }
 
-template <int NW, int K, typename S, bool HASH, bool RECT, typename... DU>
+// FB: the width of the packed key's position and row / column fields (see
+// sap_solve_mw): 10 up to 1024 columns, 12 up to 4096.
+template <int NW, int K, typename S, bool HASH, bool RECT, int FB = 10, typename... DU>
 __global__ __launch_bounds__(NW * WAVE) void lsap_i64_kernel(const S *C, uint64_t seed, int64_t mod,
                                                              int NR_, int NC, const int32_t *shape,
                                                              int32_t *col, int64_t *cost,
@@ -5557,15 +5598,20 @@ __global__ __launch_bounds__(NW * WAVE) void lsap_i64_kernel(const S *C, uint64_
   if constexpr (DUALS) {
     using LD = WithDuals<GlobalLoader<NW, K, S>, int64_t>;
     const LD ld{{C + base, n, NC, nr}, duals_v(duals...) + (size_t)b * NC};
-    sap_solve_mw<NW, K, LD, 10, RECT, true>(n, ld, Sl, steps, fallbacks, exact);
+    sap_solve_mw<NW, K, LD, FB, RECT, true>(n, ld, Sl, steps, fallbacks, exact);
     for (int i = tid; i < nr; i += NW * WAVE) duals_u(duals...)[(size_t)b * NR + i] = Sl.u[i];
     duals_fill<int64_t, NW * WAVE>(duals_u(duals...), duals_v(duals...), b, NR, NC, nr, n, 0);
   } else if constexpr (HASH) {
     const HashLoader<NW, K> ld{seed, mod, (uint64_t)b, n, nr};
-    sap_solve_mw<NW, K, HashLoader<NW, K>, 10, RECT>(n, ld, Sl, steps, fallbacks, exact);
+    sap_solve_mw<NW, K, HashLoader<NW, K>, FB, RECT>(n, ld, Sl, steps, fallbacks, exact);
   } else {
     const GlobalLoader<NW, K, S> ld{C + base, n, NC, nr};
-    sap_solve_mw<NW, K, GlobalLoader<NW, K, S>, 10, RECT>(n, ld, Sl, steps, fallbacks, exact);
+    // (spelled out for FB = 10: tests/test_lsap_adversarial_cpu.py pins this line,
+    // the key width that the window edges of tests/lsap_families.py belong to)
+    if constexpr (FB == 10)
+      sap_solve_mw<NW, K, GlobalLoader<NW, K, S>, 10, RECT>(n, ld, Sl, steps, fallbacks, exact);
+    else
+      sap_solve_mw<NW, K, GlobalLoader<NW, K, S>, FB, RECT>(n, ld, Sl, steps, fallbacks, exact);
   }
   int64_t acc = 0;
   for (int i = tid; i < NR; i += NW * WAVE) {
@@ -5636,7 +5682,8 @@ __global__ __launch_bounds__(WAVE) void lsap_f64_kernel(const S *C, int NR, int 
 
 // The same instance on NW waves (sap_solve_mw_f64).  Wave 0 sums the chosen
 // cost in lsap_f64_kernel's order, so both designs return the same bits.
-template <int NW, int K, typename S, typename... DU>
+// FB: sap_solve_mw_f64's key field width, 10 up to 1024 columns, 12 up to 4096.
+template <int NW, int K, typename S, int FB = 10, typename... DU>
 __global__ __launch_bounds__(NW * WAVE) void lsap_f64_mw_kernel(const S *C, int NR, int NC,
                                                                 const int32_t *shape, int32_t *col,
                                                                 double *cost, DU... duals) {
@@ -5655,7 +5702,7 @@ __global__ __launch_bounds__(NW * WAVE) void lsap_f64_mw_kernel(const S *C, int 
   SolveLdsF64 Sl;
   Sl.u = (double *)(smem + off);      off += r16((size_t)nr * 8);
   Sl.rv = (double *)(smem + off);     off += r16((size_t)2 * NW * 8);
-  Sl.rk = (uint32_t *)(smem + off);   off += r16((size_t)2 * NW * 4);
+  Sl.rk = (uint32_t *)(smem + off);   off += r16((size_t)2 * NW * (FB > 10 ? 8 : 4));
   Sl.c4r = (int16_t *)(smem + off);   off += r16((size_t)nr * 2);
   Sl.r4c = (int16_t *)(smem + off);   off += r16((size_t)n * 2);
   Sl.path = (int16_t *)(smem + off);
@@ -5672,7 +5719,7 @@ __global__ __launch_bounds__(NW * WAVE) void lsap_f64_mw_kernel(const S *C, int 
   using GL = GlobalLoaderF64<NW, K, S>;
   std::conditional_t<DUALS, WithDuals<GL, double>, GL> ld{GL{C + base, n, NC}};
   if constexpr (DUALS) ld.dv = duals_v(duals...) + (size_t)b * NC;
-  const int st = sap_solve_mw_f64<NW, K, DUALS>(nr, n, ld, Sl);
+  const int st = sap_solve_mw_f64<NW, K, DUALS, FB>(nr, n, ld, Sl);
   __syncthreads();
   if constexpr (DUALS)
     duals_store_f64<WG>(duals_u(duals...), duals_v(duals...), Sl.u, st, b, NR, NC, nr, n);
@@ -5739,12 +5786,15 @@ __device__ __forceinline__ T cert_max(T m, T y) {  // (a NaN sticks)
   return (y > m || y != y) ? y : m;
 }
 
-template <typename S, typename T>
+// NCAP: the column capacity (NC <= NCAP): the size of the column bitmap here
+// and of a thread's v registers in lsap_slack_kernel.
+template <typename S, typename T, int NCAP = SH_MAX_N>
 __global__ __launch_bounds__(CERT_WG) void lsap_cert_kernel(const S *C, int NR, int NC, const int32_t *shape,
                                                             const int32_t *col, const T *u, const T *v,
                                                             T *slack, int32_t *flags) {
   constexpr bool INT = std::is_same<T, int64_t>::value;
-  __shared__ uint32_t bits[SH_MAX_N / 32];
+  static_assert(NCAP / 32 <= CERT_WG, "one thread clears one bitmap word");
+  __shared__ uint32_t bits[NCAP / 32];
   __shared__ T part[4][CERT_WG / WAVE];
   __shared__ int s_flags, s_none;
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -5761,7 +5811,7 @@ __global__ __launch_bounds__(CERT_WG) void lsap_cert_kernel(const S *C, int NR, 
       return;
     }
   }
-  if (tid < SH_MAX_N / 32) bits[tid] = 0;
+  if (tid < NCAP / 32) bits[tid] = 0;
   if (tid == 0) s_flags = s_none = 0;
   __syncthreads();
   int f = 0, none = 0;
@@ -5848,12 +5898,12 @@ struct alignas(sizeof(S) * VEC) CertPack {
   S e[VEC];
 };
 
-template <typename S, typename T, int VEC>
+template <typename S, typename T, int VEC, int NCAP = SH_MAX_N>
 __global__ __launch_bounds__(CERT_WG) void lsap_slack_kernel(const S *C, int NR, int NC, const int32_t *shape,
                                                              const T *u, const T *v, T *slack,
                                                              int32_t *flags, int rows_per) {
   // thread (ty, tx): columns (tx + TX q) VEC + e, rows r0 + ty, r0 + ty + TY, ..
-  constexpr int QMAX = (SH_MAX_N + CERT_WG * VEC - 1) / (CERT_WG * VEC);
+  constexpr int QMAX = (NCAP + CERT_WG * VEC - 1) / (CERT_WG * VEC);
   __shared__ uint64_t part[CERT_WG / WAVE];
   const int b = blockIdx.x, tid = threadIdx.x;
   int nr, nc;

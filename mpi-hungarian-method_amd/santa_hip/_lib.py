@@ -67,6 +67,7 @@ SH_DESIGN_NAMES = {0: "santa_sp_kernel (1-wave sparse LDS tile)", 1: "santa_bloc
                       "32-bit lattice keys)"}
 SH_MAX_N = 1024
 SH_MAX_N_SANTA = 4096
+SH_MAX_N_LARGE = 4096  # the lsap_solve_large_ / lsap_check_duals_large_ entries
 
 _ERRF_TEXT = {SH_ERRF_ROWS: "a block's child ids out of [0, nc)",
               SH_ERRF_INFEASIBLE: "an infeasible solve",
@@ -134,6 +135,9 @@ SIGNATURES = {
     "lsap_check_duals_bf16": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "sh_gen_synthetic": (_I, [_U64, _I, _I, _I, _I, _I, _P, _P, _P]),
 }
+for _suf in ("i64", "i32", "f64", "f32", "f16", "bf16"):  # the duals / check_duals argument lists
+    SIGNATURES["lsap_solve_large_" + _suf] = SIGNATURES["lsap_solve_batched_duals_" + _suf]
+    SIGNATURES["lsap_check_duals_large_" + _suf] = SIGNATURES["lsap_check_duals_" + _suf]
 
 
 class RoundExt(ctypes.Structure):

@@ -13,6 +13,9 @@ their own width, widened in registers (exact) and solved as float64.
 solve_batched(duals=True) and linear_sum_assignment_duals also return the dual
 variables (u, v) the solve ends with, and check_duals certifies (col, u, v)
 against the costs on the device: for integer costs flags == 0 proves optimality.
+solve_batched_large, check_duals_large and linear_sum_assignment_large are the
+same three up to SH_MAX_N_LARGE = 4096 rows or columns (the reference's own
+block sizes, 2000 and 3000), through the lsap_*_large_ entries.
 """
 from __future__ import annotations
 
@@ -30,6 +33,7 @@ def _p(t):
 
 
 INT64_COST_LIMIT = 1 << 50  # |C| bound that keeps every SAP value < 2^62 (n <= 1024)
+INT64_COST_LIMIT_LARGE = 1 << 48  # the same factor 4n at n <= 4096
 EXACT_INT_LIMIT = 1 << 53   # float64 holds every integer below this exactly
 # floating-point cost dtypes of solve_batched and their C-ABI entries
 FLOAT_ENTRIES = {torch.float64: "lsap_solve_batched_rect_f64", torch.float32: "lsap_solve_batched_rect_f32",
@@ -102,6 +106,13 @@ def tall_result(col_t):
     return col_t[order], order.astype(np.int64)
 
 
+def int64_cost_limit(n: int) -> int:
+    """The bound |C| < limit of int64 costs for instances of max(NR, NC) = n:
+    every value the shortest-augmenting-path run forms stays below 2^62, a
+    factor 4n above the costs."""
+    return INT64_COST_LIMIT if n <= _lib.SH_MAX_N else INT64_COST_LIMIT_LARGE
+
+
 def exact_int64_route(C: np.ndarray) -> bool:
     """Whether an integer matrix is solved in exact int64: scipy solves in
     float64, and the int64 solve makes scipy's decisions only while every
@@ -117,12 +128,39 @@ def exact_int64_route(C: np.ndarray) -> bool:
 
 
 # ---------------------------------------------------------------------------
-def _solve_wide_duals(C: torch.Tensor, with_cost: bool, fl: int, shape_dev):
-    """_solve_wide through the lsap_solve_batched_duals_ entries: (col, cost, u, v)."""
+def _check_int64_range(C: torch.Tensor):
+    """ValueError unless an int64 batch is within int64_cost_limit of its size."""
+    limit = int64_cost_limit(max(C.shape[1:]))
+    # (max / -min as Python ints: abs() wraps at INT64_MIN)
+    if C.dtype == torch.int64 and C.numel() and max(int(C.max()), -int(C.min())) >= limit:
+        raise ValueError(f"int64 costs must satisfy |C| < 2**{limit.bit_length() - 1}; pass float64 instead")
+
+
+def _solve_wide_large(C: torch.Tensor, with_cost: bool, fl: int, shape_dev, duals: bool):
+    """_solve_wide / _solve_wide_duals through the lsap_solve_large_ entries
+    (u and v nullable): (col, cost, u, v), u and v None without duals."""
     B, nr, nc = C.shape
     dev = C.device
-    if C.dtype == torch.int64 and C.numel() and max(int(C.max()), -int(C.min())) >= INT64_COST_LIMIT:
-        raise ValueError("int64 costs must satisfy |C| < 2**50; pass float64 instead")
+    _check_int64_range(C)
+    ddt = torch.float64 if C.dtype in FLOAT_ENTRIES else torch.int64
+    col = torch.empty((B, nr), dtype=torch.int32, device=dev)
+    cost = torch.empty(B, dtype=ddt, device=dev) if with_cost else None
+    u = torch.empty((B, nr), dtype=ddt, device=dev) if duals else None
+    v = torch.empty((B, nc), dtype=ddt, device=dev) if duals else None
+    entry = getattr(_lib.lib(), "lsap_solve_large_" + DTYPE_SUFFIX[C.dtype])
+    rc = entry(_p(C), nr, nc, B, _p(shape_dev), _p(col), _p(cost), _p(u), _p(v), fl,
+               current_stream_handle(dev))
+    _lib.check(rc, "lsap_solve_large")
+    return col, cost, u, v
+
+
+def _solve_wide_duals(C: torch.Tensor, with_cost: bool, fl: int, shape_dev, large: bool = False):
+    """_solve_wide through the lsap_solve_batched_duals_ entries: (col, cost, u, v)."""
+    if large:
+        return _solve_wide_large(C, with_cost, fl, shape_dev, True)
+    B, nr, nc = C.shape
+    dev = C.device
+    _check_int64_range(C)
     ddt = torch.float64 if C.dtype in FLOAT_ENTRIES else torch.int64
     col = torch.empty((B, nr), dtype=torch.int32, device=dev)
     cost = torch.empty(B, dtype=ddt, device=dev) if with_cost else None
@@ -135,18 +173,18 @@ def _solve_wide_duals(C: torch.Tensor, with_cost: bool, fl: int, shape_dev):
     return col, cost, u, v
 
 
-def _solve_wide(C: torch.Tensor, with_cost: bool, fl: int, shape_dev):
+def _solve_wide(C: torch.Tensor, with_cost: bool, fl: int, shape_dev, large: bool = False):
     """C contiguous [B, nr, nc], 1 <= nr <= nc (the square C-ABI entries are
     the rect ones with nr == nc and no shapes)."""
+    if large:
+        return _solve_wide_large(C, with_cost, fl, shape_dev, False)[:2]
     B, nr, nc = C.shape
     dev = C.device
     col = torch.empty((B, nr), dtype=torch.int32, device=dev)
     s = current_stream_handle(dev)
     L = _lib.lib()
     if C.dtype == torch.int64:
-        # (max / -min as Python ints: abs() wraps at INT64_MIN)
-        if C.numel() and max(int(C.max()), -int(C.min())) >= INT64_COST_LIMIT:
-            raise ValueError("int64 costs must satisfy |C| < 2**50; pass float64 instead")
+        _check_int64_range(C)
         cost = torch.empty(B, dtype=torch.int64, device=dev) if with_cost else None
         rc = L.lsap_solve_batched_rect_i64(_p(C), nr, nc, B, _p(shape_dev), _p(col), _p(cost), fl, s)
     elif C.dtype == torch.int32:
@@ -192,12 +230,29 @@ def solve_batched(C: torch.Tensor, with_cost: bool = True, flags: int = 0, shape
     device.  maximize negates the matrix (and the cost back).  int64 costs
     must satisfy |C| < 2^50 over the whole padded tensor (checked on the
     device)."""
+    return _solve_batched(C, with_cost, flags, shapes, maximize, duals, False)
+
+
+def solve_batched_large(C: torch.Tensor, with_cost: bool = True, flags: int = 0, shapes=None,
+                        maximize: bool = False, duals: bool = False):
+    """solve_batched up to SH_MAX_N_LARGE = 4096 rows or columns, through the
+    lsap_solve_large_ entries: the same arguments, results and semantics.  Up
+    to SH_MAX_N it runs solve_batched's kernels and returns its bits.  int64
+    costs of a batch with max(NR, NC) > 1024 must satisfy |C| < 2^48
+    (int64_cost_limit); flags may not force the one-wave float kernel
+    (SH_FLAG_F64_SW) above 1024 columns."""
+    return _solve_batched(C, with_cost, flags, shapes, maximize, duals, True)
+
+
+def _solve_batched(C, with_cost, flags, shapes, maximize, duals, large):
+    """solve_batched (limit SH_MAX_N) and solve_batched_large (SH_MAX_N_LARGE)."""
     require_gpu()
     if C.dim() != 3:
         raise ValueError("expected [B, NR, NC]")
     B, NR, NC = C.shape
-    if max(NR, NC) > _lib.SH_MAX_N:
-        raise ValueError(f"max(NR, NC) = {max(NR, NC)} > {_lib.SH_MAX_N}")
+    limit = _lib.SH_MAX_N_LARGE if large else _lib.SH_MAX_N
+    if max(NR, NC) > limit:
+        raise ValueError(f"max(NR, NC) = {max(NR, NC)} > {limit}")
     if C.dtype not in (torch.int64, torch.int32) and C.dtype not in FLOAT_ENTRIES:
         raise TypeError(f"unsupported dtype {C.dtype}")
     dev = C.device
@@ -219,18 +274,18 @@ def solve_batched(C: torch.Tensor, with_cost: bool = True, flags: int = 0, shape
     fl = _lib.SH_COMPAT_TIEBREAK | flags
     if duals:
         if NR > NC:  # the transposed solve's row duals belong to the columns
-            col_t, cost, v, u = _solve_wide_duals(C.transpose(1, 2).contiguous(), with_cost, fl, None)
+            col_t, cost, v, u = _solve_wide_duals(C.transpose(1, 2).contiguous(), with_cost, fl, None, large)
             col = invert_tall(col_t, NR)
         else:
-            col, cost, u, v = _solve_wide_duals(C.contiguous(), with_cost, fl, shape_dev)
+            col, cost, u, v = _solve_wide_duals(C.contiguous(), with_cost, fl, shape_dev, large)
         if maximize:
             cost, u, v = (-cost if cost is not None else None), -u, -v
         return col, cost, u, v
     if NR > NC:
-        col_t, cost = _solve_wide(C.transpose(1, 2).contiguous(), with_cost, fl, None)
+        col_t, cost = _solve_wide(C.transpose(1, 2).contiguous(), with_cost, fl, None, large)
         col = invert_tall(col_t, NR)
     else:
-        col, cost = _solve_wide(C.contiguous(), with_cost, fl, shape_dev)
+        col, cost = _solve_wide(C.contiguous(), with_cost, fl, shape_dev, large)
     if maximize and cost is not None:
         cost = -cost
     return col, cost
@@ -271,12 +326,25 @@ def check_duals(C: torch.Tensor, col: torch.Tensor, u: torch.Tensor, v: torch.Te
     maximize certifies the negated problem (-C, -u, -v), so the same signs
     hold.  A tall batch is checked as its transpose (a contiguous copy) with
     the duals swapped and col inverted."""
+    return _check_duals(C, col, u, v, shapes, maximize, False)
+
+
+def check_duals_large(C: torch.Tensor, col: torch.Tensor, u: torch.Tensor, v: torch.Tensor, shapes=None,
+                      maximize: bool = False):
+    """check_duals up to SH_MAX_N_LARGE = 4096 rows or columns, through the
+    lsap_check_duals_large_ entries: the same arguments, results and meaning."""
+    return _check_duals(C, col, u, v, shapes, maximize, True)
+
+
+def _check_duals(C, col, u, v, shapes, maximize, large):
+    """check_duals (limit SH_MAX_N) and check_duals_large (SH_MAX_N_LARGE)."""
     require_gpu()
     if C.dim() != 3:
         raise ValueError("expected [B, NR, NC]")
     B, NR, NC = C.shape
-    if max(NR, NC) > _lib.SH_MAX_N:
-        raise ValueError(f"max(NR, NC) = {max(NR, NC)} > {_lib.SH_MAX_N}")
+    limit = _lib.SH_MAX_N_LARGE if large else _lib.SH_MAX_N
+    if max(NR, NC) > limit:
+        raise ValueError(f"max(NR, NC) = {max(NR, NC)} > {limit}")
     if C.dtype not in DTYPE_SUFFIX:
         raise TypeError(f"unsupported dtype {C.dtype}")
     ddt = torch.float64 if C.dtype in FLOAT_ENTRIES else torch.int64
@@ -304,7 +372,7 @@ def check_duals(C: torch.Tensor, col: torch.Tensor, u: torch.Tensor, v: torch.Te
         col, bad = invert_col(col, NC)
         NR, NC = NC, NR
     C, col, u, v = C.contiguous(), col.contiguous(), u.contiguous(), v.contiguous()
-    entry = getattr(_lib.lib(), "lsap_check_duals_" + DTYPE_SUFFIX[C.dtype])
+    entry = getattr(_lib.lib(), ("lsap_check_duals_large_" if large else "lsap_check_duals_") + DTYPE_SUFFIX[C.dtype])
     rc = entry(_p(C), NR, NC, B, _p(shape_dev), _p(col), _p(u), _p(v), _p(slack), _p(flags),
                current_stream_handle(dev))
     _lib.check(rc, "lsap_check_duals")
@@ -313,7 +381,7 @@ def check_duals(C: torch.Tensor, col: torch.Tensor, u: torch.Tensor, v: torch.Te
     return slack[:, 0], slack[:, 1], slack[:, 2], flags
 
 
-def _route(cost_matrix, maximize: bool, dev):
+def _route(cost_matrix, maximize: bool, dev, limit: int = _lib.SH_MAX_N):
     """linear_sum_assignment's host side: the wide device matrix to minimise
     (int64 on the exact route, float64 otherwise) and whether the input was
     tall; None for an empty matrix."""
@@ -323,8 +391,8 @@ def _route(cost_matrix, maximize: bool, dev):
     nr, nc = C.shape
     if nr == 0 or nc == 0:
         return None, False
-    if max(nr, nc) > _lib.SH_MAX_N:
-        raise ValueError(f"max(nr, nc) = {max(nr, nc)} > {_lib.SH_MAX_N}")
+    if max(nr, nc) > limit:
+        raise ValueError(f"max(nr, nc) = {max(nr, nc)} > {limit}")
     if C.dtype == np.bool_:
         C = C.astype(np.int64)
     if np.issubdtype(C.dtype, np.unsignedinteger):
@@ -349,28 +417,40 @@ def _route(cost_matrix, maximize: bool, dev):
     return Ct, tall
 
 
+def _lsa(cost_matrix, maximize, device, duals, solve, limit):
+    """The front ends' body: `solve` is solve_batched or solve_batched_large
+    (looked up by the caller at call time), `limit` its size limit."""
+    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    Ct, tall = _route(cost_matrix, maximize, dev, limit)
+    if Ct is None:
+        z = np.zeros(0, dtype=np.int64)
+        if not duals:
+            return z, z.copy()
+        nr, nc = np.asarray(cost_matrix).shape
+        return z, z.copy(), np.zeros(nr, dtype=np.int64), np.zeros(nc, dtype=np.int64)
+    if not duals:
+        col, _ = solve(Ct.unsqueeze(0), with_cost=False)
+    else:
+        col, _, u, v = solve(Ct.unsqueeze(0), with_cost=False, duals=True)
+    col = col[0].cpu().numpy().astype(np.int64)
+    if (col < 0).any():
+        raise ValueError("cost matrix is infeasible")
+    res = tall_result(col) if tall else (np.arange(col.size, dtype=np.int64), col)
+    if not duals:
+        return res
+    u, v = u[0].cpu().numpy(), v[0].cpu().numpy()
+    if maximize:
+        u, v = -u, -v
+    return res + ((v, u) if tall else (u, v))
+
+
 def linear_sum_assignment_duals(cost_matrix, maximize: bool = False, device: int | str = 0):
     """linear_sum_assignment that also returns the dual variables:
     (row_ind, col_ind, u [nr], v [nc]), u and v numpy arrays, int64 on the
     exact integer route and float64 on the float64 route (the routing is
     linear_sum_assignment's).  u[i] + v[j] <= C[i, j] with equality on the
     returned pairs (>= with maximize), in the sense of solve_batched."""
-    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-    Ct, tall = _route(cost_matrix, maximize, dev)
-    if Ct is None:
-        nr, nc = np.asarray(cost_matrix).shape
-        z = np.zeros(0, dtype=np.int64)
-        return z, z.copy(), np.zeros(nr, dtype=np.int64), np.zeros(nc, dtype=np.int64)
-    col, _, u, v = solve_batched(Ct.unsqueeze(0), with_cost=False, duals=True)
-    col = col[0].cpu().numpy().astype(np.int64)
-    if (col < 0).any():
-        raise ValueError("cost matrix is infeasible")
-    u, v = u[0].cpu().numpy(), v[0].cpu().numpy()
-    if maximize:
-        u, v = -u, -v
-    if tall:
-        return tall_result(col) + (v, u)
-    return np.arange(col.size, dtype=np.int64), col, u, v
+    return _lsa(cost_matrix, maximize, device, True, solve_batched, _lib.SH_MAX_N)
 
 
 def linear_sum_assignment(cost_matrix, maximize: bool = False, device: int | str = 0):
@@ -382,14 +462,12 @@ def linear_sum_assignment(cost_matrix, maximize: bool = False, device: int | str
     int64 (where scipy's float64 arithmetic is exact too); anything else in
     float64 with scipy's operation order, so the permutation is scipy's
     either way."""
-    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-    Ct, tall = _route(cost_matrix, maximize, dev)
-    if Ct is None:
-        return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
-    col, _ = solve_batched(Ct.unsqueeze(0), with_cost=False)
-    col = col[0].cpu().numpy().astype(np.int64)
-    if (col < 0).any():
-        raise ValueError("cost matrix is infeasible")
-    if tall:
-        return tall_result(col)
-    return np.arange(col.size, dtype=np.int64), col
+    return _lsa(cost_matrix, maximize, device, False, solve_batched, _lib.SH_MAX_N)
+
+
+def linear_sum_assignment_large(cost_matrix, maximize: bool = False, device: int | str = 0,
+                                duals: bool = False):
+    """linear_sum_assignment (or, with duals=True, linear_sum_assignment_duals)
+    for any shape up to SH_MAX_N_LARGE = 4096 on the longer side: the same
+    routing, results and errors, solved by solve_batched_large."""
+    return _lsa(cost_matrix, maximize, device, duals, solve_batched_large, _lib.SH_MAX_N_LARGE)
