@@ -26,6 +26,7 @@
 #ifndef SANTA_HIP_H
 #define SANTA_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -48,7 +49,10 @@ extern "C" {
 /* Test/profiling flags (same results, different code path or phases):     */
 #define SH_FLAG_EXACT_ARGMIN 2u /* always use the two-pass exact argmin    */
 #define SH_FLAG_BUILD_ONLY 4u   /* sh_solve_blocks: build the cost tiles and
-                                   apply the identity (phase timing only)  */
+                                   apply the identity (phase timing only);
+                                   lsap_solve_csr_*: run the pass over the
+                                   CSR that fills d_work and stop, the
+                                   outputs untouched (phase timing only)   */
 #define SH_FLAG_LDS_TILE 8u     /* sh_solve_blocks, singles n <= 256:      */
 #define SH_FLAG_VT_TILE 32u     /* alternative kernel designs (4-wave LDS
                                    tile / 4-wave register tile) kept for A/B
@@ -537,6 +541,59 @@ int lsap_check_duals_large_f16(const uint16_t *d_C, int nr, int nc, int B, const
 int lsap_check_duals_large_bf16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
                                const int32_t *d_col, const double *d_u, const double *d_v,
                                double *d_slack, int32_t *d_flags, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * The batched float solver on sparse (CSR) costs, a missing entry being a
+ * forbidden pair: a sparse instance is solved exactly as the dense float
+ * solver solves its densification, the nr x nc float64 matrix that holds each
+ * stored value (widened) and +inf everywhere else.  So d_col is scipy's
+ * linear_sum_assignment col_ind on that matrix, ties included; d_cost the sum
+ * of the chosen stored values in the dense kernels' fixed order (the dense
+ * entries' bits); d_u and d_v the bits of scipy's own float64 run with the
+ * signs and equalities of the _duals_ entries; an instance without a perfect
+ * matching of its rows (an empty row, two rows whose only column is shared)
+ * gets -1 in every row, cost 0 and NaN duals in its live slots.  Every stored
+ * entry is an edge whatever its value: a stored 0.0 is an edge of weight zero,
+ * a stored +inf the same as a missing entry.  NaN and -inf are the caller's to
+ * reject, as on the dense entries.
+ *
+ * A batch is ONE CSR matrix of B * nr rows over nc columns, instance b in rows
+ * b * nr .. b * nr + nr - 1: d_indptr int64 [B * nr + 1], d_indices int32
+ * [nnz], d_data float64 or float32 [nnz].  The layout is canonical: within a
+ * row the indices are strictly increasing and lie in [0, nc).  With d_shape
+ * (as on the _rect_ entries) instance b is its corner nr_b x nc_b: stored
+ * entries in rows >= nr_b or columns >= nc_b are ignored (their values are
+ * never used and may be NaN); an empty or invalid shape gives -1, cost 0 and
+ * zero duals.  1 <= nr <= nc <= SH_MAX_N_LARGE; tall input is the caller's to
+ * transpose.
+ *
+ * d_work is caller-owned scratch of at least lsap_csr_work_bytes(nr, nc, B)
+ * bytes, 8-byte aligned (ten bytes per row and 64-column word: a presence mask
+ * and a prefix count, written by a first pass over the CSR on the same
+ * stream); the entries allocate nothing and never synchronise.  d_cost is
+ * nullable; d_u and d_v are both given or both null.  The launch table is the
+ * dense float entries': one wave up to 64 columns, one wave or four above by
+ * batch size and SH_FLAG_F64_MW / SH_FLAG_F64_SW, eight waves above 1024.
+ *
+ * Memory safety does not rest on the caller's indices: an index outside
+ * [0, nc) is never used to form an address, and every read of d_indices and
+ * d_data for row r stays inside [d_indptr[r], d_indptr[r + 1]).  For a row
+ * that is not canonical the result is unspecified.
+ *
+ * Checked on the host before any device call, SH_ERR_ARGS for: nr < 1,
+ * nr > nc, nc > SH_MAX_N_LARGE, B < 0; with B > 0 a null d_indptr or d_col;
+ * one of d_u / d_v null and not the other; work_bytes too small;
+ * SH_FLAG_F64_MW with SH_FLAG_F64_SW; SH_FLAG_F64_SW with nc > SH_MAX_N.
+ * B == 0 is a no-op after the checks; d_indices and d_data may be null when
+ * there are no entries.
+ * ------------------------------------------------------------------------ */
+size_t lsap_csr_work_bytes(int nr, int nc, int B);
+int lsap_solve_csr_f64(const int64_t *d_indptr, const int32_t *d_indices, const double *d_data, int nr,
+                       int nc, int B, const int32_t *d_shape, int32_t *d_col, double *d_cost, double *d_u,
+                       double *d_v, void *d_work, size_t work_bytes, unsigned flags, void *stream);
+int lsap_solve_csr_f32(const int64_t *d_indptr, const int32_t *d_indices, const float *d_data, int nr,
+                       int nc, int B, const int32_t *d_shape, int32_t *d_col, double *d_cost, double *d_u,
+                       double *d_v, void *d_work, size_t work_bytes, unsigned flags, void *stream);
 
 /* ---------------------------------------------------------------------------
  * Synthetic data of the Kaggle shape (host, deterministic, seeded counter

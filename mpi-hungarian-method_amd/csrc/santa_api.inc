@@ -1148,6 +1148,92 @@ int launch_lsap_check_large(const S *C, int nr, int n, int B, const int32_t *sha
   if (n <= SH_MAX_N) return launch_lsap_check<S, T>(C, nr, n, B, shape, col, u, v, slack, flg, s);
   return launch_lsap_check<S, T, SH_MAX_N_LARGE>(C, nr, n, B, shape, col, u, v, slack, flg, s);
 }
+
+// ---------------------------------------------------------------------------
+// The lsap_solve_csr_ entries: the float solvers on CSR costs (CsrLoader).
+// d_work holds what lsap_csr_prep_kernel writes for the B * nr rows: the
+// 64-bit masks of their ceil(nc / 64) words, then the words' 16-bit prefixes.
+// ---------------------------------------------------------------------------
+size_t csr_words(int nr, int nc, int B) { return (size_t)B * (size_t)nr * (size_t)((nc + 63) / 64); }
+
+// Two launches on the stream: the prep, then the launch table of
+// launch_lsap_f64 and launch_lsap_f64_large with the CSR kernels.
+template <typename S>
+int launch_lsap_csr(const int64_t *indptr, const int32_t *indices, const S *data, int nr, int n, int B,
+                    const int32_t *shape, int32_t *col, double *cost, double *du, double *dv, void *work,
+                    size_t work_bytes, unsigned flags, hipStream_t s) {
+  const int rc = check_lsap_args(nr, n, B, col, SH_MAX_N_LARGE);
+  if (rc) return rc;
+  if (!indptr && B > 0) return fail(SH_ERR_ARGS, "null indptr");
+  if ((du == nullptr) != (dv == nullptr)) return fail(SH_ERR_ARGS, "u and v: both or neither");
+  if ((flags & SH_FLAG_F64_MW) && (flags & SH_FLAG_F64_SW))
+    return fail(SH_ERR_ARGS, "SH_FLAG_F64_MW and SH_FLAG_F64_SW exclude each other");
+  if ((flags & SH_FLAG_F64_SW) && n > SH_MAX_N)
+    return fail(SH_ERR_ARGS, "SH_FLAG_F64_SW: no one-wave float kernel above 1024 columns");
+  if (work_bytes < lsap_csr_work_bytes(nr, n, B) || (B > 0 && !work))
+    return fail(SH_ERR_ARGS, "work buffer smaller than lsap_csr_work_bytes");
+  if ((uintptr_t)work % 8) return fail(SH_ERR_ARGS, "work buffer not 8-byte aligned");
+  const int64_t rows = (int64_t)B * nr;
+  constexpr int PREP_ROWS = CSR_PREP_WG / WAVE;
+  if ((rows + PREP_ROWS - 1) / PREP_ROWS > INT32_MAX) return fail(SH_ERR_ARGS, "B * nr too large");
+  if (B == 0) return SH_OK;
+  uint64_t *mask = (uint64_t *)work;
+  uint16_t *pre = (uint16_t *)(mask + csr_words(nr, n, B));
+  hipLaunchKernelGGL(lsap_csr_prep_kernel, dim3((unsigned)((rows + PREP_ROWS - 1) / PREP_ROWS)), dim3(CSR_PREP_WG),
+                     0, s, indptr, indices, nr, n, rows, shape, mask, pre);
+  if (flags & SH_FLAG_BUILD_ONLY) {  // (phase timing: the prep alone)
+    HIP_TRY(hipGetLastError());
+    return SH_OK;
+  }
+#define MW_(NWW, KK, FBB)                                                                                    \
+  do {                                                                                                       \
+    if (du)                                                                                                  \
+      hipLaunchKernelGGL((lsap_csr_mw_kernel<NWW, KK, S, FBB, double *, double *>), dim3(B), dim3(NWW * WAVE), \
+                         lds, s, indptr, data, mask, pre, nr, n, shape, col, cost, du, dv);                  \
+    else                                                                                                     \
+      hipLaunchKernelGGL((lsap_csr_mw_kernel<NWW, KK, S, FBB>), dim3(B), dim3(NWW * WAVE), lds, s, indptr,   \
+                         data, mask, pre, nr, n, shape, col, cost);                                          \
+  } while (0)
+  if (n > SH_MAX_N) {
+    HIP_TRY_RC(with_large_f64_cfg(n, [&](auto cfg) {
+      using C_ = decltype(cfg);
+      // lsap_csr_mw_kernel's carve-up is lsap_f64_mw_kernel's (launch_lsap_f64_large)
+      const size_t lds = r16((size_t)nr * 8) + r16((size_t)2 * C_::NW * 8) + r16((size_t)2 * C_::NW * 8) +
+                         r16((size_t)nr * 2) + 2 * r16((size_t)n * 2);
+      MW_(C_::NW, C_::K, C_::FB);
+      return (int)SH_OK;
+    }));
+  } else if (n > WAVE && !(flags & SH_FLAG_F64_SW) && ((flags & SH_FLAG_F64_MW) || f64_mw_default(n, B))) {
+    constexpr int NW = 4;
+    const size_t lds = r16((size_t)nr * 8) + r16((size_t)2 * NW * 8) + r16((size_t)2 * NW * 4) +
+                       r16((size_t)nr * 2) + 2 * r16((size_t)n * 2);
+    if (n <= 256) MW_(NW, 1, 10);
+    else if (n <= 512) MW_(NW, 2, 10);
+    else MW_(NW, 4, 10);
+  } else {
+    const size_t lds = r16((size_t)nr * 8) + r16((size_t)nr * 2);
+#define L_(KK)                                                                                            \
+  do {                                                                                                    \
+    if (du)                                                                                               \
+      hipLaunchKernelGGL((lsap_csr_kernel<KK, S, double *, double *>), dim3(B), dim3(WAVE), lds, s,       \
+                         indptr, data, mask, pre, nr, n, shape, col, cost, du, dv);                       \
+    else                                                                                                  \
+      hipLaunchKernelGGL((lsap_csr_kernel<KK, S>), dim3(B), dim3(WAVE), lds, s, indptr, data, mask, pre,  \
+                         nr, n, shape, col, cost);                                                        \
+  } while (0)
+    switch (pick_k(n)) {
+      case 1: L_(1); break;
+      case 2: L_(2); break;
+      case 4: L_(4); break;
+      case 8: L_(8); break;
+      default: L_(16); break;
+    }
+#undef L_
+  }
+#undef MW_
+  HIP_TRY(hipGetLastError());
+  return SH_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1170,6 +1256,25 @@ SH_LARGE_ENTRIES(f32, float, float, double, launch_lsap_f64_large)
 SH_LARGE_ENTRIES(f16, uint16_t, _Float16, double, launch_lsap_f64_large)
 SH_LARGE_ENTRIES(bf16, uint16_t, sh_bf16, double, launch_lsap_f64_large)
 #undef SH_LARGE_ENTRIES
+
+size_t lsap_csr_work_bytes(int nr, int nc, int B) {
+  if (nr < 1 || nc < 1 || B < 1) return 0;
+  return r16(csr_words(nr, nc, B) * (sizeof(uint64_t) + sizeof(uint16_t)));
+}
+
+int lsap_solve_csr_f64(const int64_t *d_indptr, const int32_t *d_indices, const double *d_data, int nr, int nc,
+                       int B, const int32_t *d_shape, int32_t *d_col, double *d_cost, double *d_u, double *d_v,
+                       void *d_work, size_t work_bytes, unsigned flags, void *stream) {
+  return launch_lsap_csr(d_indptr, d_indices, d_data, nr, nc, B, d_shape, d_col, d_cost, d_u, d_v, d_work,
+                         work_bytes, flags, (hipStream_t)stream);
+}
+
+int lsap_solve_csr_f32(const int64_t *d_indptr, const int32_t *d_indices, const float *d_data, int nr, int nc,
+                       int B, const int32_t *d_shape, int32_t *d_col, double *d_cost, double *d_u, double *d_v,
+                       void *d_work, size_t work_bytes, unsigned flags, void *stream) {
+  return launch_lsap_csr(d_indptr, d_indices, d_data, nr, nc, B, d_shape, d_col, d_cost, d_u, d_v, d_work,
+                         work_bytes, flags, (hipStream_t)stream);
+}
 
 int lsap_solve_batched_i64(const int64_t *d_C, int n, int B, int32_t *d_col, int64_t *d_cost,
                            unsigned flags, void *stream) {

@@ -5735,6 +5735,222 @@ __global__ __launch_bounds__(NW * WAVE) void lsap_f64_mw_kernel(const S *C, int 
 }
 
 // ---------------------------------------------------------------------------
+// Sparse (CSR) costs for the float solvers: a missing entry is a forbidden
+// pair, i.e. the instance is solved as its densification (stored values, +inf
+// elsewhere) by the same cores, sap_solve<K, double> and sap_solve_mw_f64.
+//
+// A batch is one CSR matrix of B * NR rows over NC columns (indptr int64,
+// indices int32 strictly increasing inside a row, data float64 or float32),
+// instance b in rows b * NR ...  lsap_csr_prep_kernel makes one pass over it
+// and writes, for every row and every 64-column word q of the row (nw =
+// ceil(NC / 64) <= 64 words), a 64-bit presence mask and the number of the
+// row's entries in the words before q: with sorted indices the entry of column
+// 64 q + l is the row's entry number pre + popcount(mask below bit l).
+//
+// A thread's column j = threadIdx.x + 64 NW k lies in word w + NW k (wave
+// uniform) at bit `lane`, so CsrLoader::load reads that word's (mask, pre)
+// pair from a uniform address and then data[indptr[row] + pre + mbcnt(mask)]
+// where its bit is set -- consecutive addresses over the lanes -- and takes
+// +inf where it is not: one more dependent global load in a step than the
+// dense loader's, for nnz / (nr nc) of its row traffic.
+//
+// Memory safety does not rest on the caller's indices: the prep sets a bit only
+// for 0 <= j < nc (the instance's live columns: entries beyond a ragged corner
+// are dropped, and with sorted indices they are the row's tail), a row's set
+// bits are at most its entries, so pre + rank < indptr[r + 1] - indptr[r], and
+// `indices` is read nowhere else.  A row that is not canonical gets some
+// unspecified subset of its own values.
+// ---------------------------------------------------------------------------
+constexpr int CSR_PREP_WG = 256;  // four rows a workgroup, one wave each
+
+__global__ __launch_bounds__(CSR_PREP_WG) void lsap_csr_prep_kernel(const int64_t *__restrict__ indptr,
+                                                                    const int32_t *__restrict__ indices,
+                                                                    int NR, int NC, int64_t rows,
+                                                                    const int32_t *__restrict__ shape,
+                                                                    uint64_t *__restrict__ mask,
+                                                                    uint16_t *__restrict__ pre) {
+  __shared__ unsigned long long bits[CSR_PREP_WG / WAVE][WAVE];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int nw = (NC + 63) >> 6;
+  const int64_t g = (int64_t)blockIdx.x * (CSR_PREP_WG / WAVE) + w;  // the batch's row
+  const bool on = g < rows;                                           // (wave-uniform)
+  bits[w][lane] = 0;
+  __syncthreads();
+  if (on) {
+    int n = NC;  // live columns of the row's instance
+    if (shape) n = min(shape[2 * (size_t)(g / NR) + 1], NC);
+    const int64_t e1 = indptr[g + 1];
+    for (int64_t e = indptr[g] + lane; e < e1; e += WAVE) {
+      const int j = indices[e];
+      if (j >= 0 && j < n) atomicOr(&bits[w][j >> 6], 1ull << (j & 63));
+    }
+  }
+  __syncthreads();
+  const unsigned long long m = bits[w][lane];
+  const int cnt = __popcll(m);
+  int incl = cnt;  // inclusive scan of the words' counts over the lanes
+#pragma unroll
+  for (int o = 1; o < WAVE; o <<= 1) {
+    const int t = __shfl_up(incl, o, WAVE);
+    if (lane >= o) incl += t;
+  }
+  if (on && lane < nw) {
+    mask[(size_t)g * nw + lane] = m;
+    pre[(size_t)g * nw + lane] = (uint16_t)(incl - cnt);
+  }
+}
+
+template <int NW, int K, typename S>
+struct CsrLoader {
+  const int64_t *indptr;  // the instance's rows: indptr + b * NR
+  const S *data;          // the batch's values
+  const uint64_t *mask;   // the instance's words: mask + b * NR * nw
+  const uint16_t *pre;
+  int nw;                 // 64-column words of a row
+  __device__ __forceinline__ void load(int i, double (&c)[K]) const {
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const S *row = data + indptr[i];
+    const size_t r = (size_t)i * nw;
+    // Two round trips a step, whatever K: the K (mask, prefix) pairs, then the
+    // K values, each group issued without a branch between its loads.  (With
+    // `if (q < nw)` around the pair and `if (bit)` around the value the
+    // compiler waits for each load inside its branch, and the 2 K latencies of
+    // a step add up: GlobalLoaderF64's note, twice over.)  A word past the
+    // row's last reads the last word and is masked out; a lane without an
+    // entry reads the row's first mask word, which is always there, and takes
+    // +inf.  The values are widened after all K loads are issued.
+    uint64_t m[K];
+    int p[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int q = min(w + NW * k, nw - 1);
+      m[k] = mask[r + q];
+      p[k] = pre[r + q];
+    }
+    const S *nothing = (const S *)(mask + r);
+    S raw[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      if (w + NW * k >= nw) m[k] = 0;
+      const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m[k] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m[k], 0u));
+      raw[k] = *(((m[k] >> lane) & 1) ? row + (p[k] + rank) : nothing);
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) c[k] = ((m[k] >> lane) & 1) ? widen_f64(raw[k]) : VT<double>::inf();
+  }
+  // the stored value of (i, j), +inf for a missing entry: the cost sum's lookup
+  __device__ __forceinline__ double at(int i, int j) const {
+    if (j < 0) return VT<double>::inf();  // (no row of a solved instance is without a column)
+    const size_t r = (size_t)i * nw + (size_t)(j >> 6);
+    const uint64_t m = mask[r];
+    if (!((m >> (j & 63)) & 1)) return VT<double>::inf();
+    return widen_f64(data[indptr[i] + pre[r] + __popcll(m & ((1ull << (j & 63)) - 1))]);
+  }
+};
+
+// lsap_f64_kernel on CSR costs: the same carve-up, outputs and cost order.
+template <int K, typename S, typename... DU>
+__global__ __launch_bounds__(WAVE) void lsap_csr_kernel(const int64_t *indptr, const S *data,
+                                                        const uint64_t *mask, const uint16_t *pre, int NR,
+                                                        int NC, const int32_t *shape, int32_t *col,
+                                                        double *cost, DU... duals) {
+  constexpr bool DUALS = sizeof...(DU) == 2;
+  static_assert(DUALS || sizeof...(DU) == 0, "duals: du, dv");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int b = blockIdx.x;
+  const int lane = threadIdx.x;
+  int nr, n;  // live rows and columns (see lsap_i64_kernel)
+  if (!lsap_shape(shape, b, NR, NC, nr, n)) {
+    lsap_no_instance<WAVE>(col, cost, b, NR, NC, duals...);
+    return;
+  }
+  double *u_l = (double *)smem;
+  int16_t *c4r_l = (int16_t *)(smem + r16((size_t)nr * sizeof(double)));
+  for (int i = lane; i < nr; i += WAVE) {
+    u_l[i] = 0;
+    c4r_l[i] = -1;
+  }
+  __syncthreads();
+  int64_t steps = 0;
+  const int nw = (NC + 63) >> 6;
+  using CL = CsrLoader<1, K, S>;
+  std::conditional_t<DUALS, WithDuals<CL, double>, CL> ld{
+      CL{indptr + (size_t)b * NR, data, mask + (size_t)b * NR * nw, pre + (size_t)b * NR * nw, nw}};
+  if constexpr (DUALS) ld.dv = duals_v(duals...) + (size_t)b * NC;
+  const int st = sap_solve<K, double, DUALS>(nr, n, ld, u_l, c4r_l, steps);
+  __syncthreads();
+  if constexpr (DUALS)
+    duals_store_f64<WAVE>(duals_u(duals...), duals_v(duals...), u_l, st, b, NR, NC, nr, n);
+  double acc = 0;
+  for (int i = lane; i < NR; i += WAVE) {
+    const bool live = st == 0 && i < nr;
+    const int cidx = live ? c4r_l[i] : -1;
+    col[(size_t)b * NR + i] = cidx;
+    if (live && cost) acc += ld.at(i, cidx);
+  }
+  if (cost) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, WAVE);
+    if (lane == 0) cost[b] = acc;
+  }
+}
+
+// lsap_f64_mw_kernel on CSR costs.
+template <int NW, int K, typename S, int FB = 10, typename... DU>
+__global__ __launch_bounds__(NW * WAVE) void lsap_csr_mw_kernel(const int64_t *indptr, const S *data,
+                                                                const uint64_t *mask, const uint16_t *pre,
+                                                                int NR, int NC, const int32_t *shape,
+                                                                int32_t *col, double *cost, DU... duals) {
+  constexpr bool DUALS = sizeof...(DU) == 2;
+  static_assert(DUALS || sizeof...(DU) == 0, "duals: du, dv");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int WG = NW * WAVE;
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  int nr, n;  // live rows and columns (see lsap_i64_kernel)
+  if (!lsap_shape(shape, b, NR, NC, nr, n)) {
+    lsap_no_instance<WG>(col, cost, b, NR, NC, duals...);
+    return;
+  }
+  size_t off = 0;
+  SolveLdsF64 Sl;
+  Sl.u = (double *)(smem + off);      off += r16((size_t)nr * 8);
+  Sl.rv = (double *)(smem + off);     off += r16((size_t)2 * NW * 8);
+  Sl.rk = (uint32_t *)(smem + off);   off += r16((size_t)2 * NW * (FB > 10 ? 8 : 4));
+  Sl.c4r = (int16_t *)(smem + off);   off += r16((size_t)nr * 2);
+  Sl.r4c = (int16_t *)(smem + off);   off += r16((size_t)n * 2);
+  Sl.path = (int16_t *)(smem + off);
+  for (int i = tid; i < n; i += WG) {
+    if (i < nr) {
+      Sl.u[i] = 0;
+      Sl.c4r[i] = -1;
+    }
+    Sl.r4c[i] = -1;
+    Sl.path[i] = -1;
+  }
+  __syncthreads();
+  const int nw = (NC + 63) >> 6;
+  using CL = CsrLoader<NW, K, S>;
+  std::conditional_t<DUALS, WithDuals<CL, double>, CL> ld{
+      CL{indptr + (size_t)b * NR, data, mask + (size_t)b * NR * nw, pre + (size_t)b * NR * nw, nw}};
+  if constexpr (DUALS) ld.dv = duals_v(duals...) + (size_t)b * NC;
+  const int st = sap_solve_mw_f64<NW, K, DUALS, FB>(nr, n, ld, Sl);
+  __syncthreads();
+  if constexpr (DUALS)
+    duals_store_f64<WG>(duals_u(duals...), duals_v(duals...), Sl.u, st, b, NR, NC, nr, n);
+  for (int i = tid; i < NR; i += WG) col[(size_t)b * NR + i] = (st == 0 && i < nr) ? Sl.c4r[i] : -1;
+  if (cost && tid < WAVE) {
+    double acc = 0;
+    for (int i = tid; i < NR; i += WAVE)
+      if (st == 0 && i < nr) acc += ld.at(i, Sl.c4r[i]);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, WAVE);
+    if (tid == 0) cost[b] = acc;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Dual certificate of a batch: three launches on one stream.
 //   lsap_cert_kernel   one workgroup per instance, O(nr + nc): is col an
 //     assignment (LDS bitmap of the columns), the matched slacks, the signs of

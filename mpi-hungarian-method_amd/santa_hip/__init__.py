@@ -20,9 +20,10 @@ from .context import SantaGPU, score_from_sums  # noqa: F401
 from .driver import my_optimizer, run_rounds  # noqa: F401
 from ._lib import (SH_CERT_COL, SH_CERT_GAP, SH_CERT_NONE, SH_CERT_RANGE, SH_CERT_SIGN,  # noqa: F401
                    SH_CERT_SLACK, SH_CERT_TIGHT)
-from .lsap import (check_duals, check_duals_large, linear_sum_assignment,  # noqa: F401
-                   linear_sum_assignment_duals, linear_sum_assignment_large, solve_batched,
-                   solve_batched_large, solve_hash)
+from .lsap import (check_duals, check_duals_large, csr_transpose, densify,  # noqa: F401
+                   linear_sum_assignment, linear_sum_assignment_duals, linear_sum_assignment_large,
+                   linear_sum_assignment_sparse, solve_batched, solve_batched_large, solve_batched_sparse,
+                   solve_hash, validate_csr)
 
 lib()  # load the C-ABI at import: no silent CPU path
 
@@ -31,6 +32,7 @@ __all__ = [
     "optimize_block_triplets",
     "linear_sum_assignment", "linear_sum_assignment_duals", "solve_batched", "check_duals", "solve_hash",
     "linear_sum_assignment_large", "solve_batched_large", "check_duals_large",
+    "linear_sum_assignment_sparse", "solve_batched_sparse", "densify", "csr_transpose", "validate_csr",
     "SH_CERT_COL", "SH_CERT_SLACK", "SH_CERT_TIGHT", "SH_CERT_SIGN", "SH_CERT_GAP", "SH_CERT_NONE",
     "SH_CERT_RANGE", "my_optimizer", "run_rounds",
     "SantaGPU", "score_from_sums", "SantaHipError",

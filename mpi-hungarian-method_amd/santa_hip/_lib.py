@@ -138,6 +138,11 @@ SIGNATURES = {
 for _suf in ("i64", "i32", "f64", "f32", "f16", "bf16"):  # the duals / check_duals argument lists
     SIGNATURES["lsap_solve_large_" + _suf] = SIGNATURES["lsap_solve_batched_duals_" + _suf]
     SIGNATURES["lsap_check_duals_large_" + _suf] = SIGNATURES["lsap_check_duals_" + _suf]
+# the sparse (CSR) float entries: indptr, indices, data, nr, nc, B, shape, col, cost, u, v, work, work_bytes, flags, stream
+SIGNATURES["lsap_csr_work_bytes"] = (ctypes.c_size_t, [_I, _I, _I])
+for _suf in ("f64", "f32"):
+    SIGNATURES["lsap_solve_csr_" + _suf] = (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, ctypes.c_size_t,
+                                                 _U, _P])
 
 
 class RoundExt(ctypes.Structure):

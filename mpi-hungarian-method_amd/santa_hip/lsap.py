@@ -16,6 +16,9 @@ against the costs on the device: for integer costs flags == 0 proves optimality.
 solve_batched_large, check_duals_large and linear_sum_assignment_large are the
 same three up to SH_MAX_N_LARGE = 4096 rows or columns (the reference's own
 block sizes, 2000 and 3000), through the lsap_*_large_ entries.
+solve_batched_sparse and linear_sum_assignment_sparse take the costs as CSR, a
+missing entry being a forbidden pair (the lsap_solve_csr_ entries): the dense
+float solve of the densification (densify), without the dense matrix.
 """
 from __future__ import annotations
 
@@ -471,3 +474,225 @@ def linear_sum_assignment_large(cost_matrix, maximize: bool = False, device: int
     for any shape up to SH_MAX_N_LARGE = 4096 on the longer side: the same
     routing, results and errors, solved by solve_batched_large."""
     return _lsa(cost_matrix, maximize, device, duals, solve_batched_large, _lib.SH_MAX_N_LARGE)
+
+
+# ---------------------------------------------------------------------------
+# Sparse (CSR) costs: a missing entry is a forbidden pair.  A sparse instance
+# is solved exactly as the dense float solver solves its densification.
+# ---------------------------------------------------------------------------
+def _np(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def densify(crow, col_indices, values, shape) -> np.ndarray:
+    """The definition of a sparse instance (host-only): the float64 array of
+    `shape` -- (B, NR, NC) for a batch stored as one CSR matrix of B * NR rows,
+    or (nr, nc) for one matrix -- that holds each stored value (widened) and
+    +inf everywhere else."""
+    crow, idx = _np(crow).astype(np.int64), _np(col_indices).astype(np.int64)
+    val = _np(values.double() if isinstance(values, torch.Tensor) else values)  # (bfloat16 has no numpy dtype)
+    shape = tuple(int(s) for s in shape)
+    rows = int(np.prod(shape[:-1]))
+    if crow.size != rows + 1:
+        raise ValueError(f"crow has {crow.size} entries, expected {rows + 1}")
+    D = np.full((rows, shape[-1]), np.inf, dtype=np.float64)
+    D[np.repeat(np.arange(rows), np.diff(crow)), idx] = val.astype(np.float64)
+    return D.reshape(shape)
+
+
+def csr_transpose(indptr, indices, data, shape):
+    """(indptr, indices, data, (nc, nr)) of the transpose of an nr x nc CSR
+    matrix, in pure numpy.  The sort by column is stable, so the entries of a
+    new row keep the order of their old rows: canonical input gives canonical
+    output."""
+    indptr, indices, data = np.asarray(indptr, dtype=np.int64), np.asarray(indices), np.asarray(data)
+    nr, nc = shape
+    rows = np.repeat(np.arange(nr, dtype=indices.dtype if indices.size else np.int32), np.diff(indptr))
+    order = np.argsort(indices, kind="stable")
+    indptr_t = np.zeros(nc + 1, dtype=np.int64)
+    np.cumsum(np.bincount(indices, minlength=nc), out=indptr_t[1:])
+    return indptr_t, rows[order], data[order], (nc, nr)
+
+
+def validate_csr(crow, col_indices, values, shape, shapes=None) -> None:
+    """ValueError unless (crow, col_indices, values) is the canonical CSR batch
+    of `shape` = (B, NR, NC): crow[0] == 0, crow non-decreasing, crow[-1] ==
+    nnz, indices in [0, NC) and strictly increasing inside each row, no NaN or
+    -inf value (with `shapes`, none inside the instances' corners: what lies
+    outside is never used).  Torch ops on the tensors' own device."""
+    B, NR, NC = shape
+    rows, nnz = B * NR, col_indices.numel()
+    if crow.dim() != 1 or crow.numel() != rows + 1:
+        raise ValueError(f"crow must have B * NR + 1 = {rows + 1} entries, got {tuple(crow.shape)}")
+    if col_indices.dim() != 1 or values.dim() != 1 or values.numel() != nnz:
+        raise ValueError("col_indices and values must be 1-D and of equal length")
+    crow = crow.long()
+    if int(crow[0]) != 0:
+        raise ValueError("crow[0] != 0")
+    if bool((crow[1:] < crow[:-1]).any()):
+        raise ValueError("crow is decreasing somewhere")
+    if int(crow[-1]) != nnz:
+        raise ValueError(f"crow[-1] = {int(crow[-1])} != nnz = {nnz}")
+    if nnz == 0:
+        return
+    idx = col_indices.long()
+    if bool(((idx < 0) | (idx >= NC)).any()):
+        raise ValueError(f"a column index lies outside [0, {NC})")
+    first = torch.zeros(nnz + 1, dtype=torch.bool, device=idx.device)
+    first[crow] = True  # the entries that begin a row
+    if bool(((idx[1:] <= idx[:-1]) & ~first[1:nnz]).any()):
+        raise ValueError("the column indices of a row are not strictly increasing")
+    if values.is_floating_point():
+        bad = torch.isnan(values) | (values == float("-inf"))
+        if shapes is not None and bool(bad.any()):
+            row = torch.repeat_interleave(torch.arange(rows, device=idx.device), crow[1:] - crow[:-1])
+            sh = torch.as_tensor(np.asarray(_np(shapes), dtype=np.int64), device=idx.device)
+            b = torch.div(row, NR, rounding_mode="floor")
+            bad &= (row - b * NR < sh[b, 0]) & (idx < sh[b, 1])
+        if bool(bad.any()):
+            raise ValueError("matrix contains invalid numeric entries")
+
+
+def _csr_parts(crow, col_indices, values, shape):
+    """The (crow, col_indices, values, (B, NR, NC)) a sparse call means: the
+    triple as given, or those of one 2-D torch.sparse_csr tensor [B * NR, NC]."""
+    if isinstance(crow, torch.Tensor) and crow.layout == torch.sparse_csr:
+        A = crow
+        if A.dim() != 2:
+            raise ValueError("expected one 2-D sparse CSR tensor of shape [B * NR, NC]")
+        if shape is None:
+            shape = (1,) + tuple(A.shape)
+        crow, col_indices, values = A.crow_indices(), A.col_indices(), A.values()
+        if tuple(A.shape) != (shape[0] * shape[1], shape[2]):
+            raise ValueError(f"a sparse tensor of shape {tuple(A.shape)} is no batch of shape {tuple(shape)}")
+    if shape is None or len(shape) != 3:
+        raise ValueError("shape = (B, NR, NC) is required")
+    return crow, col_indices, values, tuple(int(s) for s in shape)
+
+
+def solve_batched_sparse(crow, col_indices=None, values=None, shape=None, with_cost: bool = True,
+                         flags: int = 0, shapes=None, maximize: bool = False, duals: bool = False,
+                         validate: bool = True):
+    """solve_batched_large on sparse costs, a missing entry being a forbidden
+    pair: each instance is solved exactly as solve_batched_large solves its
+    densification (densify: the stored values, +inf elsewhere), with the same
+    col, the same bits in cost, u and v, and -1 / cost 0 / NaN duals for an
+    instance without a perfect matching of its rows.
+
+    The batch is one CSR matrix of B * NR rows over NC columns, instance b in
+    rows b * NR ..: crow [B * NR + 1] (int64 or int32), col_indices [nnz]
+    (strictly increasing inside a row), values [nnz], all on one device, with
+    shape = (B, NR, NC); or one 2-D torch.sparse_csr tensor [B * NR, NC] in
+    place of the triple.  float64 and float32 values are read at their own
+    width; integer and 16-bit values are converted to float64, as scipy does.
+    A stored 0.0 is an edge of weight zero, a stored +inf a missing entry.
+    1 <= NR <= NC <= SH_MAX_N_LARGE (NR > NC raises ValueError: transpose).
+    `shapes` makes the batch ragged as in solve_batched; entries outside an
+    instance's corner are ignored.  validate=True checks the CSR (validate_csr)
+    on its device first; without it a malformed matrix gives an unspecified
+    result, but nothing outside the buffers is touched.  flags: SH_FLAG_F64_MW /
+    SH_FLAG_F64_SW as in solve_batched_large; SH_FLAG_BUILD_ONLY runs the first
+    pass over the CSR alone and leaves the outputs unwritten (phase timing)."""
+    crow, col_indices, values, shape = _csr_parts(crow, col_indices, values, shape)
+    B, NR, NC = shape
+    if B < 0 or NR < 0 or NC < 0:
+        raise ValueError(f"negative size in shape {shape}")
+    if NR > NC:
+        raise ValueError(f"a sparse batch must be wide, got [{NR}, {NC}]: transpose it so that NR <= NC")
+    if NC > _lib.SH_MAX_N_LARGE:
+        raise ValueError(f"max(NR, NC) = {NC} > {_lib.SH_MAX_N_LARGE}")
+    if values.is_complex():
+        raise TypeError(f"unsupported dtype {values.dtype}")
+    if values.dtype not in (torch.float64, torch.float32):
+        values = values.to(torch.float64)
+    shape_host = check_shapes(shapes, B, NR, NC) if shapes is not None else None
+    if validate:
+        validate_csr(crow, col_indices, values, shape, shape_host)
+    elif crow.numel() != B * NR + 1 or col_indices.numel() != values.numel():
+        raise ValueError("crow must have B * NR + 1 entries, col_indices and values equal lengths")
+    require_gpu()
+    dev = values.device
+    if B == 0 or NR == 0:
+        out = (torch.full((B, NR), -1, dtype=torch.int32, device=dev),
+               torch.zeros(B, dtype=torch.float64, device=dev) if with_cost else None)
+        if duals:
+            out += (torch.zeros((B, NR), dtype=torch.float64, device=dev),
+                    torch.zeros((B, NC), dtype=torch.float64, device=dev))
+        return out
+    crow = crow.to(torch.int64).contiguous()
+    col_indices = col_indices.to(torch.int32).contiguous()
+    values = (-values if maximize else values).contiguous()
+    shape_dev = torch.from_numpy(shape_host).to(dev) if shape_host is not None else None
+    L = _lib.lib()
+    nbytes = int(L.lsap_csr_work_bytes(NR, NC, B))
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    col = torch.empty((B, NR), dtype=torch.int32, device=dev)
+    cost = torch.empty(B, dtype=torch.float64, device=dev) if with_cost else None
+    u = torch.empty((B, NR), dtype=torch.float64, device=dev) if duals else None
+    v = torch.empty((B, NC), dtype=torch.float64, device=dev) if duals else None
+    entry = getattr(L, "lsap_solve_csr_" + DTYPE_SUFFIX[values.dtype])
+    nnz = values.numel()
+    rc = entry(_p(crow), _p(col_indices) if nnz else None, _p(values) if nnz else None, NR, NC, B,
+               _p(shape_dev), _p(col), _p(cost), _p(u), _p(v), _p(work), nbytes,
+               _lib.SH_COMPAT_TIEBREAK | flags, current_stream_handle(dev))
+    _lib.check(rc, "lsap_solve_csr")
+    if maximize:
+        cost = -cost if cost is not None else None
+        if duals:
+            u, v = -u, -v
+    return (col, cost, u, v) if duals else (col, cost)
+
+
+def _csr_of(A):
+    """(indptr, indices, data, (nr, nc)) in numpy of linear_sum_assignment_sparse's
+    argument, canonical when it comes from scipy.sparse or torch."""
+    if hasattr(A, "tocsr"):  # a scipy.sparse matrix or array
+        A = A.tocsr().copy()
+        A.sum_duplicates()  # (also sorts the indices; stored zeros stay)
+        return A.indptr, A.indices, A.data, tuple(A.shape)
+    if isinstance(A, torch.Tensor):
+        if A.layout != torch.sparse_csr or A.dim() != 2:
+            raise ValueError("expected a 2-D torch.sparse_csr tensor")
+        val = A.values()
+        if val.dtype in (torch.float16, torch.bfloat16):
+            val = val.double()
+        return _np(A.crow_indices()), _np(A.col_indices()), _np(val), tuple(A.shape)
+    indptr, indices, data, shape = A
+    return _np(indptr), _np(indices), _np(data), tuple(int(s) for s in shape)
+
+
+def linear_sum_assignment_sparse(A, maximize: bool = False, device: int | str = 0, duals: bool = False):
+    """linear_sum_assignment for one sparse matrix whose missing entries are
+    forbidden pairs: (row_ind, col_ind) -- with duals=True also (u, v) -- of
+    scipy's linear_sum_assignment on densify(A), ValueError("cost matrix is
+    infeasible") where no full matching of the shorter side exists.
+
+    A: a scipy.sparse matrix or array (anything with .tocsr()), a 2-D
+    torch.sparse_csr tensor, or (indptr, indices, data, (nr, nc)).  Up to
+    SH_MAX_N_LARGE on the longer side; tall input is transposed on the host
+    (csr_transpose) and re-ordered as scipy does; empty input returns empty
+    arrays."""
+    indptr, indices, data, (nr, nc) = _csr_of(A)
+    if nr == 0 or nc == 0:
+        z = np.zeros(0, dtype=np.int64)
+        return (z, z.copy(), np.zeros(nr), np.zeros(nc)) if duals else (z, z.copy())
+    if max(nr, nc) > _lib.SH_MAX_N_LARGE:
+        raise ValueError(f"max(nr, nc) = {max(nr, nc)} > {_lib.SH_MAX_N_LARGE}")
+    if data.dtype not in (np.float64, np.float32):
+        data = data.astype(np.float64)
+    tall = nr > nc
+    if tall:
+        indptr, indices, data, (nr, nc) = csr_transpose(indptr, indices, data, (nr, nc))
+    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    out = solve_batched_sparse(torch.from_numpy(np.ascontiguousarray(indptr, dtype=np.int64)).to(dev),
+                               torch.from_numpy(np.ascontiguousarray(indices, dtype=np.int32)).to(dev),
+                               torch.from_numpy(np.ascontiguousarray(data)).to(dev), shape=(1, nr, nc),
+                               with_cost=False, maximize=maximize, duals=duals)
+    col = out[0][0].cpu().numpy().astype(np.int64)
+    if (col < 0).any():
+        raise ValueError("cost matrix is infeasible")
+    res = tall_result(col) if tall else (np.arange(col.size, dtype=np.int64), col)
+    if not duals:
+        return res
+    u, v = out[2][0].cpu().numpy(), out[3][0].cpu().numpy()
+    return res + ((v, u) if tall else (u, v))
