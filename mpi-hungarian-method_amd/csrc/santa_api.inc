@@ -889,8 +889,8 @@ int sh_unpack_types(int16_t *d_types, const int32_t *d_rows, int count, const in
 
 namespace {
 // nr x nc instances (the square entries: nr == nc == n); host-side only.
-// (cap: SH_MAX_N, or SH_MAX_N_LARGE for the lsap_*_large_ entries)
-int check_lsap_args(int nr, int nc, int B, const int32_t *col, int cap = SH_MAX_N) {
+// cap: SH_MAX_N, or SH_MAX_N_LARGE for the lsap_*_large_ and lsap_solve_csr_ entries.
+int check_lsap_args(int nr, int nc, int B, const int32_t *col, int cap) {
   if (nr < 1 || nc > cap)
     return fail(SH_ERR_ARGS, cap == SH_MAX_N ? "sizes must be in [1, 1024]" : "sizes must be in [1, 4096]");
   if (nr > nc) return fail(SH_ERR_ARGS, "nr > nc: transpose tall input (as scipy does) and solve that");
@@ -899,172 +899,46 @@ int check_lsap_args(int nr, int nc, int B, const int32_t *col, int cap = SH_MAX_
   return SH_OK;
 }
 
-// The launch configuration follows the column slots nc (a thread owns K of
-// them, as in the square case); the LDS size the rows and columns.
-// DUALS: the kernels' duals form (du, dv required), same configurations.
-template <typename S, bool HASH, bool DUALS = false>
-int launch_lsap_i64(const S *C, uint64_t seed, int64_t mod, int nr, int n, int B, const int32_t *shape,
-                    int32_t *col, int64_t *cost, unsigned flags, hipStream_t s, int64_t *du = nullptr,
-                    int64_t *dv = nullptr) {
-  const int rc = check_lsap_args(nr, n, B, col);
-  if (rc) return rc;
-  if (DUALS && (!du || !dv) && B > 0) return fail(SH_ERR_ARGS, "null u or v");
-  if (B == 0) return SH_OK;
-  // The LDS sizes here and in launch_lsap_f64 mirror by hand how the kernels
-  // carve smem: lsap_i64_kernel's Sl.u / c4r / r4c / path / red lines (red
-  // sized for four waves whatever NW, plus 64 spare bytes), lsap_f64_mw_kernel's
-  // Sl.u / rv / rk / c4r / r4c / path lines, and lsap_f64_kernel's u_l and
-  // c4r_l.  A change to one side must be made on the other.
-  const size_t lds = r16((size_t)nr * 8) + r16((size_t)nr * 2) + 2 * r16((size_t)n * 2) +
-                     r16((size_t)4 * 4 * 8) + 64;
-  const bool rect = nr != n || shape;
-#define L__(NWW, KK, RR)                                                                            \
-  hipLaunchKernelGGL((lsap_i64_kernel<NWW, KK, S, HASH, RR, 10>), dim3(B), dim3(NWW * WAVE), lds, s, C, \
-                     seed, mod, nr, n, shape, col, cost, (int32_t *)nullptr, flags)
-#define L_(NWW, KK)                                                                                  \
-  do {                                                                                               \
-    if constexpr (DUALS)                                                                             \
-      hipLaunchKernelGGL((lsap_i64_kernel<NWW, KK, S, HASH, true, 10, int64_t *, int64_t *>),        \
-                         dim3(B), dim3(NWW * WAVE), lds, s, C, seed, mod, nr, n, shape, col, cost,   \
-                         (int32_t *)nullptr, flags, du, dv);                                         \
-    else if (rect) L__(NWW, KK, true);                                                               \
-    else L__(NWW, KK, false);                                                                        \
-  } while (0)
-  // a batch that fills the chip many times over runs one wave per instance
-  // with several columns per thread (fewer waves per block, more blocks per
-  // CU: the large-block kernel's lesson): n <= 128 from 4096 instances
-  // (65536 hash-generated: 1.45 -> 2.49 M solves/s), n = 256 from 65536
-  // (397 -> 443 k/s; at 4096 it lost 17 %); n = 512 gained nothing
-  // (profiles/r02e_lsap_sweep_ab.jsonl)
-  if (n <= WAVE) L_(1, 1);
-  else if (B >= 4096 && n <= 128) L_(1, 2);
-  else if (B >= 65536 && n <= 256) L_(1, 4);
-  else if (n <= 256) L_(4, 1);
-  else if (n <= 512) L_(4, 2);
-  else L_(4, 4);
-#undef L_
-#undef L__
-  HIP_TRY(hipGetLastError());
-  return SH_OK;
-}
-
-// Whether a float batch of B instances with nc columns runs four waves per
-// instance by default (measured: DESIGN §7, profiles/lsap_float_ab.jsonl).
-// Up to 1024 instances one wave each leaves SIMDs idle and four waves won at
-// every nc measured (128: 5-9 %, 256: 17-22 %, 512: 29-36 %, 1024: 38-49 %);
-// at 4096 instances one wave each won (nc = 128, 256, 512), and nothing
-// between 1024 and 4096 was measured except nc = 256 (2048: four waves, 5 %),
-// so those batches keep the kernel they always ran.
-bool f64_mw_default(int nc, int B) { return nc > WAVE && B <= 1024; }
-
-// Floating-point costs stored as S (double, float, _Float16, sh_bf16), solved
-// in float64.  One wave per instance (lsap_f64_kernel) or, for nc > 64, four
-// (lsap_f64_mw_kernel, 1 / 2 / 4 columns per thread as the integer path's):
-// the default is f64_mw_default above, SH_FLAG_F64_MW / SH_FLAG_F64_SW force one.
-template <typename S, bool DUALS = false>
-int launch_lsap_f64(const S *C, int nr, int n, int B, const int32_t *shape, int32_t *col,
-                    double *cost, unsigned flags, hipStream_t s, double *du = nullptr,
-                    double *dv = nullptr) {
+// The checks of the lsap_solve_batched_rect_ entries and, with `duals` (u and
+// v required), of the lsap_solve_batched_duals_ ones: up to SH_MAX_N columns.
+template <typename T>
+int check_solve(const void *C, int nr, int nc, int B, const int32_t *col, bool duals, const T *du, const T *dv) {
   if (!C && B > 0) return fail(SH_ERR_ARGS, "null C");
-  const int rc = check_lsap_args(nr, n, B, col);
-  if (rc) return rc;
-  if (DUALS && (!du || !dv) && B > 0) return fail(SH_ERR_ARGS, "null u or v");
-  if ((flags & SH_FLAG_F64_MW) && (flags & SH_FLAG_F64_SW))
-    return fail(SH_ERR_ARGS, "SH_FLAG_F64_MW and SH_FLAG_F64_SW exclude each other");
-  if (B == 0) return SH_OK;
-  const bool mw = n > WAVE && !(flags & SH_FLAG_F64_SW) && ((flags & SH_FLAG_F64_MW) || f64_mw_default(n, B));
-  if (mw) {
-    constexpr int NW = 4;
-    const size_t lds = r16((size_t)nr * 8) + r16((size_t)2 * NW * 8) + r16((size_t)2 * NW * 4) +
-                       r16((size_t)nr * 2) + 2 * r16((size_t)n * 2);
-#define L_(KK)                                                                                        \
-  do {                                                                                                \
-    if constexpr (DUALS)                                                                              \
-      hipLaunchKernelGGL((lsap_f64_mw_kernel<NW, KK, S, 10, double *, double *>), dim3(B),            \
-                         dim3(NW * WAVE), lds, s, C, nr, n, shape, col, cost, du, dv);                \
-    else                                                                                              \
-      hipLaunchKernelGGL((lsap_f64_mw_kernel<NW, KK, S, 10>), dim3(B), dim3(NW * WAVE), lds, s, C,    \
-                         nr, n, shape, col, cost);                                                    \
-  } while (0)
-    if (n <= 256) L_(1);
-    else if (n <= 512) L_(2);
-    else L_(4);
-#undef L_
-  } else {
-    const size_t lds = r16((size_t)nr * 8) + r16((size_t)nr * 2);
-#define L_(KK)                                                                                       \
-  do {                                                                                               \
-    if constexpr (DUALS)                                                                             \
-      hipLaunchKernelGGL((lsap_f64_kernel<KK, S, double *, double *>), dim3(B), dim3(WAVE), lds, s,  \
-                         C, nr, n, shape, col, cost, du, dv);                                        \
-    else                                                                                             \
-      hipLaunchKernelGGL((lsap_f64_kernel<KK, S>), dim3(B), dim3(WAVE), lds, s, C, nr, n, shape,     \
-                         col, cost);                                                                 \
-  } while (0)
-    switch (pick_k(n)) {
-      case 1: L_(1); break;
-      case 2: L_(2); break;
-      case 4: L_(4); break;
-      case 8: L_(8); break;
-      default: L_(16); break;
-    }
-#undef L_
-  }
-  HIP_TRY(hipGetLastError());
+  HIP_TRY_RC(check_lsap_args(nr, nc, B, col, SH_MAX_N));
+  if (duals && (!du || !dv) && B > 0) return fail(SH_ERR_ARGS, "null u or v");
   return SH_OK;
 }
 
-// The certificate (lsap_cert_kernel, lsap_slack_kernel, lsap_cert_final_kernel):
-// S the stored cost type, T int64_t or double.  The pass over the corners
-// reads 16 bytes per load when every row starts 16-byte aligned; a batch too
-// small to fill the chip with one workgroup per instance is split by rows.
-// NCAP: the kernels' column capacity, SH_MAX_N or SH_MAX_N_LARGE.
-template <typename S, typename T, int NCAP = SH_MAX_N>
-int launch_lsap_check(const S *C, int nr, int n, int B, const int32_t *shape, const int32_t *col,
-                      const T *u, const T *v, T *slack, int32_t *flg, hipStream_t s) {
-  const int rc = check_lsap_args(nr, n, B, col, NCAP);
-  if (rc) return rc;
-  if (B > 0 && (!C || !u || !v || !slack || !flg)) return fail(SH_ERR_ARGS, "null C, u, v, slack or flags");
-  if (B == 0) return SH_OK;
-  hipLaunchKernelGGL((lsap_cert_kernel<S, T, NCAP>), dim3(B), dim3(CERT_WG), 0, s, C, nr, n, shape, col, u, v,
-                     slack, flg);
-  // at least 8 rows per workgroup, about 2048 workgroups when the batch allows
-  const int chunks = std::min(std::max(1, 2048 / B), (nr + 7) / 8);
-  const int rows_per = (nr + chunks - 1) / chunks;
-  const dim3 grid(B, (nr + rows_per - 1) / rows_per);
-  constexpr int VEC = 16 / (int)sizeof(S);
-  if ((uintptr_t)C % 16 == 0 && n % VEC == 0)
-    hipLaunchKernelGGL((lsap_slack_kernel<S, T, VEC, NCAP>), grid, dim3(CERT_WG), 0, s, C, nr, n, shape, u, v,
-                       slack, flg, rows_per);
-  else
-    hipLaunchKernelGGL((lsap_slack_kernel<S, T, 1, NCAP>), grid, dim3(CERT_WG), 0, s, C, nr, n, shape, u, v,
-                       slack, flg, rows_per);
-  hipLaunchKernelGGL((lsap_cert_final_kernel<T>), dim3((B + CERT_WG - 1) / CERT_WG), dim3(CERT_WG), 0, s,
-                     B, slack, flg);
-  HIP_TRY(hipGetLastError());
-  return SH_OK;
-}
-
-// ---------------------------------------------------------------------------
-// The lsap_*_large_ entries: up to SH_MAX_N_LARGE columns.  Every check is made
-// on the host before any device call; up to SH_MAX_N columns they forward to
-// the launchers above (the same kernels, the same bits), beyond that to the
-// FB = 12 instantiations below.
-// ---------------------------------------------------------------------------
+// Those of the lsap_solve_large_ entries: up to SH_MAX_N_LARGE columns, the
+// sizes first, u and v nullable.
 template <typename T>
 int check_large_solve(const void *C, int nr, int nc, int B, const int32_t *col, const T *du, const T *dv) {
-  const int rc = check_lsap_args(nr, nc, B, col, SH_MAX_N_LARGE);
-  if (rc) return rc;
+  HIP_TRY_RC(check_lsap_args(nr, nc, B, col, SH_MAX_N_LARGE));
   if (!C && B > 0) return fail(SH_ERR_ARGS, "null C");
   if ((du == nullptr) != (dv == nullptr)) return fail(SH_ERR_ARGS, "u and v: both or neither");
   return SH_OK;
 }
 
-// The (NW, K) of a large launch by its column slots, handed to f as a
-// BigCfg<NW, K, 12> tag.  Integer costs take with_big_cfg's table for a batch
-// that fills the chip: four columns per thread up to 2048 columns on 8 waves,
-// 16 waves beyond with three columns where they cover the instance (16 x 2 at
-// 2000 columns: 5 % faster up to 256 instances, equal at 1024; not taken).
+// A solve kernel's duals form is the same kernel with `T *du, T *dv` as a
+// trailing parameter pack.  f(d...) receives (du, dv) when the caller passed
+// them and nothing otherwise, and names its kernel with decltype(d)..., so a
+// launch is written once for both forms.  CAN = false: no duals form exists.
+template <bool CAN = true, typename T, typename F>
+void with_duals(T *du, T *dv, F &&f) {
+  if constexpr (CAN) {
+    if (du) return f(du, dv);
+  }
+  f();
+}
+
+template <int V>
+using int_c = std::integral_constant<int, V>;
+
+// The (NW, K) of a launch beyond SH_MAX_N columns by its column slots, handed
+// to f as a BigCfg<NW, K, 12> tag.  Integer costs take with_big_cfg's table for
+// a batch that fills the chip: four columns per thread up to 2048 columns on 8
+// waves, 16 waves beyond with three columns where they cover the instance (16 x
+// 2 at 2000 columns: 5 % faster up to 256 instances, equal at 1024; not taken).
 // Float costs stay on 8 waves with more columns per thread: every wave folds
 // the NW (value, key, row) slots of a step, and 16 of them cost more than the
 // columns spread over them save (2000 columns, 16 x 2 against 8 x 4: 25 %
@@ -1085,68 +959,231 @@ int with_large_f64_cfg(int nc, F &&f) {
   return f(BigCfg<8, 8, 12>{});
 }
 
-template <typename S>
-int launch_lsap_i64_large(const S *C, int nr, int n, int B, const int32_t *shape, int32_t *col, int64_t *cost,
-                          int64_t *du, int64_t *dv, unsigned flags, hipStream_t s) {
-  const int rc = check_large_solve(C, nr, n, B, col, du, dv);
-  if (rc) return rc;
+// Integer costs: S (int64_t, int32_t) read from C or, with HASH, generated from
+// (seed, mod).  The one launch table of lsap_i64_kernel, for every entry; the
+// entries' checks (above) come first.  The configuration follows the column
+// slots n (a thread owns K of them, as in the square case), the LDS size the
+// rows and columns (lsap_i64_lds).  HASH has neither a duals form nor
+// instances beyond SH_MAX_N columns.
+template <typename S, bool HASH>
+int launch_i64(const S *C, uint64_t seed, int64_t mod, int nr, int n, int B, const int32_t *shape, int32_t *col,
+               int64_t *cost, int64_t *du, int64_t *dv, unsigned flags, hipStream_t s) {
   if (B == 0) return SH_OK;
-  if (n <= SH_MAX_N)
-    return du ? launch_lsap_i64<S, false, true>(C, 0, 1, nr, n, B, shape, col, cost, flags, s, du, dv)
-              : launch_lsap_i64<S, false>(C, 0, 1, nr, n, B, shape, col, cost, flags, s);
-  return with_large_cfg(n, [&](auto cfg) {
+  auto go = [&](auto cfg) {
     using C_ = decltype(cfg);
-    // lsap_i64_kernel's carve-up: u, c4r, r4c, path, red (4 NW words), part (NW words)
-    const size_t lds = r16((size_t)nr * 8) + r16((size_t)nr * 2) + 2 * r16((size_t)n * 2) +
-                       r16((size_t)4 * C_::NW * 8) + r16((size_t)C_::NW * 8);
-    if (du)
-      hipLaunchKernelGGL((lsap_i64_kernel<C_::NW, C_::K, S, false, true, C_::FB, int64_t *, int64_t *>), dim3(B),
-                         dim3(C_::NW * WAVE), lds, s, C, (uint64_t)0, (int64_t)1, nr, n, shape, col, cost,
-                         (int32_t *)nullptr, flags, du, dv);
-    else
-      hipLaunchKernelGGL((lsap_i64_kernel<C_::NW, C_::K, S, false, true, C_::FB>), dim3(B), dim3(C_::NW * WAVE),
-                         lds, s, C, (uint64_t)0, (int64_t)1, nr, n, shape, col, cost, (int32_t *)nullptr, flags);
+    const size_t lds = lsap_i64_lds(nr, n, C_::NW, C_::FB);
+    with_duals<!HASH>(du, dv, [&](auto... d) {
+      auto launch = [&](auto rect) {
+        hipLaunchKernelGGL((lsap_i64_kernel<C_::NW, C_::K, S, HASH, decltype(rect)::value, C_::FB, decltype(d)...>),
+                           dim3(B), dim3(C_::NW * WAVE), lds, s, C, seed, mod, nr, n, shape, col, cost,
+                           (int32_t *)nullptr, flags, d...);
+      };
+      // the square form (RECT = false): the 10-bit key without duals, and no other
+      if constexpr (C_::FB == 10 && sizeof...(d) == 0) {
+        if (nr == n && !shape) return launch(std::false_type{});
+      }
+      launch(std::true_type{});
+    });
     HIP_TRY(hipGetLastError());
-    return (int)SH_OK;
-  });
+    return SH_OK;
+  };
+  if constexpr (!HASH) {
+    if (n > SH_MAX_N) return with_large_cfg(n, go);
+  }
+  // a batch that fills the chip many times over runs one wave per instance
+  // with several columns per thread (fewer waves per block, more blocks per
+  // CU: the large-block kernel's lesson): n <= 128 from 4096 instances
+  // (65536 hash-generated: 1.45 -> 2.49 M solves/s), n = 256 from 65536
+  // (397 -> 443 k/s; at 4096 it lost 17 %); n = 512 gained nothing
+  // (profiles/r02e_lsap_sweep_ab.jsonl)
+  if (n <= WAVE) return go(BigCfg<1, 1, 10>{});
+  if (B >= 4096 && n <= 128) return go(BigCfg<1, 2, 10>{});
+  if (B >= 65536 && n <= 256) return go(BigCfg<1, 4, 10>{});
+  if (n <= 256) return go(BigCfg<4, 1, 10>{});
+  if (n <= 512) return go(BigCfg<4, 2, 10>{});
+  return go(BigCfg<4, 4, 10>{});
 }
 
 template <typename S>
-int launch_lsap_f64_large(const S *C, int nr, int n, int B, const int32_t *shape, int32_t *col, double *cost,
-                          double *du, double *dv, unsigned flags, hipStream_t s) {
-  const int rc = check_large_solve(C, nr, n, B, col, du, dv);
-  if (rc) return rc;
+int solve_i64(const S *C, int nr, int n, int B, const int32_t *shape, int32_t *col, int64_t *cost, int64_t *du,
+              int64_t *dv, unsigned flags, hipStream_t s) {
+  return launch_i64<S, false>(C, 0, 1, nr, n, B, shape, col, cost, du, dv, flags, s);
+}
+
+// Whether a float batch of B instances with nc columns runs four waves per
+// instance by default (measured: DESIGN §7, profiles/lsap_float_ab.jsonl).
+// Up to 1024 instances one wave each leaves SIMDs idle and four waves won at
+// every nc measured (128: 5-9 %, 256: 17-22 %, 512: 29-36 %, 1024: 38-49 %);
+// at 4096 instances one wave each won (nc = 128, 256, 512), and nothing
+// between 1024 and 4096 was measured except nc = 256 (2048: four waves, 5 %),
+// so those batches keep the kernel they always ran.
+bool f64_mw_default(int nc, int B) { return nc > WAVE && B <= 1024; }
+
+int check_f64_flags(unsigned flags, int n) {
   if ((flags & SH_FLAG_F64_MW) && (flags & SH_FLAG_F64_SW))
     return fail(SH_ERR_ARGS, "SH_FLAG_F64_MW and SH_FLAG_F64_SW exclude each other");
   if ((flags & SH_FLAG_F64_SW) && n > SH_MAX_N)
     return fail(SH_ERR_ARGS, "SH_FLAG_F64_SW: no one-wave float kernel above 1024 columns");
-  if (B == 0) return SH_OK;
-  if (n <= SH_MAX_N)
-    return du ? launch_lsap_f64<S, true>(C, nr, n, B, shape, col, cost, flags, s, du, dv)
-              : launch_lsap_f64<S>(C, nr, n, B, shape, col, cost, flags, s);
-  return with_large_f64_cfg(n, [&](auto cfg) {
-    using C_ = decltype(cfg);
-    // lsap_f64_mw_kernel's carve-up: u, rv, rk (key and row: 8 bytes a slot), c4r, r4c, path
-    const size_t lds = r16((size_t)nr * 8) + r16((size_t)2 * C_::NW * 8) + r16((size_t)2 * C_::NW * 8) +
-                       r16((size_t)nr * 2) + 2 * r16((size_t)n * 2);
-    if (du)
-      hipLaunchKernelGGL((lsap_f64_mw_kernel<C_::NW, C_::K, S, C_::FB, double *, double *>), dim3(B),
-                         dim3(C_::NW * WAVE), lds, s, C, nr, n, shape, col, cost, du, dv);
-    else
-      hipLaunchKernelGGL((lsap_f64_mw_kernel<C_::NW, C_::K, S, C_::FB>), dim3(B), dim3(C_::NW * WAVE), lds, s, C,
-                         nr, n, shape, col, cost);
-    HIP_TRY(hipGetLastError());
-    return (int)SH_OK;
-  });
+  return SH_OK;
 }
 
+// A float launch's cost source: the two kernels of a kind of costs and their
+// leading arguments.  Dense costs stored as S (double, float, _Float16,
+// sh_bf16), or CSR (double, float) after lsap_csr_prep_kernel.
+template <typename S>
+struct DenseF64 {
+  const S *C;
+  template <int K, typename... DU>
+  void one_wave(int B, size_t lds, hipStream_t s, int nr, int n, const int32_t *shape, int32_t *col, double *cost,
+                DU... d) const {
+    hipLaunchKernelGGL((lsap_f64_kernel<K, S, DU...>), dim3(B), dim3(WAVE), lds, s, C, nr, n, shape, col, cost, d...);
+  }
+  template <int NW, int K, int FB, typename... DU>
+  void multi_wave(int B, size_t lds, hipStream_t s, int nr, int n, const int32_t *shape, int32_t *col, double *cost,
+                  DU... d) const {
+    hipLaunchKernelGGL((lsap_f64_mw_kernel<NW, K, S, FB, DU...>), dim3(B), dim3(NW * WAVE), lds, s, C, nr, n, shape,
+                       col, cost, d...);
+  }
+};
+
+template <typename S>
+struct CsrF64 {
+  const int64_t *indptr;
+  const S *data;
+  const uint64_t *mask;
+  const uint16_t *pre;
+  template <int K, typename... DU>
+  void one_wave(int B, size_t lds, hipStream_t s, int nr, int n, const int32_t *shape, int32_t *col, double *cost,
+                DU... d) const {
+    hipLaunchKernelGGL((lsap_csr_kernel<K, S, DU...>), dim3(B), dim3(WAVE), lds, s, indptr, data, mask, pre, nr, n,
+                       shape, col, cost, d...);
+  }
+  template <int NW, int K, int FB, typename... DU>
+  void multi_wave(int B, size_t lds, hipStream_t s, int nr, int n, const int32_t *shape, int32_t *col, double *cost,
+                  DU... d) const {
+    hipLaunchKernelGGL((lsap_csr_mw_kernel<NW, K, S, FB, DU...>), dim3(B), dim3(NW * WAVE), lds, s, indptr, data, mask,
+                       pre, nr, n, shape, col, cost, d...);
+  }
+};
+
+// Floating-point costs, solved in float64: the one launch table of the float
+// kernels, for every entry and both sources; the entries' checks (above) come
+// first.  One wave per instance (lsap_f64_lds) or, for n > 64, four (1 / 2 / 4
+// columns per thread as the integer path's; lsap_f64_mw_lds): the default is
+// f64_mw_default, SH_FLAG_F64_MW / SH_FLAG_F64_SW force one.  Beyond SH_MAX_N
+// columns with_large_f64_cfg's eight waves.
+template <typename Src>
+int launch_f64(const Src &src, int nr, int n, int B, const int32_t *shape, int32_t *col, double *cost, double *du,
+               double *dv, unsigned flags, hipStream_t s) {
+  HIP_TRY_RC(check_f64_flags(flags, n));
+  if (B == 0) return SH_OK;
+  with_duals(du, dv, [&](auto... d) {
+    auto mw = [&](auto cfg) {
+      using C_ = decltype(cfg);
+      src.template multi_wave<C_::NW, C_::K, C_::FB>(B, lsap_f64_mw_lds(nr, n, C_::NW, C_::FB), s, nr, n, shape,
+                                                     col, cost, d...);
+      return SH_OK;
+    };
+    auto sw = [&](auto k) {
+      src.template one_wave<decltype(k)::value>(B, lsap_f64_lds(nr), s, nr, n, shape, col, cost, d...);
+    };
+    if (n > SH_MAX_N) {
+      with_large_f64_cfg(n, mw);
+    } else if (n > WAVE && !(flags & SH_FLAG_F64_SW) && ((flags & SH_FLAG_F64_MW) || f64_mw_default(n, B))) {
+      if (n <= 256) mw(BigCfg<4, 1, 10>{});
+      else if (n <= 512) mw(BigCfg<4, 2, 10>{});
+      else mw(BigCfg<4, 4, 10>{});
+    } else {
+      switch (pick_k(n)) {
+        case 1: sw(int_c<1>{}); break;
+        case 2: sw(int_c<2>{}); break;
+        case 4: sw(int_c<4>{}); break;
+        case 8: sw(int_c<8>{}); break;
+        default: sw(int_c<16>{}); break;
+      }
+    }
+  });
+  HIP_TRY(hipGetLastError());
+  return SH_OK;
+}
+
+template <typename S>
+int solve_f64(const S *C, int nr, int n, int B, const int32_t *shape, int32_t *col, double *cost, double *du,
+              double *dv, unsigned flags, hipStream_t s) {
+  return launch_f64(DenseF64<S>{C}, nr, n, B, shape, col, cost, du, dv, flags, s);
+}
+
+// The LDS bytes the launches above request, at the seams of their tables: the
+// figures of the hand-written sums these launchers held before the layouts
+// were shared with the kernels (tests/test_lsap_lds_layout_cpu.py).
+static_assert(lsap_i64_lds(1, 1, 1, 10) == 256 && lsap_i64_lds(1, 1, 4, 10) == 256);
+static_assert(lsap_i64_lds(64, 64, 1, 10) == 1088 && lsap_i64_lds(64, 64, 4, 10) == 1088);
+static_assert(lsap_i64_lds(65, 65, 1, 10) == 1152 && lsap_i64_lds(65, 65, 4, 10) == 1152);
+static_assert(lsap_i64_lds(256, 256, 1, 10) == 3776 && lsap_i64_lds(256, 256, 4, 10) == 3776);
+static_assert(lsap_i64_lds(257, 257, 1, 10) == 3840 && lsap_i64_lds(257, 257, 4, 10) == 3840);
+static_assert(lsap_i64_lds(512, 512, 1, 10) == 7360 && lsap_i64_lds(512, 512, 4, 10) == 7360);
+static_assert(lsap_i64_lds(513, 513, 1, 10) == 7424 && lsap_i64_lds(513, 513, 4, 10) == 7424);
+static_assert(lsap_i64_lds(1024, 1024, 1, 10) == 14528 && lsap_i64_lds(1024, 1024, 4, 10) == 14528);
+static_assert(lsap_i64_lds(1, 1024, 4, 10) == 4320);
+static_assert(lsap_i64_lds(1025, 1025, 8, 12) == 14720);
+static_assert(lsap_i64_lds(2048, 2048, 8, 12) == 28992);
+static_assert(lsap_i64_lds(2049, 2049, 16, 12) == 29376);
+static_assert(lsap_i64_lds(3072, 3072, 16, 12) == 43648);
+static_assert(lsap_i64_lds(3073, 3073, 16, 12) == 43712);
+static_assert(lsap_i64_lds(4096, 4096, 16, 12) == 57984);
+static_assert(lsap_i64_lds(1, 4096, 16, 12) == 17056);
+static_assert(lsap_f64_lds(1) == 32 && lsap_f64_mw_lds(1, 1, 4, 10) == 160);
+static_assert(lsap_f64_lds(64) == 640 && lsap_f64_mw_lds(64, 64, 4, 10) == 992);
+static_assert(lsap_f64_lds(65) == 672 && lsap_f64_mw_lds(65, 65, 4, 10) == 1056);
+static_assert(lsap_f64_lds(256) == 2560 && lsap_f64_mw_lds(256, 256, 4, 10) == 3680);
+static_assert(lsap_f64_lds(257) == 2592 && lsap_f64_mw_lds(257, 257, 4, 10) == 3744);
+static_assert(lsap_f64_lds(512) == 5120 && lsap_f64_mw_lds(512, 512, 4, 10) == 7264);
+static_assert(lsap_f64_lds(513) == 5152 && lsap_f64_mw_lds(513, 513, 4, 10) == 7328);
+static_assert(lsap_f64_lds(1024) == 10240 && lsap_f64_mw_lds(1024, 1024, 4, 10) == 14432);
+static_assert(lsap_f64_lds(1) == 32 && lsap_f64_mw_lds(1, 1024, 4, 10) == 4224);
+static_assert(lsap_f64_mw_lds(1025, 1025, 8, 12) == 14656);
+static_assert(lsap_f64_mw_lds(2048, 2048, 8, 12) == 28928);
+static_assert(lsap_f64_mw_lds(2049, 2049, 8, 12) == 28992);
+static_assert(lsap_f64_mw_lds(3072, 3072, 8, 12) == 43264);
+static_assert(lsap_f64_mw_lds(3073, 3073, 8, 12) == 43328);
+static_assert(lsap_f64_mw_lds(4096, 4096, 8, 12) == 57600);
+static_assert(lsap_f64_mw_lds(1, 4096, 8, 12) == 16672);
+
+// The certificate (lsap_cert_kernel, lsap_slack_kernel, lsap_cert_final_kernel):
+// S the stored cost type, T int64_t or double.  The pass over the corners
+// reads 16 bytes per load when every row starts 16-byte aligned; a batch too
+// small to fill the chip with one workgroup per instance is split by rows.
+// cap: the entry's limit, SH_MAX_N or SH_MAX_N_LARGE.  The kernels' column
+// capacity NCAP is SH_MAX_N up to that many columns whatever the entry (the
+// same kernels, the same bits), SH_MAX_N_LARGE beyond.
 template <typename S, typename T>
-int launch_lsap_check_large(const S *C, int nr, int n, int B, const int32_t *shape, const int32_t *col,
-                            const T *u, const T *v, T *slack, int32_t *flg, hipStream_t s) {
-  const int rc = check_lsap_args(nr, n, B, col, SH_MAX_N_LARGE);
-  if (rc) return rc;
-  if (n <= SH_MAX_N) return launch_lsap_check<S, T>(C, nr, n, B, shape, col, u, v, slack, flg, s);
-  return launch_lsap_check<S, T, SH_MAX_N_LARGE>(C, nr, n, B, shape, col, u, v, slack, flg, s);
+int launch_lsap_check(const S *C, int nr, int n, int B, int cap, const int32_t *shape, const int32_t *col,
+                      const T *u, const T *v, T *slack, int32_t *flg, hipStream_t s) {
+  HIP_TRY_RC(check_lsap_args(nr, n, B, col, cap));
+  if (B > 0 && (!C || !u || !v || !slack || !flg)) return fail(SH_ERR_ARGS, "null C, u, v, slack or flags");
+  if (B == 0) return SH_OK;
+  auto go = [&](auto ncap) {
+    constexpr int NCAP = decltype(ncap)::value;
+    hipLaunchKernelGGL((lsap_cert_kernel<S, T, NCAP>), dim3(B), dim3(CERT_WG), 0, s, C, nr, n, shape, col, u, v,
+                       slack, flg);
+    // at least 8 rows per workgroup, about 2048 workgroups when the batch allows
+    const int chunks = std::min(std::max(1, 2048 / B), (nr + 7) / 8);
+    const int rows_per = (nr + chunks - 1) / chunks;
+    const dim3 grid(B, (nr + rows_per - 1) / rows_per);
+    constexpr int VEC = 16 / (int)sizeof(S);
+    if ((uintptr_t)C % 16 == 0 && n % VEC == 0)
+      hipLaunchKernelGGL((lsap_slack_kernel<S, T, VEC, NCAP>), grid, dim3(CERT_WG), 0, s, C, nr, n, shape, u, v,
+                         slack, flg, rows_per);
+    else
+      hipLaunchKernelGGL((lsap_slack_kernel<S, T, 1, NCAP>), grid, dim3(CERT_WG), 0, s, C, nr, n, shape, u, v,
+                         slack, flg, rows_per);
+  };
+  if (n <= SH_MAX_N) go(int_c<SH_MAX_N>{});
+  else go(int_c<SH_MAX_N_LARGE>{});
+  hipLaunchKernelGGL((lsap_cert_final_kernel<T>), dim3((B + CERT_WG - 1) / CERT_WG), dim3(CERT_WG), 0, s,
+                     B, slack, flg);
+  HIP_TRY(hipGetLastError());
+  return SH_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -1156,20 +1193,16 @@ int launch_lsap_check_large(const S *C, int nr, int n, int B, const int32_t *sha
 // ---------------------------------------------------------------------------
 size_t csr_words(int nr, int nc, int B) { return (size_t)B * (size_t)nr * (size_t)((nc + 63) / 64); }
 
-// Two launches on the stream: the prep, then the launch table of
-// launch_lsap_f64 and launch_lsap_f64_large with the CSR kernels.
+// Two launches on the stream: the prep, then launch_f64's table with the CSR
+// kernels.  Every check, launch_f64's among them, precedes the first launch.
 template <typename S>
 int launch_lsap_csr(const int64_t *indptr, const int32_t *indices, const S *data, int nr, int n, int B,
                     const int32_t *shape, int32_t *col, double *cost, double *du, double *dv, void *work,
                     size_t work_bytes, unsigned flags, hipStream_t s) {
-  const int rc = check_lsap_args(nr, n, B, col, SH_MAX_N_LARGE);
-  if (rc) return rc;
+  HIP_TRY_RC(check_lsap_args(nr, n, B, col, SH_MAX_N_LARGE));
   if (!indptr && B > 0) return fail(SH_ERR_ARGS, "null indptr");
   if ((du == nullptr) != (dv == nullptr)) return fail(SH_ERR_ARGS, "u and v: both or neither");
-  if ((flags & SH_FLAG_F64_MW) && (flags & SH_FLAG_F64_SW))
-    return fail(SH_ERR_ARGS, "SH_FLAG_F64_MW and SH_FLAG_F64_SW exclude each other");
-  if ((flags & SH_FLAG_F64_SW) && n > SH_MAX_N)
-    return fail(SH_ERR_ARGS, "SH_FLAG_F64_SW: no one-wave float kernel above 1024 columns");
+  HIP_TRY_RC(check_f64_flags(flags, n));
   if (work_bytes < lsap_csr_work_bytes(nr, n, B) || (B > 0 && !work))
     return fail(SH_ERR_ARGS, "work buffer smaller than lsap_csr_work_bytes");
   if ((uintptr_t)work % 8) return fail(SH_ERR_ARGS, "work buffer not 8-byte aligned");
@@ -1185,81 +1218,67 @@ int launch_lsap_csr(const int64_t *indptr, const int32_t *indices, const S *data
     HIP_TRY(hipGetLastError());
     return SH_OK;
   }
-#define MW_(NWW, KK, FBB)                                                                                    \
-  do {                                                                                                       \
-    if (du)                                                                                                  \
-      hipLaunchKernelGGL((lsap_csr_mw_kernel<NWW, KK, S, FBB, double *, double *>), dim3(B), dim3(NWW * WAVE), \
-                         lds, s, indptr, data, mask, pre, nr, n, shape, col, cost, du, dv);                  \
-    else                                                                                                     \
-      hipLaunchKernelGGL((lsap_csr_mw_kernel<NWW, KK, S, FBB>), dim3(B), dim3(NWW * WAVE), lds, s, indptr,   \
-                         data, mask, pre, nr, n, shape, col, cost);                                          \
-  } while (0)
-  if (n > SH_MAX_N) {
-    HIP_TRY_RC(with_large_f64_cfg(n, [&](auto cfg) {
-      using C_ = decltype(cfg);
-      // lsap_csr_mw_kernel's carve-up is lsap_f64_mw_kernel's (launch_lsap_f64_large)
-      const size_t lds = r16((size_t)nr * 8) + r16((size_t)2 * C_::NW * 8) + r16((size_t)2 * C_::NW * 8) +
-                         r16((size_t)nr * 2) + 2 * r16((size_t)n * 2);
-      MW_(C_::NW, C_::K, C_::FB);
-      return (int)SH_OK;
-    }));
-  } else if (n > WAVE && !(flags & SH_FLAG_F64_SW) && ((flags & SH_FLAG_F64_MW) || f64_mw_default(n, B))) {
-    constexpr int NW = 4;
-    const size_t lds = r16((size_t)nr * 8) + r16((size_t)2 * NW * 8) + r16((size_t)2 * NW * 4) +
-                       r16((size_t)nr * 2) + 2 * r16((size_t)n * 2);
-    if (n <= 256) MW_(NW, 1, 10);
-    else if (n <= 512) MW_(NW, 2, 10);
-    else MW_(NW, 4, 10);
-  } else {
-    const size_t lds = r16((size_t)nr * 8) + r16((size_t)nr * 2);
-#define L_(KK)                                                                                            \
-  do {                                                                                                    \
-    if (du)                                                                                               \
-      hipLaunchKernelGGL((lsap_csr_kernel<KK, S, double *, double *>), dim3(B), dim3(WAVE), lds, s,       \
-                         indptr, data, mask, pre, nr, n, shape, col, cost, du, dv);                       \
-    else                                                                                                  \
-      hipLaunchKernelGGL((lsap_csr_kernel<KK, S>), dim3(B), dim3(WAVE), lds, s, indptr, data, mask, pre,  \
-                         nr, n, shape, col, cost);                                                        \
-  } while (0)
-    switch (pick_k(n)) {
-      case 1: L_(1); break;
-      case 2: L_(2); break;
-      case 4: L_(4); break;
-      case 8: L_(8); break;
-      default: L_(16); break;
-    }
-#undef L_
-  }
-#undef MW_
-  HIP_TRY(hipGetLastError());
-  return SH_OK;
+  return launch_f64(CsrF64<S>{indptr, data, mask, pre}, nr, n, B, shape, col, cost, du, dv, flags, s);
 }
 }  // namespace
 
 extern "C" {
 
-#define SH_LARGE_ENTRIES(SUF, CT, KT, T, SOLVE)                                                                 \
+// The five entries of a dense cost type: CT its C-ABI type, KT the kernels'
+// element type, T the type of costs and duals, SOLVE solve_i64 or solve_f64.
+// nr x nc instances, nr <= nc (the square entries below: nr == nc, no
+// shapes).  Every check is on the host and precedes the first device call.
+// The _rect_ and _duals_ entries go up to SH_MAX_N columns; the _large_ ones
+// up to SH_MAX_N_LARGE, with the same kernels and bits up to SH_MAX_N and the
+// FB = 12 instantiations beyond.
+#define SH_LSAP_ENTRIES(SUF, CT, KT, T, SOLVE)                                                                  \
+  int lsap_solve_batched_rect_##SUF(const CT *d_C, int nr, int nc, int B, const int32_t *d_shape,               \
+                                    int32_t *d_col, T *d_cost, unsigned flags, void *stream) {                  \
+    HIP_TRY_RC(check_solve<T>(d_C, nr, nc, B, d_col, false, nullptr, nullptr));                                 \
+    return SOLVE((const KT *)d_C, nr, nc, B, d_shape, d_col, d_cost, (T *)nullptr, (T *)nullptr, flags,         \
+                 (hipStream_t)stream);                                                                          \
+  }                                                                                                             \
+  int lsap_solve_batched_duals_##SUF(const CT *d_C, int nr, int nc, int B, const int32_t *d_shape,              \
+                                     int32_t *d_col, T *d_cost, T *d_u, T *d_v, unsigned flags, void *stream) { \
+    HIP_TRY_RC(check_solve<T>(d_C, nr, nc, B, d_col, true, d_u, d_v));                                          \
+    return SOLVE((const KT *)d_C, nr, nc, B, d_shape, d_col, d_cost, d_u, d_v, flags, (hipStream_t)stream);     \
+  }                                                                                                             \
   int lsap_solve_large_##SUF(const CT *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,      \
                              T *d_cost, T *d_u, T *d_v, unsigned flags, void *stream) {                         \
+    HIP_TRY_RC(check_large_solve<T>(d_C, nr, nc, B, d_col, d_u, d_v));                                          \
     return SOLVE((const KT *)d_C, nr, nc, B, d_shape, d_col, d_cost, d_u, d_v, flags, (hipStream_t)stream);     \
+  }                                                                                                             \
+  int lsap_check_duals_##SUF(const CT *d_C, int nr, int nc, int B, const int32_t *d_shape,                      \
+                             const int32_t *d_col, const T *d_u, const T *d_v, T *d_slack, int32_t *d_flags,    \
+                             void *stream) {                                                                    \
+    return launch_lsap_check((const KT *)d_C, nr, nc, B, SH_MAX_N, d_shape, d_col, d_u, d_v, d_slack, d_flags,  \
+                             (hipStream_t)stream);                                                              \
   }                                                                                                             \
   int lsap_check_duals_large_##SUF(const CT *d_C, int nr, int nc, int B, const int32_t *d_shape,                \
                                    const int32_t *d_col, const T *d_u, const T *d_v, T *d_slack,                \
                                    int32_t *d_flags, void *stream) {                                            \
-    return launch_lsap_check_large((const KT *)d_C, nr, nc, B, d_shape, d_col, d_u, d_v, d_slack, d_flags,      \
-                                   (hipStream_t)stream);                                                        \
+    return launch_lsap_check((const KT *)d_C, nr, nc, B, SH_MAX_N_LARGE, d_shape, d_col, d_u, d_v, d_slack,     \
+                             d_flags, (hipStream_t)stream);                                                     \
   }
-SH_LARGE_ENTRIES(i64, int64_t, int64_t, int64_t, launch_lsap_i64_large)
-SH_LARGE_ENTRIES(i32, int32_t, int32_t, int64_t, launch_lsap_i64_large)
-SH_LARGE_ENTRIES(f64, double, double, double, launch_lsap_f64_large)
-SH_LARGE_ENTRIES(f32, float, float, double, launch_lsap_f64_large)
-SH_LARGE_ENTRIES(f16, uint16_t, _Float16, double, launch_lsap_f64_large)
-SH_LARGE_ENTRIES(bf16, uint16_t, sh_bf16, double, launch_lsap_f64_large)
-#undef SH_LARGE_ENTRIES
+SH_LSAP_ENTRIES(i64, int64_t, int64_t, int64_t, solve_i64)
+SH_LSAP_ENTRIES(i32, int32_t, int32_t, int64_t, solve_i64)
+SH_LSAP_ENTRIES(f64, double, double, double, solve_f64)
+SH_LSAP_ENTRIES(f32, float, float, double, solve_f64)
+SH_LSAP_ENTRIES(f16, uint16_t, _Float16, double, solve_f64)
+SH_LSAP_ENTRIES(bf16, uint16_t, sh_bf16, double, solve_f64)
+#undef SH_LSAP_ENTRIES
+
+int lsap_solve_batched_rect_hash(uint64_t seed, int64_t modulus, int nr, int nc, int B,
+                                 int32_t *d_col, int64_t *d_cost, unsigned flags, void *stream) {
+  if (modulus <= 0) return fail(SH_ERR_ARGS, "modulus must be > 0");
+  HIP_TRY_RC(check_lsap_args(nr, nc, B, d_col, SH_MAX_N));
+  return launch_i64<int64_t, true>(nullptr, seed, modulus, nr, nc, B, nullptr, d_col, d_cost, nullptr, nullptr,
+                                   flags, (hipStream_t)stream);
+}
 
 size_t lsap_csr_work_bytes(int nr, int nc, int B) {
   if (nr < 1 || nc < 1 || B < 1) return 0;
-  return r16(csr_words(nr, nc, B) * (sizeof(uint64_t) + sizeof(uint16_t)));
+  return (csr_words(nr, nc, B) * (sizeof(uint64_t) + sizeof(uint16_t)) + 15) / 16 * 16;
 }
 
 int lsap_solve_csr_f64(const int64_t *d_indptr, const int32_t *d_indices, const double *d_data, int nr, int nc,
@@ -1276,6 +1295,7 @@ int lsap_solve_csr_f32(const int64_t *d_indptr, const int32_t *d_indices, const 
                          work_bytes, flags, (hipStream_t)stream);
 }
 
+// The square entries: nr == nc == n, no shapes.
 int lsap_solve_batched_i64(const int64_t *d_C, int n, int B, int32_t *d_col, int64_t *d_cost,
                            unsigned flags, void *stream) {
   return lsap_solve_batched_rect_i64(d_C, n, n, B, nullptr, d_col, d_cost, flags, stream);
@@ -1296,132 +1316,5 @@ int lsap_solve_batched_hash(uint64_t seed, int64_t modulus, int n, int B, int32_
   return lsap_solve_batched_rect_hash(seed, modulus, n, n, B, d_col, d_cost, flags, stream);
 }
 
-// nr x nc instances, nr <= nc (the square entries above: nr == nc, no shapes).
-// Every check here is on the host and precedes the first device call.
-int lsap_solve_batched_rect_i64(const int64_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
-                                int32_t *d_col, int64_t *d_cost, unsigned flags, void *stream) {
-  if (!d_C && B > 0) return fail(SH_ERR_ARGS, "null C");
-  return launch_lsap_i64<int64_t, false>(d_C, 0, 1, nr, nc, B, d_shape, d_col, d_cost, flags,
-                                         (hipStream_t)stream);
-}
-
-int lsap_solve_batched_rect_i32(const int32_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
-                                int32_t *d_col, int64_t *d_cost, unsigned flags, void *stream) {
-  if (!d_C && B > 0) return fail(SH_ERR_ARGS, "null C");
-  return launch_lsap_i64<int32_t, false>(d_C, 0, 1, nr, nc, B, d_shape, d_col, d_cost, flags,
-                                         (hipStream_t)stream);
-}
-
-int lsap_solve_batched_rect_f64(const double *d_C, int nr, int nc, int B, const int32_t *d_shape,
-                                int32_t *d_col, double *d_cost, unsigned flags, void *stream) {
-  return launch_lsap_f64(d_C, nr, nc, B, d_shape, d_col, d_cost, flags, (hipStream_t)stream);
-}
-
-int lsap_solve_batched_rect_f32(const float *d_C, int nr, int nc, int B, const int32_t *d_shape,
-                                int32_t *d_col, double *d_cost, unsigned flags, void *stream) {
-  return launch_lsap_f64(d_C, nr, nc, B, d_shape, d_col, d_cost, flags, (hipStream_t)stream);
-}
-
-int lsap_solve_batched_rect_f16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
-                                int32_t *d_col, double *d_cost, unsigned flags, void *stream) {
-  return launch_lsap_f64((const _Float16 *)d_C, nr, nc, B, d_shape, d_col, d_cost, flags,
-                         (hipStream_t)stream);
-}
-
-int lsap_solve_batched_rect_bf16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
-                                 int32_t *d_col, double *d_cost, unsigned flags, void *stream) {
-  return launch_lsap_f64((const sh_bf16 *)d_C, nr, nc, B, d_shape, d_col, d_cost, flags,
-                         (hipStream_t)stream);
-}
-
-int lsap_solve_batched_rect_hash(uint64_t seed, int64_t modulus, int nr, int nc, int B,
-                                 int32_t *d_col, int64_t *d_cost, unsigned flags, void *stream) {
-  if (modulus <= 0) return fail(SH_ERR_ARGS, "modulus must be > 0");
-  return launch_lsap_i64<int64_t, true>(nullptr, seed, modulus, nr, nc, B, nullptr, d_col, d_cost,
-                                        flags, (hipStream_t)stream);
-}
-
-// The duals forms of the six entries above (the same checks and launches).
-int lsap_solve_batched_duals_i64(const int64_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
-                                 int32_t *d_col, int64_t *d_cost, int64_t *d_u, int64_t *d_v,
-                                 unsigned flags, void *stream) {
-  if (!d_C && B > 0) return fail(SH_ERR_ARGS, "null C");
-  return launch_lsap_i64<int64_t, false, true>(d_C, 0, 1, nr, nc, B, d_shape, d_col, d_cost, flags,
-                                               (hipStream_t)stream, d_u, d_v);
-}
-
-int lsap_solve_batched_duals_i32(const int32_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
-                                 int32_t *d_col, int64_t *d_cost, int64_t *d_u, int64_t *d_v,
-                                 unsigned flags, void *stream) {
-  if (!d_C && B > 0) return fail(SH_ERR_ARGS, "null C");
-  return launch_lsap_i64<int32_t, false, true>(d_C, 0, 1, nr, nc, B, d_shape, d_col, d_cost, flags,
-                                               (hipStream_t)stream, d_u, d_v);
-}
-
-int lsap_solve_batched_duals_f64(const double *d_C, int nr, int nc, int B, const int32_t *d_shape,
-                                 int32_t *d_col, double *d_cost, double *d_u, double *d_v,
-                                 unsigned flags, void *stream) {
-  return launch_lsap_f64<double, true>(d_C, nr, nc, B, d_shape, d_col, d_cost, flags, (hipStream_t)stream,
-                                       d_u, d_v);
-}
-
-int lsap_solve_batched_duals_f32(const float *d_C, int nr, int nc, int B, const int32_t *d_shape,
-                                 int32_t *d_col, double *d_cost, double *d_u, double *d_v,
-                                 unsigned flags, void *stream) {
-  return launch_lsap_f64<float, true>(d_C, nr, nc, B, d_shape, d_col, d_cost, flags, (hipStream_t)stream,
-                                      d_u, d_v);
-}
-
-int lsap_solve_batched_duals_f16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
-                                 int32_t *d_col, double *d_cost, double *d_u, double *d_v,
-                                 unsigned flags, void *stream) {
-  return launch_lsap_f64<_Float16, true>((const _Float16 *)d_C, nr, nc, B, d_shape, d_col, d_cost, flags,
-                                         (hipStream_t)stream, d_u, d_v);
-}
-
-int lsap_solve_batched_duals_bf16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
-                                  int32_t *d_col, double *d_cost, double *d_u, double *d_v,
-                                  unsigned flags, void *stream) {
-  return launch_lsap_f64<sh_bf16, true>((const sh_bf16 *)d_C, nr, nc, B, d_shape, d_col, d_cost, flags,
-                                        (hipStream_t)stream, d_u, d_v);
-}
-
-int lsap_check_duals_i64(const int64_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
-                         const int32_t *d_col, const int64_t *d_u, const int64_t *d_v,
-                         int64_t *d_slack, int32_t *d_flags, void *stream) {
-  return launch_lsap_check(d_C, nr, nc, B, d_shape, d_col, d_u, d_v, d_slack, d_flags, (hipStream_t)stream);
-}
-
-int lsap_check_duals_i32(const int32_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
-                         const int32_t *d_col, const int64_t *d_u, const int64_t *d_v,
-                         int64_t *d_slack, int32_t *d_flags, void *stream) {
-  return launch_lsap_check(d_C, nr, nc, B, d_shape, d_col, d_u, d_v, d_slack, d_flags, (hipStream_t)stream);
-}
-
-int lsap_check_duals_f64(const double *d_C, int nr, int nc, int B, const int32_t *d_shape,
-                         const int32_t *d_col, const double *d_u, const double *d_v,
-                         double *d_slack, int32_t *d_flags, void *stream) {
-  return launch_lsap_check(d_C, nr, nc, B, d_shape, d_col, d_u, d_v, d_slack, d_flags, (hipStream_t)stream);
-}
-
-int lsap_check_duals_f32(const float *d_C, int nr, int nc, int B, const int32_t *d_shape,
-                         const int32_t *d_col, const double *d_u, const double *d_v,
-                         double *d_slack, int32_t *d_flags, void *stream) {
-  return launch_lsap_check(d_C, nr, nc, B, d_shape, d_col, d_u, d_v, d_slack, d_flags, (hipStream_t)stream);
-}
-
-int lsap_check_duals_f16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
-                         const int32_t *d_col, const double *d_u, const double *d_v,
-                         double *d_slack, int32_t *d_flags, void *stream) {
-  return launch_lsap_check((const _Float16 *)d_C, nr, nc, B, d_shape, d_col, d_u, d_v, d_slack, d_flags,
-                           (hipStream_t)stream);
-}
-
-int lsap_check_duals_bf16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape,
-                          const int32_t *d_col, const double *d_u, const double *d_v,
-                          double *d_slack, int32_t *d_flags, void *stream) {
-  return launch_lsap_check((const sh_bf16 *)d_C, nr, nc, B, d_shape, d_col, d_u, d_v, d_slack, d_flags,
-                           (hipStream_t)stream);
-}
-
 }  // extern "C"
+

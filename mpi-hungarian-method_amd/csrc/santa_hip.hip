@@ -1512,7 +1512,7 @@ __device__ __forceinline__ void block_sums_store(const SantaArgs &a, const int b
   store_outputs(a, b, tc, td0, td1, steps, fallbacks);
 }
 
-__host__ __device__ __forceinline__ size_t r16(size_t x) { return (x + 15) & ~(size_t)15; }
+__host__ __device__ __forceinline__ constexpr size_t r16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 constexpr int SANTA_NW = 4;
 constexpr int SANTA_WG = SANTA_NW * WAVE;
@@ -5555,6 +5555,52 @@ __device__ __forceinline__ void duals_store_f64(double *du, double *dv, const do
   duals_fill<double, WG>(du, dv, b, NR, NC, nr, n, 0.0);
 }
 
+// The dynamic LDS of the LSAP solve kernels, one list per design: X(pointer,
+// element type, bytes) for each region in carve order.  A kernel expands its
+// list with LDS_CARVE at the live (nr, n); its launcher asks the constexpr
+// function under the list, the same list summed, for the bytes at the padded
+// (nr, n).  So the two cannot drift.  (A request that is too small does not
+// fault: it returns wrong assignments at the largest shapes.  The
+// static_asserts beside the launchers pin the bytes.)
+// Lists, and not a function that returns offsets as big_lds_layout does,
+// because LDS_CARVE expands to the statements these kernels always had.  Every
+// function tried (a struct of offsets, of pointers from a base, one accessor a
+// region) moved the kernels' address arithmetic and changed the instruction
+// stream of 11 to 132 of the 231 LSAP kernels.
+#define LDS_CARVE(ptr, T, bytes) ptr = (T *)(smem + off); off += r16(bytes);
+#define LDS_BYTES(ptr, T, bytes) +r16(bytes)
+
+#define LSAP_I64_LDS(X, nr, n, nw)                                 \
+  X(Sl.u, int64_t, (size_t)nr * 8)                                 \
+  X(Sl.c4r, int16_t, (size_t)nr * 2)                               \
+  X(Sl.r4c, int16_t, (size_t)n * 2)                                \
+  X(Sl.path, int16_t, (size_t)n * 2)                               \
+  X(Sl.red, uint64_t, (size_t)4 * nw * 8) /* (SolveLds::red) */    \
+  X(part, int64_t, (size_t)nw * 8)        /* the waves' cost partials */
+// The 10-bit-key launches (one and four waves) have always requested the
+// bytes of four waves whatever nw, and 32 beyond them: more than the kernel
+// uses.  Kept to the byte, because a smaller request can change how many
+// blocks share a CU and that has not been measured.
+__host__ __device__ constexpr size_t lsap_i64_lds(int nr, int n, int nw, int fb) {
+  return fb == 10 ? 0 LSAP_I64_LDS(LDS_BYTES, nr, n, 4) + 32 : 0 LSAP_I64_LDS(LDS_BYTES, nr, n, nw);
+}
+
+#define LSAP_F64_LDS(X, nr)       \
+  X(u_l, double, (size_t)nr * 8)  \
+  X(c4r_l, int16_t, (size_t)nr * 2)
+__host__ __device__ constexpr size_t lsap_f64_lds(int nr) { return 0 LSAP_F64_LDS(LDS_BYTES, nr); }
+
+#define LSAP_F64_MW_LDS(X, nr, n, nw, fb)                                                       \
+  X(Sl.u, double, (size_t)nr * 8)                                                               \
+  X(Sl.rv, double, (size_t)2 * nw * 8)                                                          \
+  X(Sl.rk, uint32_t, (size_t)2 * nw * (fb > 10 ? 8 : 4)) /* (FB > 10: key and row4col a slot) */ \
+  X(Sl.c4r, int16_t, (size_t)nr * 2)                                                            \
+  X(Sl.r4c, int16_t, (size_t)n * 2)                                                             \
+  X(Sl.path, int16_t, (size_t)n * 2)
+__host__ __device__ constexpr size_t lsap_f64_mw_lds(int nr, int n, int nw, int fb) {
+  return 0 LSAP_F64_MW_LDS(LDS_BYTES, nr, n, nw, fb);
+}
+
 // FB: the width of the packed key's position and row / column fields (see
 // sap_solve_mw): 10 up to 1024 columns, 12 up to 4096.
 template <int NW, int K, typename S, bool HASH, bool RECT, int FB = 10, typename... DU>
@@ -5577,12 +5623,8 @@ __global__ __launch_bounds__(NW * WAVE) void lsap_i64_kernel(const S *C, uint64_
   }
   size_t off = 0;
   SolveLds Sl;
-  Sl.u = (int64_t *)(smem + off);    off += r16((size_t)nr * 8);
-  Sl.c4r = (int16_t *)(smem + off);  off += r16((size_t)nr * 2);
-  Sl.r4c = (int16_t *)(smem + off);  off += r16((size_t)n * 2);
-  Sl.path = (int16_t *)(smem + off); off += r16((size_t)n * 2);
-  Sl.red = (uint64_t *)(smem + off); off += r16((size_t)4 * NW * 8);
-  int64_t *part = (int64_t *)(smem + off);
+  int64_t *part;
+  LSAP_I64_LDS(LDS_CARVE, nr, n, NW)
   for (int i = tid; i < n; i += NW * WAVE) {
     if (i < nr) {
       Sl.u[i] = 0;
@@ -5649,8 +5691,10 @@ __global__ __launch_bounds__(WAVE) void lsap_f64_kernel(const S *C, int NR, int 
     lsap_no_instance<WAVE>(col, cost, b, NR, NC, duals...);
     return;
   }
-  double *u_l = (double *)smem;
-  int16_t *c4r_l = (int16_t *)(smem + r16((size_t)nr * sizeof(double)));
+  size_t off = 0;
+  double *u_l;
+  int16_t *c4r_l;
+  LSAP_F64_LDS(LDS_CARVE, nr)
   for (int i = lane; i < nr; i += WAVE) {
     u_l[i] = 0;
     c4r_l[i] = -1;
@@ -5700,12 +5744,7 @@ __global__ __launch_bounds__(NW * WAVE) void lsap_f64_mw_kernel(const S *C, int 
   }
   size_t off = 0;
   SolveLdsF64 Sl;
-  Sl.u = (double *)(smem + off);      off += r16((size_t)nr * 8);
-  Sl.rv = (double *)(smem + off);     off += r16((size_t)2 * NW * 8);
-  Sl.rk = (uint32_t *)(smem + off);   off += r16((size_t)2 * NW * (FB > 10 ? 8 : 4));
-  Sl.c4r = (int16_t *)(smem + off);   off += r16((size_t)nr * 2);
-  Sl.r4c = (int16_t *)(smem + off);   off += r16((size_t)n * 2);
-  Sl.path = (int16_t *)(smem + off);
+  LSAP_F64_MW_LDS(LDS_CARVE, nr, n, NW, FB)
   for (int i = tid; i < n; i += WG) {
     if (i < nr) {
       Sl.u[i] = 0;
@@ -5865,8 +5904,10 @@ __global__ __launch_bounds__(WAVE) void lsap_csr_kernel(const int64_t *indptr, c
     lsap_no_instance<WAVE>(col, cost, b, NR, NC, duals...);
     return;
   }
-  double *u_l = (double *)smem;
-  int16_t *c4r_l = (int16_t *)(smem + r16((size_t)nr * sizeof(double)));
+  size_t off = 0;
+  double *u_l;
+  int16_t *c4r_l;
+  LSAP_F64_LDS(LDS_CARVE, nr)
   for (int i = lane; i < nr; i += WAVE) {
     u_l[i] = 0;
     c4r_l[i] = -1;
@@ -5915,12 +5956,7 @@ __global__ __launch_bounds__(NW * WAVE) void lsap_csr_mw_kernel(const int64_t *i
   }
   size_t off = 0;
   SolveLdsF64 Sl;
-  Sl.u = (double *)(smem + off);      off += r16((size_t)nr * 8);
-  Sl.rv = (double *)(smem + off);     off += r16((size_t)2 * NW * 8);
-  Sl.rk = (uint32_t *)(smem + off);   off += r16((size_t)2 * NW * (FB > 10 ? 8 : 4));
-  Sl.c4r = (int16_t *)(smem + off);   off += r16((size_t)nr * 2);
-  Sl.r4c = (int16_t *)(smem + off);   off += r16((size_t)n * 2);
-  Sl.path = (int16_t *)(smem + off);
+  LSAP_F64_MW_LDS(LDS_CARVE, nr, n, NW, FB)
   for (int i = tid; i < n; i += WG) {
     if (i < nr) {
       Sl.u[i] = 0;

@@ -139,68 +139,27 @@ def _check_int64_range(C: torch.Tensor):
         raise ValueError(f"int64 costs must satisfy |C| < 2**{limit.bit_length() - 1}; pass float64 instead")
 
 
-def _solve_wide_large(C: torch.Tensor, with_cost: bool, fl: int, shape_dev, duals: bool):
-    """_solve_wide / _solve_wide_duals through the lsap_solve_large_ entries
-    (u and v nullable): (col, cost, u, v), u and v None without duals."""
+def _solve_wide(C: torch.Tensor, with_cost: bool, fl: int, shape_dev, duals: bool, large: bool):
+    """C contiguous [B, nr, nc], 1 <= nr <= nc (the square C-ABI entries are
+    the rect ones with nr == nc and no shapes) -> (col, cost, u, v), u and v
+    None without duals.  The entry by (large, duals, dtype): lsap_solve_large_
+    (u and v nullable), lsap_solve_batched_duals_ or lsap_solve_batched_rect_."""
     B, nr, nc = C.shape
     dev = C.device
+    if C.dtype not in DTYPE_SUFFIX:
+        raise TypeError(f"unsupported dtype {C.dtype}")
     _check_int64_range(C)
     ddt = torch.float64 if C.dtype in FLOAT_ENTRIES else torch.int64
     col = torch.empty((B, nr), dtype=torch.int32, device=dev)
     cost = torch.empty(B, dtype=ddt, device=dev) if with_cost else None
     u = torch.empty((B, nr), dtype=ddt, device=dev) if duals else None
     v = torch.empty((B, nc), dtype=ddt, device=dev) if duals else None
-    entry = getattr(_lib.lib(), "lsap_solve_large_" + DTYPE_SUFFIX[C.dtype])
-    rc = entry(_p(C), nr, nc, B, _p(shape_dev), _p(col), _p(cost), _p(u), _p(v), fl,
-               current_stream_handle(dev))
-    _lib.check(rc, "lsap_solve_large")
+    name = "lsap_solve_large" if large else "lsap_solve_batched_duals" if duals else "lsap_solve_batched_rect"
+    uv = (_p(u), _p(v)) if large or duals else ()
+    rc = getattr(_lib.lib(), f"{name}_{DTYPE_SUFFIX[C.dtype]}")(
+        _p(C), nr, nc, B, _p(shape_dev), _p(col), _p(cost), *uv, fl, current_stream_handle(dev))
+    _lib.check(rc, "lsap_solve_batched" if name.endswith("rect") else name)
     return col, cost, u, v
-
-
-def _solve_wide_duals(C: torch.Tensor, with_cost: bool, fl: int, shape_dev, large: bool = False):
-    """_solve_wide through the lsap_solve_batched_duals_ entries: (col, cost, u, v)."""
-    if large:
-        return _solve_wide_large(C, with_cost, fl, shape_dev, True)
-    B, nr, nc = C.shape
-    dev = C.device
-    _check_int64_range(C)
-    ddt = torch.float64 if C.dtype in FLOAT_ENTRIES else torch.int64
-    col = torch.empty((B, nr), dtype=torch.int32, device=dev)
-    cost = torch.empty(B, dtype=ddt, device=dev) if with_cost else None
-    u = torch.empty((B, nr), dtype=ddt, device=dev)
-    v = torch.empty((B, nc), dtype=ddt, device=dev)
-    entry = getattr(_lib.lib(), "lsap_solve_batched_duals_" + DTYPE_SUFFIX[C.dtype])
-    rc = entry(_p(C), nr, nc, B, _p(shape_dev), _p(col), _p(cost), _p(u), _p(v), fl,
-               current_stream_handle(dev))
-    _lib.check(rc, "lsap_solve_batched_duals")
-    return col, cost, u, v
-
-
-def _solve_wide(C: torch.Tensor, with_cost: bool, fl: int, shape_dev, large: bool = False):
-    """C contiguous [B, nr, nc], 1 <= nr <= nc (the square C-ABI entries are
-    the rect ones with nr == nc and no shapes)."""
-    if large:
-        return _solve_wide_large(C, with_cost, fl, shape_dev, False)[:2]
-    B, nr, nc = C.shape
-    dev = C.device
-    col = torch.empty((B, nr), dtype=torch.int32, device=dev)
-    s = current_stream_handle(dev)
-    L = _lib.lib()
-    if C.dtype == torch.int64:
-        _check_int64_range(C)
-        cost = torch.empty(B, dtype=torch.int64, device=dev) if with_cost else None
-        rc = L.lsap_solve_batched_rect_i64(_p(C), nr, nc, B, _p(shape_dev), _p(col), _p(cost), fl, s)
-    elif C.dtype == torch.int32:
-        cost = torch.empty(B, dtype=torch.int64, device=dev) if with_cost else None
-        rc = L.lsap_solve_batched_rect_i32(_p(C), nr, nc, B, _p(shape_dev), _p(col), _p(cost), fl, s)
-    elif C.dtype in FLOAT_ENTRIES:  # read at their own width, solved in float64
-        cost = torch.empty(B, dtype=torch.float64, device=dev) if with_cost else None
-        entry = getattr(L, FLOAT_ENTRIES[C.dtype])
-        rc = entry(_p(C), nr, nc, B, _p(shape_dev), _p(col), _p(cost), fl, s)
-    else:
-        raise TypeError(f"unsupported dtype {C.dtype}")
-    _lib.check(rc, "lsap_solve_batched")
-    return col, cost
 
 
 def solve_batched(C: torch.Tensor, with_cost: bool = True, flags: int = 0, shapes=None,
@@ -275,23 +234,16 @@ def _solve_batched(C, with_cost, flags, shapes, maximize, duals, large):
     if maximize:  # (int32: -INT32_MIN wraps, so widen; the int64 bound covers int64)
         C = -(C.to(torch.int64) if C.dtype == torch.int32 else C)
     fl = _lib.SH_COMPAT_TIEBREAK | flags
-    if duals:
-        if NR > NC:  # the transposed solve's row duals belong to the columns
-            col_t, cost, v, u = _solve_wide_duals(C.transpose(1, 2).contiguous(), with_cost, fl, None, large)
-            col = invert_tall(col_t, NR)
-        else:
-            col, cost, u, v = _solve_wide_duals(C.contiguous(), with_cost, fl, shape_dev, large)
-        if maximize:
-            cost, u, v = (-cost if cost is not None else None), -u, -v
-        return col, cost, u, v
-    if NR > NC:
-        col_t, cost = _solve_wide(C.transpose(1, 2).contiguous(), with_cost, fl, None, large)
+    if NR > NC:  # the transposed solve's row duals belong to the columns
+        col_t, cost, v, u = _solve_wide(C.transpose(1, 2).contiguous(), with_cost, fl, None, duals, large)
         col = invert_tall(col_t, NR)
     else:
-        col, cost = _solve_wide(C.contiguous(), with_cost, fl, shape_dev, large)
+        col, cost, u, v = _solve_wide(C.contiguous(), with_cost, fl, shape_dev, duals, large)
     if maximize and cost is not None:
         cost = -cost
-    return col, cost
+    if not duals:
+        return col, cost
+    return (col, cost, -u, -v) if maximize else (col, cost, u, v)
 
 
 def solve_hash(seed: int, modulus: int, n: int, B: int, device: int | str = 0, with_cost: bool = True,

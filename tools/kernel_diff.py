@@ -36,6 +36,8 @@ def kernels(co):
             out[name] = []
         elif name and line.strip():
             x = line.split("//")[0].strip()
+            if x == "...":  # the listing's mark for zero padding after the code object's last kernel
+                continue
             x = re.sub(r"<[^>]*>", "<L>", x)           # branch-target labels
             x = re.sub(r"(s_c?branch\S*|s_call\S*)\s+\S+", r"\1", x)  # and their offsets
             out[name].append(x)
