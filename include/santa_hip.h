@@ -94,6 +94,15 @@ extern "C" {
                                    (lsap_f64_kernel); A/B, identical results
                                    bit for bit.  Both set: SH_ERR_ARGS.  The
                                    integer and Santa entries ignore them  */
+#define SH_FLAG_MAXIMIZE 65536u /* lbap_solve_* entries: make the SMALLEST
+                                   chosen cost as large as possible (the
+                                   reversed order; costs are never negated) */
+#define SH_FLAG_LBAP_MW 131072u /* lbap_solve_* entries: force the multi-wave
+                                   kernel ...                               */
+#define SH_FLAG_LBAP_SW 262144u /* ... or the one-wave kernel (nc <= SH_MAX_N);
+                                   A/B, identical results bit for bit.  Both
+                                   set: SH_ERR_ARGS.  Other entries ignore
+                                   the three                                */
 #define SH_FLAG_NO_APPLY 1024u  /* solve and report (col, cost, deltas,
                                    steps) but leave the gift types untouched:
                                    blocks may then overlap (batched
@@ -594,6 +603,53 @@ int lsap_solve_csr_f64(const int64_t *d_indptr, const int32_t *d_indices, const 
 int lsap_solve_csr_f32(const int64_t *d_indptr, const int32_t *d_indices, const float *d_data, int nr,
                        int nc, int B, const int32_t *d_shape, int32_t *d_col, double *d_cost, double *d_u,
                        double *d_v, void *d_work, size_t work_bytes, unsigned flags, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Batched linear bottleneck assignment (min-max matching): for each nr x nc
+ * instance, nr <= nc, the assignment of every row to a column of its own whose
+ * LARGEST chosen cost is as small as possible; with SH_FLAG_MAXIMIZE the one
+ * whose smallest chosen cost is as large as possible.  Batch layout, d_shape
+ * and padding as on the lsap_solve_batched_rect_ entries (the padding is never
+ * read); 1 <= nr <= nc <= SH_MAX_N_LARGE; tall input is the caller's to
+ * transpose.
+ *
+ * Costs are only compared, never added: every dtype is solved exactly at its
+ * own width, int64 over its whole range.  -0.0 and +0.0 compare equal.
+ * Forbidden pairs: +inf and NaN of the float dtypes (under SH_FLAG_MAXIMIZE:
+ * -inf and NaN); integers have none.  The optimum is far from unique; the
+ * entries return the one the loop in DESIGN.md §15 defines (one search per
+ * row; the next column is the unvisited one with the least path bottleneck,
+ * free columns before taken ones, then the lowest index), the same in every
+ * kernel configuration.
+ *
+ * d_col [B x nr]: the column of each row; -1 in every row of an infeasible
+ * instance, in padded rows and for an empty or invalid shape.  d_value [B]
+ * (nullable; the dtype of d_C, uint16_t storage for f16 / bf16): the
+ * bottleneck, an element of the instance bit for bit; +inf (-inf under
+ * SH_FLAG_MAXIMIZE) for an infeasible instance, 0 for an empty one.
+ *
+ * One wave per instance up to SH_MAX_N columns or several (required above);
+ * the default is by size and batch, SH_FLAG_LBAP_MW /
+ * SH_FLAG_LBAP_SW force one.  The entries allocate nothing and never
+ * synchronise.
+ *
+ * Checked on the host before any device call, SH_ERR_ARGS for: nr < 1,
+ * nr > nc, nc > SH_MAX_N_LARGE, B < 0; with B > 0 a null d_C or d_col;
+ * SH_FLAG_LBAP_MW with SH_FLAG_LBAP_SW; SH_FLAG_LBAP_SW with nc > SH_MAX_N.
+ * B == 0 is a no-op after the checks.
+ * ------------------------------------------------------------------------ */
+int lbap_solve_i64(const int64_t *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,
+                   int64_t *d_value, unsigned flags, void *stream);
+int lbap_solve_i32(const int32_t *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,
+                   int32_t *d_value, unsigned flags, void *stream);
+int lbap_solve_f64(const double *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,
+                   double *d_value, unsigned flags, void *stream);
+int lbap_solve_f32(const float *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,
+                   float *d_value, unsigned flags, void *stream);
+int lbap_solve_f16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,
+                   uint16_t *d_value, unsigned flags, void *stream);
+int lbap_solve_bf16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,
+                    uint16_t *d_value, unsigned flags, void *stream);
 
 /* ---------------------------------------------------------------------------
  * Synthetic data of the Kaggle shape (host, deterministic, seeded counter

@@ -1220,6 +1220,71 @@ int launch_lsap_csr(const int64_t *indptr, const int32_t *indices, const S *data
   }
   return launch_f64(CsrF64<S>{indptr, data, mask, pre}, nr, n, B, shape, col, cost, du, dv, flags, s);
 }
+
+// ---------------------------------------------------------------------------
+// The lbap_solve_ entries (bottleneck assignment, lbap_kernel).
+// ---------------------------------------------------------------------------
+// Whether a batch of B instances with nc columns runs the multi-wave design by
+// default (measured: DESIGN §15, profiles/lbap.jsonl; four dtypes, 16 / 256 /
+// 4096 instances, the multi-wave time over the one-wave time or back).  Up to
+// 256 columns one wave won or tied everywhere (128 columns: 25-55 % up to 256
+// instances, 2.4-2.6x at 4096; 256 columns: 0-17 %, 1.6-1.9x at 4096).  At
+// 1024 columns four waves won everywhere (42-87 % up to 256 instances, 4-13 %
+// at 4096).  At 512 columns four waves won up to 1024 instances (5-42 %) and
+// one wave from 2048 (4-17 %; 27-54 % at 4096).
+bool lbap_mw_default(int nc, int B) { return nc > 512 || (nc > 256 && B <= 1024); }
+
+// The one launch table of lbap_kernel, for the six dtypes DT (LBAP_*); every
+// check precedes the launch.  One wave with pick_k's columns a lane up to
+// SH_MAX_N columns, or four waves with 1 / 2 / 4 columns a thread (the float
+// LSAP table's), eight and sixteen waves with four beyond SH_MAX_N.
+template <int DT>
+int launch_lbap(const void *C, int nr, int n, int B, const int32_t *shape, int32_t *col, void *value,
+                unsigned flags, hipStream_t s) {
+  HIP_TRY_RC(check_lsap_args(nr, n, B, col, SH_MAX_N_LARGE));
+  if (!C && B > 0) return fail(SH_ERR_ARGS, "null C");
+  if ((flags & SH_FLAG_LBAP_MW) && (flags & SH_FLAG_LBAP_SW))
+    return fail(SH_ERR_ARGS, "SH_FLAG_LBAP_MW and SH_FLAG_LBAP_SW exclude each other");
+  if ((flags & SH_FLAG_LBAP_SW) && n > SH_MAX_N)
+    return fail(SH_ERR_ARGS, "SH_FLAG_LBAP_SW: no one-wave kernel above 1024 columns");
+  if (B == 0) return SH_OK;
+  auto go = [&](auto cfg) {
+    using C_ = decltype(cfg);
+    hipLaunchKernelGGL((lbap_kernel<C_::NW, C_::K, DT>), dim3(B), dim3(C_::NW * WAVE), lbap_lds(nr, n, C_::NW), s,
+                       C, nr, n, shape, col, value, flags);
+    HIP_TRY(hipGetLastError());
+    return SH_OK;
+  };
+  const bool mw = n > SH_MAX_N || (!(flags & SH_FLAG_LBAP_SW) && ((flags & SH_FLAG_LBAP_MW) || lbap_mw_default(n, B)));
+  if (!mw) {
+    switch (pick_k(n)) {
+      case 1: return go(BigCfg<1, 1, 0>{});
+      case 2: return go(BigCfg<1, 2, 0>{});
+      case 4: return go(BigCfg<1, 4, 0>{});
+      case 8: return go(BigCfg<1, 8, 0>{});
+      default: return go(BigCfg<1, 16, 0>{});
+    }
+  }
+  if (n <= 256) return go(BigCfg<4, 1, 0>{});
+  if (n <= 512) return go(BigCfg<4, 2, 0>{});
+  if (n <= 1024) return go(BigCfg<4, 4, 0>{});
+  if (n <= 2048) return go(BigCfg<8, 4, 0>{});
+  return go(BigCfg<16, 4, 0>{});
+}
+
+// lbap_lds at the seams of the table above, each region rounded up to 16
+// bytes: 16 NW and 8 NW of step slots, 2 nr of col4row, 2 n each of row4col
+// and path.
+static_assert(lbap_lds(1, 1, 1) == 80 && lbap_lds(64, 64, 1) == 416 && lbap_lds(65, 65, 1) == 464);
+static_assert(lbap_lds(128, 128, 1) == 800 && lbap_lds(129, 129, 1) == 848);
+static_assert(lbap_lds(256, 256, 1) == 1568 && lbap_lds(257, 257, 1) == 1616);
+static_assert(lbap_lds(512, 512, 1) == 3104 && lbap_lds(513, 513, 1) == 3152);
+static_assert(lbap_lds(1024, 1024, 1) == 6176);
+static_assert(lbap_lds(1, 1, 4) == 144 && lbap_lds(256, 256, 4) == 1632 && lbap_lds(257, 257, 4) == 1680);
+static_assert(lbap_lds(512, 512, 4) == 3168 && lbap_lds(513, 513, 4) == 3216);
+static_assert(lbap_lds(1024, 1024, 4) == 6240 && lbap_lds(1025, 1025, 8) == 6384);
+static_assert(lbap_lds(2048, 2048, 8) == 12480 && lbap_lds(2049, 2049, 16) == 12720);
+static_assert(lbap_lds(4096, 4096, 16) == 24960 && lbap_lds(1, 4096, 16) == 16784);
 }  // namespace
 
 extern "C" {
@@ -1294,6 +1359,19 @@ int lsap_solve_csr_f32(const int64_t *d_indptr, const int32_t *d_indices, const 
   return launch_lsap_csr(d_indptr, d_indices, d_data, nr, nc, B, d_shape, d_col, d_cost, d_u, d_v, d_work,
                          work_bytes, flags, (hipStream_t)stream);
 }
+
+#define SH_LBAP_ENTRY(SUF, CT, DT)                                                                       \
+  int lbap_solve_##SUF(const CT *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,     \
+                       CT *d_value, unsigned flags, void *stream) {                                      \
+    return launch_lbap<DT>(d_C, nr, nc, B, d_shape, d_col, d_value, flags, (hipStream_t)stream);         \
+  }
+SH_LBAP_ENTRY(i64, int64_t, LBAP_I64)
+SH_LBAP_ENTRY(i32, int32_t, LBAP_I32)
+SH_LBAP_ENTRY(f64, double, LBAP_F64)
+SH_LBAP_ENTRY(f32, float, LBAP_F32)
+SH_LBAP_ENTRY(f16, uint16_t, LBAP_F16)
+SH_LBAP_ENTRY(bf16, uint16_t, LBAP_BF16)
+#undef SH_LBAP_ENTRY
 
 // The square entries: nr == nc == n, no shapes.
 int lsap_solve_batched_i64(const int64_t *d_C, int n, int B, int32_t *d_col, int64_t *d_cost,

@@ -6232,6 +6232,314 @@ __global__ __launch_bounds__(CERT_WG) void lsap_cert_final_kernel(int B, T *slac
 }
 
 // ---------------------------------------------------------------------------
+// Batched linear bottleneck assignment (LBAP): the assignment whose LARGEST
+// chosen cost is as small as possible (Derigs-Zimmermann: the shortest
+// augmenting path loop with max in place of +).  One search per
+// row; a path's length is the largest cost on it, so there are no duals and no
+// arithmetic on costs, only comparisons: a cost is mapped on load to an
+// order-preserving unsigned key (cert_key's mapping at the dtype's own width)
+// and everything after that is unsigned.
+//
+//   integers   key = bits ^ sign; nothing is forbidden (INT_MAX is a cost)
+//   floats     -0.0 is read as +0.0 (they compare equal), then the usual
+//              sign-magnitude flip; +inf and NaN are forbidden: the key above
+//              every cost key (all ones, which no float key reaches)
+//   maximize   key ^= all ones (the reversed order, never a negation: -INT_MIN
+//              wraps); the forbidden infinity is then -inf
+//
+// 64-bit keys for int64 / float64, 32-bit keys for the four narrower dtypes
+// (float16 / bfloat16: the 16-bit key, zero-extended).
+//
+// Thread tid of the NW * 64 owns columns j = tid + 64 NW k (mw_col's map),
+// k < K: path length spc, path row and a visited bit in registers, row4col's
+// sign as a `taken` bit re-read from LDS at each search's start.  A search's
+// first step writes spc and path of every column (the semantics' initial value
+// lies above every key, the forbidden one included, so no sentinel is needed
+// and "no column left" is decided by the visited bits alone).  The step's
+// winner is the unvisited column with the least (spc, taken, j):
+//   32-bit keys  one wave_min_u64_dpp over (spc << 32) | taken << 31 | j; an
+//                excluded column contributes all ones, which no candidate
+//                equals (j < 2^31 - 1)
+//   64-bit keys  two reductions, min spc and then min (taken << 31 | j) among
+//                the columns at that spc (sap_solve_mw_f64's form)
+// and with NW > 1 the waves' minima meet in LDS slots double-buffered by step
+// parity, one barrier a step (as sap_solve_mw_f64's rv / rk).  Returns 0, or
+// -1 for an infeasible instance (block-uniform; floats only).
+// ---------------------------------------------------------------------------
+enum { LBAP_I64 = 0, LBAP_I32, LBAP_F64, LBAP_F32, LBAP_F16, LBAP_BF16 };
+
+// U: a cost's bits; KT: its key; INFB: the bits of +inf
+template <int DT> struct LbapT;
+template <> struct LbapT<LBAP_I64> {
+  using U = uint64_t; using KT = uint64_t;
+  static constexpr bool FLT = false;
+  static constexpr U SIGN = 1ull << 63, INFB = 0;
+};
+template <> struct LbapT<LBAP_I32> {
+  using U = uint32_t; using KT = uint32_t;
+  static constexpr bool FLT = false;
+  static constexpr U SIGN = 1u << 31, INFB = 0;
+};
+template <> struct LbapT<LBAP_F64> {
+  using U = uint64_t; using KT = uint64_t;
+  static constexpr bool FLT = true;
+  static constexpr U SIGN = 1ull << 63, INFB = 0x7FF0000000000000ull;
+};
+template <> struct LbapT<LBAP_F32> {
+  using U = uint32_t; using KT = uint32_t;
+  static constexpr bool FLT = true;
+  static constexpr U SIGN = 1u << 31, INFB = 0x7F800000u;
+};
+template <> struct LbapT<LBAP_F16> {
+  using U = uint16_t; using KT = uint32_t;
+  static constexpr bool FLT = true;
+  static constexpr U SIGN = 0x8000, INFB = 0x7C00;
+};
+template <> struct LbapT<LBAP_BF16> {
+  using U = uint16_t; using KT = uint32_t;
+  static constexpr bool FLT = true;
+  static constexpr U SIGN = 0x8000, INFB = 0x7F80;
+};
+
+// mask: 0, or all ones under maximize (wave-uniform)
+template <int DT>
+__device__ __forceinline__ typename LbapT<DT>::KT lbap_key(typename LbapT<DT>::U raw,
+                                                           const typename LbapT<DT>::U mask) {
+  using L = LbapT<DT>;
+  using U = typename L::U;
+  using KT = typename L::KT;
+  if constexpr (!L::FLT) {
+    return (KT)(U)(raw ^ L::SIGN ^ mask);
+  } else {
+    const U a = (U)(raw & (U)~L::SIGN);
+    if (a == 0) raw = 0;
+    const U k = (raw & L::SIGN) ? (U)~raw : (U)(raw | L::SIGN);
+    const U worst = mask ? (U)(L::INFB | L::SIGN) : L::INFB;
+    return (a > L::INFB || raw == worst) ? ~(KT)0 : (KT)(U)(k ^ mask);
+  }
+}
+
+struct LbapLds {
+  uint64_t *rv;   // [2 * NW]  the waves' step minima, by step parity (32-bit keys: the packed word)
+  uint32_t *rk;   // [2 * NW]  64-bit keys: and their (taken, column) words
+  int16_t *c4r;   // [nr]  col4row (the result)
+  int16_t *r4c;   // [n]   row4col
+  int16_t *path;  // [n]   path dump of the visited columns
+};
+
+#define LBAP_LDS(X, nr, n, nw)            \
+  X(Sl.rv, uint64_t, (size_t)2 * nw * 8)  \
+  X(Sl.rk, uint32_t, (size_t)2 * nw * 4)  \
+  X(Sl.c4r, int16_t, (size_t)nr * 2)      \
+  X(Sl.r4c, int16_t, (size_t)n * 2)       \
+  X(Sl.path, int16_t, (size_t)n * 2)
+__host__ __device__ constexpr size_t lbap_lds(int nr, int n, int nw) { return 0 LBAP_LDS(LDS_BYTES, nr, n, nw); }
+
+__device__ __forceinline__ uint64_t uniform_u64(uint64_t x) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(x >> 32));
+  return ((uint64_t)hi << 32) | lo;
+}
+
+template <int NW, int K, int DT>
+__device__ __forceinline__ int lbap_solve(const typename LbapT<DT>::U *__restrict__ C, const int ld, const int nr,
+                                          const int n, const typename LbapT<DT>::U mask, const LbapLds &S) {
+  using L = LbapT<DT>;
+  using U = typename L::U;
+  using KT = typename L::KT;
+  constexpr bool K32 = sizeof(KT) == 4;
+  constexpr int WG = NW * WAVE;
+  static_assert(K <= 32, "visited and taken bits in one word each");
+  const int tid = threadIdx.x, w = tid >> 6;
+  KT spc[K];
+  int path[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    spc[k] = 0;
+    path[k] = -1;
+  }
+  int par = 0;  // slot buffer of the step
+  for (int cur = 0; cur < nr; ++cur) {
+    uint32_t vis = 0, taken = 0;  // (a slot beyond the live columns counts as visited)
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int j = tid + WG * k;
+      if (j >= n)
+        vis |= 1u << k;
+      else if (S.r4c[j] >= 0)
+        taken |= 1u << k;
+    }
+    int i = cur, sink = -1;
+    KT mv = 0;
+    bool first = true;
+    for (int left = n; left > 0; --left) {
+      // row i's costs of this thread's columns, the last live one for a slot
+      // beyond them (n >= 1: the padding is never read); all K loads first
+      const U *row = C + (size_t)i * ld;
+      U raw[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) raw[k] = row[min(tid + WG * k, n - 1)];
+      uint64_t bkey = ~0ull;  // 32-bit keys: the packed word
+      uint32_t bsec = SEC_NONE;
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        const KT c = lbap_key<DT>(raw[k], mask);
+        const KT r = c > mv ? c : mv;
+        // (a visited column has spc <= mv <= r and keeps its path)
+        if (first || r < spc[k]) {
+          spc[k] = r;
+          path[k] = i;
+        }
+        if (!((vis >> k) & 1u)) {
+          const uint32_t sec = (((taken >> k) & 1u) << 31) | (uint32_t)(tid + WG * k);
+          if constexpr (K32) {
+            bkey = umin64(bkey, ((uint64_t)spc[k] << 32) | sec);
+          } else {
+            if (spc[k] < bkey || (spc[k] == bkey && sec < bsec)) {
+              bkey = spc[k];
+              bsec = sec;
+            }
+          }
+        }
+      }
+      first = false;
+      uint64_t gk = wave_min_u64_dpp(bkey);
+      uint32_t gs = SEC_NONE;
+      if constexpr (!K32) gs = wave_min_u32_dpp(bkey == gk ? bsec : SEC_NONE);
+      if constexpr (NW > 1) {
+        if ((tid & 63) == 0) {
+          S.rv[par * NW + w] = gk;
+          if constexpr (!K32) S.rk[par * NW + w] = gs;
+        }
+        __syncthreads();
+        gk = S.rv[par * NW];
+        if constexpr (!K32) gs = S.rk[par * NW];
+#pragma unroll
+        for (int q = 1; q < NW; ++q) {
+          const uint64_t kq = S.rv[par * NW + q];
+          if constexpr (K32) {
+            gk = umin64(gk, kq);
+          } else {
+            const uint32_t sq = S.rk[par * NW + q];
+            if (kq < gk || (kq == gk && sq < gs)) {
+              gk = kq;
+              gs = sq;
+            }
+          }
+        }
+        par ^= 1;
+        gk = uniform_u64(gk);
+        if constexpr (!K32) gs = (uint32_t)__builtin_amdgcn_readfirstlane((int)gs);
+      }
+      if constexpr (K32) {
+        if (gk == ~0ull) return -1;  // no column left
+        gs = (uint32_t)gk;
+        mv = (KT)(gk >> 32);
+      } else {
+        if (gs == SEC_NONE) return -1;  // no column left
+        mv = (KT)gk;
+      }
+      if constexpr (L::FLT) {
+        if (mv == ~(KT)0) return -1;  // only forbidden entries lead on: infeasible
+      }
+      const int jstar = (int)(gs & 0x7FFFFFFFu);
+#pragma unroll
+      for (int k = 0; k < K; ++k)
+        if (tid + WG * k == jstar) vis |= 1u << k;
+      if (!(gs >> 31)) {
+        sink = jstar;
+        break;
+      }
+      i = __builtin_amdgcn_readfirstlane((int)S.r4c[jstar]);
+    }
+    if (sink < 0) return -1;
+    // path dump of the visited columns, then one thread augments from the
+    // sink back to cur (<= nr hops), as the min-sum solvers do
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int j = tid + WG * k;
+      if (j < n && ((vis >> k) & 1u)) S.path[j] = (int16_t)path[k];
+    }
+    __syncthreads();
+    if (tid == 0) {
+      int j = sink;
+      for (int hop = 0; hop < nr; ++hop) {
+        const int pi = S.path[j];
+        if (pi < 0) break;  // (unreachable)
+        S.r4c[j] = (int16_t)pi;
+        const int t = S.c4r[pi];
+        S.c4r[pi] = (int16_t)j;
+        j = t;
+        if (pi == cur || j < 0) break;
+      }
+    }
+    __syncthreads();
+  }
+  return 0;
+}
+
+// One instance a workgroup: NW = 1 is the one-wave design (K columns a lane,
+// up to 1024 columns), NW > 1 the multi-wave one (up to 4096).  C and value
+// are the costs' bits (LbapT<DT>::U).  value[b] is the largest chosen cost,
+// read back from C (an element of C bit for bit): the first row, in lane
+// order, whose chosen entry has the largest key.  An infeasible instance gets
+// col = -1 and value = +inf (-inf under maximize); an empty one -1 and 0.
+template <int NW, int K, int DT>
+__global__ __launch_bounds__(NW * WAVE) void lbap_kernel(const void *C_, int NR, int NC, const int32_t *shape,
+                                                         int32_t *col, void *value_, unsigned flags) {
+  using L = LbapT<DT>;
+  using U = typename L::U;
+  using KT = typename L::KT;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int WG = NW * WAVE;
+  const U *C = (const U *)C_;
+  U *value = (U *)value_;
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const U mask = (flags & SH_FLAG_MAXIMIZE) ? (U)~(U)0 : (U)0;
+  int nr, n;  // live rows and columns (see lsap_i64_kernel)
+  if (!lsap_shape(shape, b, NR, NC, nr, n)) {
+    lsap_no_instance<WG>(col, value, b, NR, NC);
+    return;
+  }
+  size_t off = 0;
+  LbapLds Sl;
+  LBAP_LDS(LDS_CARVE, nr, n, NW)
+  for (int i = tid; i < n; i += WG) {
+    if (i < nr) Sl.c4r[i] = -1;
+    Sl.r4c[i] = -1;
+    Sl.path[i] = -1;
+  }
+  __syncthreads();
+  const size_t base = (size_t)b * NR * NC;
+  const int st = lbap_solve<NW, K, DT>(C + base, NC, nr, n, mask, Sl);
+  __syncthreads();
+  for (int i = tid; i < NR; i += WG) col[(size_t)b * NR + i] = (st == 0 && i < nr) ? Sl.c4r[i] : -1;
+  if (value && tid < WAVE) {
+    if (st != 0) {
+      if (tid == 0) value[b] = mask ? (U)(L::INFB | L::SIGN) : L::INFB;
+    } else {
+      KT bk = 0;
+      U braw = 0;
+      bool have = false;
+      for (int i = tid; i < nr; i += WAVE) {
+        const U x = C[base + (size_t)i * NC + Sl.c4r[i]];
+        const KT k = lbap_key<DT>(x, mask);
+        if (!have || k > bk) {
+          bk = k;
+          braw = x;
+          have = true;
+        }
+      }
+      // (a lane without a row holds key 0, below or equal to lane 0's)
+      const uint64_t top = ~wave_min_u64_dpp(~(uint64_t)bk);
+      const uint64_t at = __builtin_amdgcn_ballot_w64(have && (uint64_t)bk == top);
+      if (tid == (int)__builtin_ctzll(at)) value[b] = braw;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Score: streaming S_child / S_gift / family checks (mpi_single.py:13-83).
 // A wave takes 64 consecutive children, reads their wishlist rows as one
 // contiguous span with 16-B loads, and finds each child's first matching rank

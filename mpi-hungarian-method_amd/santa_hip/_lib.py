@@ -35,6 +35,9 @@ SH_FLAG_DT_TILE = 4096  # force the dense-tile one-wave kernel (santa_dt_kernel)
 SH_FLAG_BIG_ROWS = 8192  # singles n > 256: force the row-rebuild kernel (santa_big_kernel)
 SH_FLAG_F64_MW = 16384  # float LSAP entries, nc > 64: force the four-wave kernel (lsap_f64_mw_kernel)
 SH_FLAG_F64_SW = 32768  # float LSAP entries: force the one-wave kernel (lsap_f64_kernel)
+SH_FLAG_MAXIMIZE = 65536  # lbap_solve_ entries: the reversed order (max-min), never a negation
+SH_FLAG_LBAP_MW = 131072  # lbap_solve_ entries: force the multi-wave kernel
+SH_FLAG_LBAP_SW = 262144  # lbap_solve_ entries: force the one-wave kernel (nc <= SH_MAX_N)
 # lsap_check_duals_*: the certificate's per-instance bits (include/santa_hip.h)
 SH_CERT_COL = 1
 SH_CERT_SLACK = 2
@@ -138,6 +141,8 @@ SIGNATURES = {
 for _suf in ("i64", "i32", "f64", "f32", "f16", "bf16"):  # the duals / check_duals argument lists
     SIGNATURES["lsap_solve_large_" + _suf] = SIGNATURES["lsap_solve_batched_duals_" + _suf]
     SIGNATURES["lsap_check_duals_large_" + _suf] = SIGNATURES["lsap_check_duals_" + _suf]
+    # bottleneck assignment: C, nr, nc, B, shape, col, value, flags, stream
+    SIGNATURES["lbap_solve_" + _suf] = (_I, [_P, _I, _I, _I, _P, _P, _P, _U, _P])
 # the sparse (CSR) float entries: indptr, indices, data, nr, nc, B, shape, col, cost, u, v, work, work_bytes, flags, stream
 SIGNATURES["lsap_csr_work_bytes"] = (ctypes.c_size_t, [_I, _I, _I])
 for _suf in ("f64", "f32"):
