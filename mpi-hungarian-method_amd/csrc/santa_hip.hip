@@ -3663,15 +3663,19 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
     //  Dijkstra's scalar branches and operands turn into lane masks and VGPRs)
     int np = n;
     asm volatile("" : "+s"(np));
-    for (int cur = 0; cur < n; ++cur) {
-      if (cur == np - SP3_PRIO_A) __builtin_amdgcn_s_setprio(2);  // (issue priority, above)
-      if (cur == np - SP3_PRIO_B) __builtin_amdgcn_s_setprio(1);
-      if (cur == np - SP3_PRIO_C) __builtin_amdgcn_s_setprio(0);
+    // Two nested loops over the Dijkstras.  The inner one runs consecutive
+    // single-step Dijkstras (the common case) and carries only what that path
+    // changes -- c4r, r4c, LI, cur, steps -- so its back edge copies no
+    // register; a multi-step Dijkstra leaves it for the hand-over, the
+    // generic steps, the dual update and the augmentation, and the outer
+    // back edge returns to it (as one loop, the back edge moved
+    // W, Wp, LI, prow, c4r, r4c, accU and accW between the two paths' homes
+    // after every Dijkstra).
+    int cur = 0;
+    while (cur < n) {
       // A Dijkstra's state: the peeled first step needs none of it (remaining
       // = [n-1 .. 0], every column < n live, spc = inf are folded in); its
       // hand-over sets what the generic loop holds after its step 0
-      int ln = lane;
-      asm volatile("" : "+v"(ln));
       int nrem;
       uint32_t rq;   // &rem[nrem - 1], stepped down (a VGPR: the LDS address operand, stepped by one VALU)
       uint32_t mvb;  // minVal + BIAS (the key's value field of the last winner)
@@ -3896,12 +3900,23 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
           i = __builtin_amdgcn_readlane((int)rsel, lw);
         }
       };
-      step(std::true_type{}, fetch(cur, T0[(cur >> 2) & 31], T1[(cur >> 2) & 31]));
-      // the winner's lane (the one lane holding the key) and column
-      const uint64_t wl = __builtin_amdgcn_ballot_w64(best == g);
-      const int lw = (int)__builtin_ctzll(wl);
-      sink = 4 * lw + kw;
-      if (!assigned) {
+      uint64_t wl;  // the winner's lane (the one lane holding the key)
+      int lw;
+      bool multi = false;
+      do {
+        if (cur == np - SP3_PRIO_A) __builtin_amdgcn_s_setprio(2);  // (issue priority, above)
+        if (cur == np - SP3_PRIO_B) __builtin_amdgcn_s_setprio(1);
+        if (cur == np - SP3_PRIO_C) __builtin_amdgcn_s_setprio(0);
+        first = true;
+        i = cur;  // (the step's row: its overflow range is read by it)
+        step(std::true_type{}, fetch(cur, T0[(cur >> 2) & 31], T1[(cur >> 2) & 31]));
+        wl = __builtin_amdgcn_ballot_w64(best == g);
+        lw = (int)__builtin_ctzll(wl);
+        sink = 4 * lw + kw;  // the winner's column
+        if (assigned) {
+          multi = true;
+          break;
+        }
         // The single-step Dijkstra (the common case: DESIGN §4.0b): row cur
         // takes the unassigned column that won the first scan, and nothing
         // else changes -- no column was visited, the sink's dual moves by 0,
@@ -3923,8 +3938,10 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
         flip_sink(wl, kw);
         stamp(tD1);
         stamp(tD2);
-        continue;
-      }
+      } while (++cur < n);
+      if (!multi) break;
+      int ln = lane;  // (opaque: see `remaining` below)
+      asm volatile("" : "+v"(ln));
       // Hand-over: the state the generic loop holds after its step 0 -- the
       // winner (assigned: pstar = pkey) leaves `remaining`, the mover is
       // column 0 (rem[n - 1] of a pristine `remaining`), rowq[n - 1] = &u[cur]
@@ -3965,6 +3982,11 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
       // unreached column reads an unused in-bounds word).
       const int32_t minVal = (int32_t)mvb - SP3_BIAS;
       i32x4 prow;  // (one VGPR tuple: the augmentation selects prow[j & 3] by an indexed move)
+      // (defined here, in its pinned registers, by an empty asm: the masked
+      //  regions below write only the visited columns' slots, and a tuple
+      //  left partly undefined was carried round the Dijkstra loop and copied
+      //  at its back edge)
+      asm volatile("" : "=" SH_VTUPLE(SP3_PROW_V, SP3_PROW_VE)(prow));
       // (the visited columns and the sink only, exec-masked: DESIGN §4.0b; 1 % faster
       //  here, 2-4 % slower in santa_dt_kernel: profiles/r05h_masked_dual_ab.jsonl)
       // (the sink's slot in this lane as one value per Dijkstra, sink - 4 lane
@@ -4018,6 +4040,7 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
       } while (pi != cur && --left >= 0);
       bad |= pi != cur;
       stamp(tD2);
+      ++cur;
     }
   }
   stamp(tD);
