@@ -652,6 +652,74 @@ int lbap_solve_bf16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d
                     uint16_t *d_value, unsigned flags, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * The bottleneck solve with a proof of its value, and the check of that proof.
+ *
+ * lbap_solve_wit_*: lbap_solve_*'s arguments, checks, flags and results (d_col
+ * and d_value are the same bits) and d_wit uint8 [B x nr] (required with
+ * B > 0): 1 on the rows of a Hall violator R, 0 elsewhere (padded rows, empty
+ * and invalid shapes: 0).  The entries of the instance strictly below the value
+ * (in the direction's order) join R to at most |R| - 1 columns, so no
+ * assignment of every row stays below it.  R is defined by the loop (DESIGN.md
+ * §15), the same in every kernel configuration: of the last search whose final
+ * path bottleneck rose strictly above every earlier search's (the first search
+ * counts as one), the row searched from and the rows matched to the columns
+ * visited at a smaller path bottleneck; of a search that failed (infeasible),
+ * the row searched from and the rows of every column visited.
+ *
+ * lbap_check_*: d_col, d_value (required) and d_wit as the solver wrote them,
+ * or anything else: they are read as data, never as an index outside the
+ * buffers.  `flags`: SH_FLAG_MAXIMIZE as given to the solver (SH_FLAG_LBAP_MW /
+ * SH_FLAG_LBAP_SW are checked as there and change nothing).  Every comparison
+ * is on the solver's order-preserving keys (-0.0 equals +0.0; NaN and the
+ * forbidden infinity share the key above every cost), so it is exact for every
+ * dtype and for int64 over its whole range.
+ *   d_counts int32 [B x 2]: nR, the live rows with d_wit != 0, and nN, the live
+ *     columns that an entry strictly below d_value joins to one of those rows
+ *   d_flags int32 [B]: SH_LBCERT_* bits.  0 proves the instance optimal;
+ *     SH_LBCERT_NONE alone proves it infeasible.  An empty instance gives 0 and
+ *     (0, 0).
+ * One launch on `stream`, one workgroup per instance; nothing is allocated and
+ * nothing synchronises.  SH_ERR_ARGS as on lbap_solve_*, and for a null
+ * d_value, d_wit, d_counts or d_flags with B > 0.
+ * ------------------------------------------------------------------------ */
+#define SH_LBCERT_COL 1     /* d_col is not an assignment of the live rows (SH_CERT_COL's
+                               definition); an integer instance whose live rows all have -1 */
+#define SH_LBCERT_VALUE 2   /* the largest chosen entry is not d_value (compared as keys); with
+                               no chosen entry, d_value is not the forbidden infinity */
+#define SH_LBCERT_WITNESS 4 /* not nN < nR: d_wit does not prove d_value */
+#define SH_LBCERT_NONE 8    /* every live row has col == -1 */
+int lbap_solve_wit_i64(const int64_t *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,
+                       int64_t *d_value, uint8_t *d_wit, unsigned flags, void *stream);
+int lbap_solve_wit_i32(const int32_t *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,
+                       int32_t *d_value, uint8_t *d_wit, unsigned flags, void *stream);
+int lbap_solve_wit_f64(const double *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,
+                       double *d_value, uint8_t *d_wit, unsigned flags, void *stream);
+int lbap_solve_wit_f32(const float *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,
+                       float *d_value, uint8_t *d_wit, unsigned flags, void *stream);
+int lbap_solve_wit_f16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,
+                       uint16_t *d_value, uint8_t *d_wit, unsigned flags, void *stream);
+int lbap_solve_wit_bf16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,
+                        uint16_t *d_value, uint8_t *d_wit, unsigned flags, void *stream);
+int lbap_check_i64(const int64_t *d_C, int nr, int nc, int B, const int32_t *d_shape, const int32_t *d_col,
+                   const int64_t *d_value, const uint8_t *d_wit, int32_t *d_counts, int32_t *d_flags,
+                   unsigned flags, void *stream);
+int lbap_check_i32(const int32_t *d_C, int nr, int nc, int B, const int32_t *d_shape, const int32_t *d_col,
+                   const int32_t *d_value, const uint8_t *d_wit, int32_t *d_counts, int32_t *d_flags,
+                   unsigned flags, void *stream);
+int lbap_check_f64(const double *d_C, int nr, int nc, int B, const int32_t *d_shape, const int32_t *d_col,
+                   const double *d_value, const uint8_t *d_wit, int32_t *d_counts, int32_t *d_flags,
+                   unsigned flags, void *stream);
+int lbap_check_f32(const float *d_C, int nr, int nc, int B, const int32_t *d_shape, const int32_t *d_col,
+                   const float *d_value, const uint8_t *d_wit, int32_t *d_counts, int32_t *d_flags,
+                   unsigned flags, void *stream);
+int lbap_check_f16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape, const int32_t *d_col,
+                   const uint16_t *d_value, const uint8_t *d_wit, int32_t *d_counts, int32_t *d_flags,
+                   unsigned flags, void *stream);
+int lbap_check_bf16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape, const int32_t *d_col,
+                    const uint16_t *d_value, const uint8_t *d_wit, int32_t *d_counts, int32_t *d_flags,
+                    unsigned flags, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Synthetic data of the Kaggle shape (host, deterministic, seeded counter
  * PRNG).  Wishlists: n_wish distinct gift types per child; good-kids: n_good
  * distinct children per gift; baseline: a feasible assignment (triplets and

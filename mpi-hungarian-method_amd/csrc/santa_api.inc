@@ -1238,20 +1238,32 @@ bool lbap_mw_default(int nc, int B) { return nc > 512 || (nc > 256 && B <= 1024)
 // check precedes the launch.  One wave with pick_k's columns a lane up to
 // SH_MAX_N columns, or four waves with 1 / 2 / 4 columns a thread (the float
 // LSAP table's), eight and sixteen waves with four beyond SH_MAX_N.
-template <int DT>
-int launch_lbap(const void *C, int nr, int n, int B, const int32_t *shape, int32_t *col, void *value,
-                unsigned flags, hipStream_t s) {
+int check_lbap_args(const void *C, int nr, int n, int B, const int32_t *col, unsigned flags) {
   HIP_TRY_RC(check_lsap_args(nr, n, B, col, SH_MAX_N_LARGE));
   if (!C && B > 0) return fail(SH_ERR_ARGS, "null C");
   if ((flags & SH_FLAG_LBAP_MW) && (flags & SH_FLAG_LBAP_SW))
     return fail(SH_ERR_ARGS, "SH_FLAG_LBAP_MW and SH_FLAG_LBAP_SW exclude each other");
   if ((flags & SH_FLAG_LBAP_SW) && n > SH_MAX_N)
     return fail(SH_ERR_ARGS, "SH_FLAG_LBAP_SW: no one-wave kernel above 1024 columns");
+  return SH_OK;
+}
+
+// WIT: the lbap_solve_wit_ entries, bneck_wit_kernel through the same table
+// and switch, with `wit` and its own LDS list.
+template <int DT, bool WIT = false>
+int launch_lbap(const void *C, int nr, int n, int B, const int32_t *shape, int32_t *col, void *value,
+                unsigned flags, hipStream_t s, uint8_t *wit = nullptr) {
+  HIP_TRY_RC(check_lbap_args(C, nr, n, B, col, flags));
+  if (WIT && !wit && B > 0) return fail(SH_ERR_ARGS, "null wit");
   if (B == 0) return SH_OK;
   auto go = [&](auto cfg) {
     using C_ = decltype(cfg);
-    hipLaunchKernelGGL((lbap_kernel<C_::NW, C_::K, DT>), dim3(B), dim3(C_::NW * WAVE), lbap_lds(nr, n, C_::NW), s,
-                       C, nr, n, shape, col, value, flags);
+    if constexpr (WIT)
+      hipLaunchKernelGGL((bneck_wit_kernel<C_::NW, C_::K, DT>), dim3(B), dim3(C_::NW * WAVE),
+                         lbap_wit_lds(nr, n, C_::NW), s, C, nr, n, shape, col, value, wit, flags);
+    else
+      hipLaunchKernelGGL((lbap_kernel<C_::NW, C_::K, DT>), dim3(B), dim3(C_::NW * WAVE), lbap_lds(nr, n, C_::NW), s,
+                         C, nr, n, shape, col, value, flags);
     HIP_TRY(hipGetLastError());
     return SH_OK;
   };
@@ -1285,6 +1297,32 @@ static_assert(lbap_lds(512, 512, 4) == 3168 && lbap_lds(513, 513, 4) == 3216);
 static_assert(lbap_lds(1024, 1024, 4) == 6240 && lbap_lds(1025, 1025, 8) == 6384);
 static_assert(lbap_lds(2048, 2048, 8) == 12480 && lbap_lds(2049, 2049, 16) == 12720);
 static_assert(lbap_lds(4096, 4096, 16) == 24960 && lbap_lds(1, 4096, 16) == 16784);
+// lbap_wit_lds at the same seams: the list above and 2 nr of stamp.
+static_assert(lbap_wit_lds(1, 1, 1) == 96 && lbap_wit_lds(64, 64, 1) == 544 && lbap_wit_lds(65, 65, 1) == 608);
+static_assert(lbap_wit_lds(128, 128, 1) == 1056 && lbap_wit_lds(129, 129, 1) == 1120);
+static_assert(lbap_wit_lds(256, 256, 1) == 2080 && lbap_wit_lds(257, 257, 1) == 2144);
+static_assert(lbap_wit_lds(512, 512, 1) == 4128 && lbap_wit_lds(513, 513, 1) == 4192);
+static_assert(lbap_wit_lds(1024, 1024, 1) == 8224);
+static_assert(lbap_wit_lds(1, 1, 4) == 160 && lbap_wit_lds(256, 256, 4) == 2144 && lbap_wit_lds(257, 257, 4) == 2208);
+static_assert(lbap_wit_lds(512, 512, 4) == 4192 && lbap_wit_lds(513, 513, 4) == 4256);
+static_assert(lbap_wit_lds(1024, 1024, 4) == 8288 && lbap_wit_lds(1025, 1025, 8) == 8448);
+static_assert(lbap_wit_lds(2048, 2048, 8) == 16576 && lbap_wit_lds(2049, 2049, 16) == 16832);
+static_assert(lbap_wit_lds(4096, 4096, 16) == 33152 && lbap_wit_lds(1, 4096, 16) == 16800);
+
+// The lbap_check_ entries (bneck_check_kernel): lbap_solve_'s checks, then one
+// launch of one workgroup per instance.
+template <int DT>
+int launch_lbap_check(const void *C, int nr, int n, int B, const int32_t *shape, const int32_t *col,
+                      const void *value, const uint8_t *wit, int32_t *counts, int32_t *flg, unsigned flags,
+                      hipStream_t s) {
+  HIP_TRY_RC(check_lbap_args(C, nr, n, B, col, flags));
+  if (B > 0 && (!value || !wit || !counts || !flg)) return fail(SH_ERR_ARGS, "null value, wit, counts or flags");
+  if (B == 0) return SH_OK;
+  hipLaunchKernelGGL((bneck_check_kernel<DT>), dim3(B), dim3(CERT_WG), 0, s, C, nr, n, shape, col, value, wit,
+                     counts, flg, flags);
+  HIP_TRY(hipGetLastError());
+  return SH_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1364,6 +1402,17 @@ int lsap_solve_csr_f32(const int64_t *d_indptr, const int32_t *d_indices, const 
   int lbap_solve_##SUF(const CT *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,     \
                        CT *d_value, unsigned flags, void *stream) {                                      \
     return launch_lbap<DT>(d_C, nr, nc, B, d_shape, d_col, d_value, flags, (hipStream_t)stream);         \
+  }                                                                                                      \
+  int lbap_solve_wit_##SUF(const CT *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col, \
+                           CT *d_value, uint8_t *d_wit, unsigned flags, void *stream) {                  \
+    return launch_lbap<DT, true>(d_C, nr, nc, B, d_shape, d_col, d_value, flags, (hipStream_t)stream,    \
+                                 d_wit);                                                                 \
+  }                                                                                                      \
+  int lbap_check_##SUF(const CT *d_C, int nr, int nc, int B, const int32_t *d_shape,                     \
+                       const int32_t *d_col, const CT *d_value, const uint8_t *d_wit, int32_t *d_counts, \
+                       int32_t *d_flags, unsigned flags, void *stream) {                                 \
+    return launch_lbap_check<DT>(d_C, nr, nc, B, d_shape, d_col, d_value, d_wit, d_counts, d_flags,      \
+                                 flags, (hipStream_t)stream);                                            \
   }
 SH_LBAP_ENTRY(i64, int64_t, LBAP_I64)
 SH_LBAP_ENTRY(i32, int32_t, LBAP_I32)

@@ -6364,9 +6364,18 @@ __device__ __forceinline__ uint64_t uniform_u64(uint64_t x) {
   return ((uint64_t)hi << 32) | lo;
 }
 
-template <int NW, int K, int DT>
+// WIT (the witness kernels, below): the searches also leave a Hall violator R,
+// row i in R iff i == *wit_cur or stamp[i] == *wit_cur.  A search whose final
+// path length mv rises strictly above every earlier search's (search 0 always)
+// makes R = {cur} and the rows of the visited columns with spc < mv, written in
+// the path-dump phase, where r4c is still the matching the search ran on.  A
+// search that fails makes R = {cur} and the rows of every visited column, and
+// the early returns become one exit through that store.  Nothing is cleared
+// between searches: a stamp of an earlier rise differs from *wit_cur.
+template <int NW, int K, int DT, bool WIT = false>
 __device__ __forceinline__ int lbap_solve(const typename LbapT<DT>::U *__restrict__ C, const int ld, const int nr,
-                                          const int n, const typename LbapT<DT>::U mask, const LbapLds &S) {
+                                          const int n, const typename LbapT<DT>::U mask, const LbapLds &S,
+                                          int16_t *stamp = nullptr, int *wit_cur = nullptr) {
   using L = LbapT<DT>;
   using U = typename L::U;
   using KT = typename L::KT;
@@ -6382,6 +6391,8 @@ __device__ __forceinline__ int lbap_solve(const typename LbapT<DT>::U *__restric
     path[k] = -1;
   }
   int par = 0;  // slot buffer of the step
+  [[maybe_unused]] KT top = 0;     // WIT: the largest final path length so far
+  [[maybe_unused]] int wcur = -1;  // WIT: the search of the last rise
   for (int cur = 0; cur < nr; ++cur) {
     uint32_t vis = 0, taken = 0;  // (a slot beyond the live columns counts as visited)
 #pragma unroll
@@ -6455,15 +6466,24 @@ __device__ __forceinline__ int lbap_solve(const typename LbapT<DT>::U *__restric
         if constexpr (!K32) gs = (uint32_t)__builtin_amdgcn_readfirstlane((int)gs);
       }
       if constexpr (K32) {
-        if (gk == ~0ull) return -1;  // no column left
+        if (gk == ~0ull) {  // no column left
+          if constexpr (WIT) break;
+          else return -1;
+        }
         gs = (uint32_t)gk;
         mv = (KT)(gk >> 32);
       } else {
-        if (gs == SEC_NONE) return -1;  // no column left
+        if (gs == SEC_NONE) {  // no column left
+          if constexpr (WIT) break;
+          else return -1;
+        }
         mv = (KT)gk;
       }
       if constexpr (L::FLT) {
-        if (mv == ~(KT)0) return -1;  // only forbidden entries lead on: infeasible
+        if (mv == ~(KT)0) {  // only forbidden entries lead on: infeasible
+          if constexpr (WIT) break;
+          else return -1;
+        }
       }
       const int jstar = (int)(gs & 0x7FFFFFFFu);
 #pragma unroll
@@ -6475,13 +6495,39 @@ __device__ __forceinline__ int lbap_solve(const typename LbapT<DT>::U *__restric
       }
       i = __builtin_amdgcn_readfirstlane((int)S.r4c[jstar]);
     }
-    if (sink < 0) return -1;
+    if (sink < 0) {
+      if constexpr (WIT) {  // (every visited column is taken: a free one ends the search)
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+          const int j = tid + WG * k;
+          if (j < n && ((vis >> k) & 1u)) {
+            const int r = S.r4c[j];
+            if (r >= 0) stamp[r] = (int16_t)cur;
+          }
+        }
+        *wit_cur = cur;
+      }
+      return -1;
+    }
+    [[maybe_unused]] bool rise = false;
+    if constexpr (WIT) {
+      rise = cur == 0 || mv > top;
+      if (rise) {
+        top = mv;
+        wcur = cur;
+      }
+    }
     // path dump of the visited columns, then one thread augments from the
     // sink back to cur (<= nr hops), as the min-sum solvers do
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       const int j = tid + WG * k;
-      if (j < n && ((vis >> k) & 1u)) S.path[j] = (int16_t)path[k];
+      if (j < n && ((vis >> k) & 1u)) {
+        S.path[j] = (int16_t)path[k];
+        if constexpr (WIT) {  // (spc < mv: not the sink, so the column is taken)
+          if (rise && spc[k] < mv) stamp[S.r4c[j]] = (int16_t)cur;
+        }
+      }
     }
     __syncthreads();
     if (tid == 0) {
@@ -6498,7 +6544,14 @@ __device__ __forceinline__ int lbap_solve(const typename LbapT<DT>::U *__restric
     }
     __syncthreads();
   }
+  if constexpr (WIT) *wit_cur = wcur;
   return 0;
+}
+
+// The witness kernels' LDS: lbap_kernel's list and stamp[nr] (lbap_solve, WIT).
+#define LBAP_WIT_LDS(X, nr, n, nw) LBAP_LDS(X, nr, n, nw) X(stamp, int16_t, (size_t)nr * 2)
+__host__ __device__ constexpr size_t lbap_wit_lds(int nr, int n, int nw) {
+  return 0 LBAP_WIT_LDS(LDS_BYTES, nr, n, nw);
 }
 
 // One instance a workgroup: NW = 1 is the one-wave design (K columns a lane,
@@ -6559,6 +6612,199 @@ __global__ __launch_bounds__(NW * WAVE) void lbap_kernel(const void *C_, int NR,
       const uint64_t at = __builtin_amdgcn_ballot_w64(have && (uint64_t)bk == top);
       if (tid == (int)__builtin_ctzll(at)) value[b] = braw;
     }
+  }
+}
+
+// The witness solver: lbap_kernel line for line (kept apart so that kernel's
+// code stays what it was), with stamp[] in LDS, lbap_solve in its WIT form and
+// wit uint8 [B, NR]: 1 on the rows of the Hall violator, 0 on the others, on
+// the padded rows and on every row of an empty instance.  (The name is kept
+// clear of lbap_kernel's: the tests count that family by name.)
+template <int NW, int K, int DT>
+__global__ __launch_bounds__(NW * WAVE) void bneck_wit_kernel(const void *C_, int NR, int NC, const int32_t *shape,
+                                                              int32_t *col, void *value_, uint8_t *wit,
+                                                              unsigned flags) {
+  using L = LbapT<DT>;
+  using U = typename L::U;
+  using KT = typename L::KT;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int WG = NW * WAVE;
+  const U *C = (const U *)C_;
+  U *value = (U *)value_;
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const U mask = (flags & SH_FLAG_MAXIMIZE) ? (U)~(U)0 : (U)0;
+  int nr, n;
+  if (!lsap_shape(shape, b, NR, NC, nr, n)) {
+    lsap_no_instance<WG>(col, value, b, NR, NC);
+    for (int i = tid; i < NR; i += WG) wit[(size_t)b * NR + i] = 0;
+    return;
+  }
+  size_t off = 0;
+  LbapLds Sl;
+  int16_t *stamp;
+  LBAP_WIT_LDS(LDS_CARVE, nr, n, NW)
+  for (int i = tid; i < n; i += WG) {
+    if (i < nr) {
+      Sl.c4r[i] = -1;
+      stamp[i] = -1;
+    }
+    Sl.r4c[i] = -1;
+    Sl.path[i] = -1;
+  }
+  __syncthreads();
+  const size_t base = (size_t)b * NR * NC;
+  int wcur = -1;
+  const int st = lbap_solve<NW, K, DT, true>(C + base, NC, nr, n, mask, Sl, stamp, &wcur);
+  __syncthreads();
+  for (int i = tid; i < NR; i += WG) {
+    col[(size_t)b * NR + i] = (st == 0 && i < nr) ? Sl.c4r[i] : -1;
+    wit[(size_t)b * NR + i] = (i < nr && (i == wcur || stamp[i] == wcur)) ? 1 : 0;
+  }
+  if (value && tid < WAVE) {
+    if (st != 0) {
+      if (tid == 0) value[b] = mask ? (U)(L::INFB | L::SIGN) : L::INFB;
+    } else {
+      KT bk = 0;
+      U braw = 0;
+      bool have = false;
+      for (int i = tid; i < nr; i += WAVE) {
+        const U x = C[base + (size_t)i * NC + Sl.c4r[i]];
+        const KT k = lbap_key<DT>(x, mask);
+        if (!have || k > bk) {
+          bk = k;
+          braw = x;
+          have = true;
+        }
+      }
+      const uint64_t top = ~wave_min_u64_dpp(~(uint64_t)bk);
+      const uint64_t at = __builtin_amdgcn_ballot_w64(have && (uint64_t)bk == top);
+      if (tid == (int)__builtin_ctzll(at)) value[b] = braw;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// The certificate of a bottleneck solve: one workgroup per instance, every
+// comparison on lbap_key keys, so it holds for every dtype and the whole int64
+// range.  flags (SH_LBCERT_*):
+//   COL      col is not an assignment of the live rows (SH_CERT_COL's
+//            definition), or an integer instance has every live col == -1
+//   VALUE    the largest key over the chosen entries is not lbap_key(value);
+//            with no chosen entry, value is not the direction's forbidden
+//            infinity (integers have none)
+//   WITNESS  unless nN < nR: nR the live rows with wit != 0 (R), nN the live
+//            columns j with lbap_key(c(i, j)) < lbap_key(value) for some i in R
+//   NONE     every live row has col == -1
+// flags == 0: col is an assignment whose largest entry is value, and the
+// entries strictly below value join R to fewer than |R| columns (Hall), so no
+// assignment stays below value: optimal.  flags == NONE: a forbidden value has
+// the all-ones key, so the same count proves that the entries which are not
+// forbidden hold no assignment.  counts = (nR, nN).
+// R is compacted into LDS (row order does not matter to a count); a thread
+// owns the columns tid + CERT_WG k, so that a row of R is read coalesced, and
+// leaves a column at its first entry below the value.  col and wit are read as
+// data: a col outside [0, nc) is never an index and any nonzero wit counts.
+// ---------------------------------------------------------------------------
+template <int DT>
+__global__ __launch_bounds__(CERT_WG) void bneck_check_kernel(const void *C_, int NR, int NC, const int32_t *shape,
+                                                              const int32_t *col, const void *value_,
+                                                              const uint8_t *wit, int32_t *counts, int32_t *flg,
+                                                              unsigned flags) {
+  using L = LbapT<DT>;
+  using U = typename L::U;
+  using KT = typename L::KT;
+  static_assert(SH_MAX_N_LARGE / 32 <= CERT_WG, "one thread clears one bitmap word");
+  __shared__ uint32_t bits[SH_MAX_N_LARGE / 32];
+  __shared__ int16_t rows[SH_MAX_N_LARGE];
+  __shared__ uint64_t part[CERT_WG / WAVE];
+  __shared__ int s_flags, s_none, s_have, s_nr, s_nn;
+  const U *C = (const U *)C_;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const U mask = (flags & SH_FLAG_MAXIMIZE) ? (U)~(U)0 : (U)0;
+  int nr, nc;
+  if (!lsap_shape(shape, b, NR, NC, nr, nc)) {
+    const bool empty = nr == 0 && nc >= 0 && nc <= NC;
+    if (tid == 0) s_flags = empty ? 0 : SH_LBCERT_COL;  // (else: not a shape of this tensor)
+    __syncthreads();
+    if (empty) {
+      int f = 0;
+      for (int i = tid; i < NR; i += CERT_WG)
+        if (col[(size_t)b * NR + i] != -1) f = SH_LBCERT_COL;
+      if (f) atomicOr(&s_flags, f);
+    }
+    __syncthreads();
+    if (tid == 0) {
+      counts[2 * (size_t)b] = counts[2 * (size_t)b + 1] = 0;
+      flg[b] = s_flags;
+    }
+    return;
+  }
+  if (tid < SH_MAX_N_LARGE / 32) bits[tid] = 0;
+  if (tid == 0) s_flags = s_none = s_have = s_nr = s_nn = 0;
+  __syncthreads();
+  const size_t base = (size_t)b * NR * NC;
+  int f = 0, none = 0;
+  KT top = 0;
+  bool have = false;
+  for (int i = tid; i < NR; i += CERT_WG) {
+    const int c = col[(size_t)b * NR + i];
+    if (i >= nr) {
+      if (c != -1) f |= SH_LBCERT_COL;
+      continue;
+    }
+    if (wit[(size_t)b * NR + i]) rows[atomicAdd(&s_nr, 1)] = (int16_t)i;  // (at most nr <= 4096 appends)
+    if (c == -1) {
+      ++none;
+      continue;
+    }
+    if (c < 0 || c >= nc) {
+      f |= SH_LBCERT_COL;
+      continue;
+    }
+    const uint32_t bit = 1u << (c & 31);
+    if (atomicOr(&bits[c >> 5], bit) & bit) f |= SH_LBCERT_COL;
+    const KT k = lbap_key<DT>(C[base + (size_t)i * NC + c], mask);
+    if (!have || k > top) top = k;
+    have = true;
+  }
+  if (none) atomicAdd(&s_none, none);
+  if (have) atomicOr(&s_have, 1);
+  const uint64_t wtop = ~wave_min_u64_dpp(~(uint64_t)top);  // (a lane without an entry holds key 0)
+  if ((tid & 63) == 0) part[tid >> 6] = wtop;
+  __syncthreads();
+  if (s_none == nr) f |= SH_LBCERT_NONE | (L::FLT ? 0 : SH_LBCERT_COL);
+  else if (s_none) f |= SH_LBCERT_COL;
+  const U vraw = ((const U *)value_)[b];
+  const KT vk = lbap_key<DT>(vraw, mask);
+  if (s_have) {
+    uint64_t t = part[0];
+    for (int q = 1; q < CERT_WG / WAVE; ++q) t = part[q] > t ? part[q] : t;
+    if (t != (uint64_t)vk) f |= SH_LBCERT_VALUE;
+  } else if (!L::FLT || vraw != (mask ? (U)(L::INFB | L::SIGN) : L::INFB)) {
+    f |= SH_LBCERT_VALUE;
+  }
+  const int n_r = s_nr;
+  int nn = 0;
+  for (int j = tid; j < nc; j += CERT_WG) {
+    bool below = false;
+    for (int r = 0; r < n_r && !below; r += 4) {  // four loads in flight (the last row again past the end)
+      U x[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) x[q] = C[base + (size_t)rows[min(r + q, n_r - 1)] * NC + j];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) below |= lbap_key<DT>(x[q], mask) < vk;
+    }
+    nn += below;
+  }
+  if (nn) atomicAdd(&s_nn, nn);
+  if (f) atomicOr(&s_flags, f);
+  __syncthreads();
+  if (tid == 0) {
+    const int n_n = s_nn;
+    counts[2 * (size_t)b] = n_r;
+    counts[2 * (size_t)b + 1] = n_n;
+    flg[b] = s_flags | (n_n < n_r ? 0 : SH_LBCERT_WITNESS);
   }
 }
 

@@ -24,7 +24,7 @@ from .lsap import (check_duals, check_duals_large, csr_transpose, densify,  # no
                    linear_sum_assignment, linear_sum_assignment_duals, linear_sum_assignment_large,
                    linear_sum_assignment_sparse, solve_batched, solve_batched_large, solve_batched_sparse,
                    solve_hash, validate_csr)
-from .lbap import linear_bottleneck_assignment, solve_bottleneck_batched  # noqa: F401
+from .lbap import check_bottleneck, linear_bottleneck_assignment, solve_bottleneck_batched  # noqa: F401
 
 lib()  # load the C-ABI at import: no silent CPU path
 
@@ -34,7 +34,7 @@ __all__ = [
     "linear_sum_assignment", "linear_sum_assignment_duals", "solve_batched", "check_duals", "solve_hash",
     "linear_sum_assignment_large", "solve_batched_large", "check_duals_large",
     "linear_sum_assignment_sparse", "solve_batched_sparse", "densify", "csr_transpose", "validate_csr",
-    "linear_bottleneck_assignment", "solve_bottleneck_batched",
+    "linear_bottleneck_assignment", "solve_bottleneck_batched", "check_bottleneck",
     "SH_CERT_COL", "SH_CERT_SLACK", "SH_CERT_TIGHT", "SH_CERT_SIGN", "SH_CERT_GAP", "SH_CERT_NONE",
     "SH_CERT_RANGE", "my_optimizer", "run_rounds",
     "SantaGPU", "score_from_sums", "SantaHipError",

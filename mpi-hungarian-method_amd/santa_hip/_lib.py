@@ -46,6 +46,11 @@ SH_CERT_SIGN = 8
 SH_CERT_GAP = 16
 SH_CERT_NONE = 32
 SH_CERT_RANGE = 64
+# lbap_check_ flag bits
+SH_LBCERT_COL = 1
+SH_LBCERT_VALUE = 2
+SH_LBCERT_WITNESS = 4
+SH_LBCERT_NONE = 8
 SH_ERRF_ROWS = 1
 SH_ERRF_INFEASIBLE = 2
 SH_ERRF_TYPE = 4
@@ -143,6 +148,10 @@ for _suf in ("i64", "i32", "f64", "f32", "f16", "bf16"):  # the duals / check_du
     SIGNATURES["lsap_check_duals_large_" + _suf] = SIGNATURES["lsap_check_duals_" + _suf]
     # bottleneck assignment: C, nr, nc, B, shape, col, value, flags, stream
     SIGNATURES["lbap_solve_" + _suf] = (_I, [_P, _I, _I, _I, _P, _P, _P, _U, _P])
+    # ... with the witness: C, nr, nc, B, shape, col, value, wit, flags, stream
+    SIGNATURES["lbap_solve_wit_" + _suf] = (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _U, _P])
+    # its certificate: C, nr, nc, B, shape, col, value, wit, counts, flags out, flags, stream
+    SIGNATURES["lbap_check_" + _suf] = (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _U, _P])
 # the sparse (CSR) float entries: indptr, indices, data, nr, nc, B, shape, col, cost, u, v, work, work_bytes, flags, stream
 SIGNATURES["lsap_csr_work_bytes"] = (ctypes.c_size_t, [_I, _I, _I])
 for _suf in ("f64", "f32"):

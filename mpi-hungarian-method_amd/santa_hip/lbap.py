@@ -13,6 +13,13 @@ Forbidden pairs are +inf and NaN of the floating-point dtypes (-inf and NaN
 under maximize); integers have none.  Optima are far from unique: the solver
 returns the one its search order defines, the same in every
 kernel configuration, which tests/lbap_ref.py replays on the host.
+
+An answer can be proved without that replay.  With witness=True the solver
+also returns a Hall violator: rows R which the entries strictly below `value`
+join to fewer than |R| columns, so that no assignment of every row stays below
+`value`; check_bottleneck counts both on the device and flags == 0 proves an
+instance optimal (flags == SH_LBCERT_NONE: infeasible), for every dtype and
+the whole int64 range.
 """
 from __future__ import annotations
 
@@ -21,11 +28,28 @@ import torch
 
 from . import _lib
 from .context import current_stream_handle, require_gpu
-from .lsap import DTYPE_SUFFIX, _p, check_shapes, invert_tall, tall_result
+from .lsap import DTYPE_SUFFIX, _p, check_shapes, invert_col, invert_tall, tall_result
+
+
+def _check_batch(C: torch.Tensor, shapes):
+    """The argument errors of the bottleneck entries -> the host shapes or None."""
+    if C.dim() != 3:
+        raise ValueError("expected [B, NR, NC]")
+    B, NR, NC = C.shape
+    if max(NR, NC) > _lib.SH_MAX_N_LARGE:
+        raise ValueError(f"max(NR, NC) = {max(NR, NC)} > {_lib.SH_MAX_N_LARGE}")
+    if C.dtype not in DTYPE_SUFFIX:
+        raise TypeError(f"unsupported dtype {C.dtype}")
+    if shapes is None:
+        return None
+    if NR > NC:
+        raise ValueError(f"a ragged batch must be padded wide, got [{NR}, {NC}]: "
+                         "transpose the batch so that every instance has nr <= nc")
+    return check_shapes(shapes, B, NR, NC)
 
 
 def solve_bottleneck_batched(C: torch.Tensor, with_value: bool = True, flags: int = 0, shapes=None,
-                             maximize: bool = False):
+                             maximize: bool = False, witness: bool = False):
     """C: device tensor [B, NR, NC] (int64 / int32 / float64 / float32 /
     float16 / bfloat16) -> (col int32 [B, NR], value [B] of C.dtype, or None
     without with_value).
@@ -45,24 +69,23 @@ def solve_bottleneck_batched(C: torch.Tensor, with_value: bool = True, flags: in
     maximize reverses the order of the costs and never negates them.  There
     is no int64 range check and none is needed: the whole int64 range is
     solved exactly, INT64_MIN and INT64_MAX included.  Raises as solve_batched
-    does: ValueError for rank, size and shapes, TypeError for the dtype."""
-    if C.dim() != 3:
-        raise ValueError("expected [B, NR, NC]")
+    does: ValueError for rank, size and shapes, TypeError for the dtype.
+
+    witness=True returns (col, value, wit) from the lbap_solve_wit_ entries,
+    col and value the same bits.  wit (uint8) marks a Hall violator R with 1:
+    the entries strictly below value[b] (above, under maximize) join the lines
+    of R to fewer than |R| lines of the other side, which proves value[b]
+    optimal; for an infeasible instance the same holds of the entries that are
+    not forbidden.  wit is [B, min(NR, NC)] over the SHORTER side: rows of a
+    wide batch, and, since a tall batch is solved as its transpose, [B, NC]
+    over the columns of a tall one.  Padded rows and empty instances are 0."""
+    shape_host = _check_batch(C, shapes)
     B, NR, NC = C.shape
-    if max(NR, NC) > _lib.SH_MAX_N_LARGE:
-        raise ValueError(f"max(NR, NC) = {max(NR, NC)} > {_lib.SH_MAX_N_LARGE}")
-    if C.dtype not in DTYPE_SUFFIX:
-        raise TypeError(f"unsupported dtype {C.dtype}")
-    shape_host = None
-    if shapes is not None:
-        if NR > NC:
-            raise ValueError(f"a ragged batch must be padded wide, got [{NR}, {NC}]: "
-                             "transpose the batch so that every instance has nr <= nc")
-        shape_host = check_shapes(shapes, B, NR, NC)
     dev = C.device
     if B == 0 or NR == 0 or NC == 0:
-        return (torch.full((B, NR), -1, dtype=torch.int32, device=dev),
-                torch.zeros(B, dtype=C.dtype, device=dev) if with_value else None)
+        empty = (torch.full((B, NR), -1, dtype=torch.int32, device=dev),
+                 torch.zeros(B, dtype=C.dtype, device=dev) if with_value else None)
+        return empty + (torch.zeros((B, min(NR, NC)), dtype=torch.uint8, device=dev),) if witness else empty
     require_gpu()
     shape_dev = torch.from_numpy(shape_host).to(dev) if shape_host is not None else None
     tall = NR > NC
@@ -71,10 +94,66 @@ def solve_bottleneck_batched(C: torch.Tensor, with_value: bool = True, flags: in
     col = torch.empty((B, nr), dtype=torch.int32, device=dev)
     value = torch.empty(B, dtype=C.dtype, device=dev) if with_value else None
     fl = flags | (_lib.SH_FLAG_MAXIMIZE if maximize else 0)
+    if witness:
+        wit = torch.empty((B, nr), dtype=torch.uint8, device=dev)
+        rc = getattr(_lib.lib(), "lbap_solve_wit_" + DTYPE_SUFFIX[C.dtype])(
+            _p(Cw), nr, nc, B, _p(shape_dev), _p(col), _p(value), _p(wit), fl, current_stream_handle(dev))
+        _lib.check(rc, "lbap_solve_wit")
+        return (invert_tall(col, NR) if tall else col), value, wit
     rc = getattr(_lib.lib(), "lbap_solve_" + DTYPE_SUFFIX[C.dtype])(
         _p(Cw), nr, nc, B, _p(shape_dev), _p(col), _p(value), fl, current_stream_handle(dev))
     _lib.check(rc, "lbap_solve")
     return (invert_tall(col, NR) if tall else col), value
+
+
+def check_bottleneck(C: torch.Tensor, col: torch.Tensor, value: torch.Tensor, wit: torch.Tensor, shapes=None,
+                     maximize: bool = False):
+    """The certificate of a bottleneck solve, on the device (lbap_check_
+    entries) -> (nR int32 [B], nN int32 [B], flags int32 [B]).
+
+    C, col, value and wit as solve_bottleneck_batched(witness=True) takes and
+    returns them: col [B, NR], value [B] of C.dtype, wit uint8 [B, min(NR, NC)].
+    nR is the number of live lines marked in wit and nN the number of live lines
+    of the other side that an entry strictly better than value[b] joins to one
+    of them.  flags holds SH_LBCERT_* bits:
+      COL      col is not an assignment of the live rows (integers: or is all -1)
+      VALUE    value is not the largest chosen entry (smallest under maximize;
+               -0.0 equals +0.0), or col is all -1 and value not the forbidden
+               infinity
+      WITNESS  not nN < nR: wit does not prove the value
+      NONE     every live row has col == -1
+    flags == 0 proves instance b optimal and flags == SH_LBCERT_NONE proves it
+    infeasible, by comparisons alone: every dtype, int64 over its whole range.
+    An empty instance gives 0 and (0, 0).  A tall batch is checked as its
+    transpose, with col inverted on the device.  Raises as the solver does."""
+    shape_host = _check_batch(C, shapes)
+    B, NR, NC = C.shape
+    if tuple(col.shape) != (B, NR) or tuple(value.shape) != (B,) or tuple(wit.shape) != (B, min(NR, NC)):
+        raise ValueError(f"expected col [{B}, {NR}], value [{B}] and wit [{B}, {min(NR, NC)}]")
+    if value.dtype != C.dtype or wit.dtype not in (torch.uint8, torch.bool):
+        raise TypeError(f"value must be {C.dtype} and wit uint8 or bool")
+    dev = C.device
+    counts = torch.zeros((B, 2), dtype=torch.int32, device=dev)
+    flags = torch.zeros(B, dtype=torch.int32, device=dev)
+    if B == 0 or NR == 0 or NC == 0:
+        return counts[:, 0], counts[:, 1], flags
+    require_gpu()
+    shape_dev = torch.from_numpy(shape_host).to(dev) if shape_host is not None else None
+    col = col.to(torch.int32)
+    bad = None
+    if NR > NC:
+        C = C.transpose(1, 2)
+        col, bad = invert_col(col, NC)
+        NR, NC = NC, NR
+    C, col, value = C.contiguous(), col.contiguous(), value.contiguous()
+    wit = wit.to(torch.uint8).contiguous()
+    rc = getattr(_lib.lib(), "lbap_check_" + DTYPE_SUFFIX[C.dtype])(
+        _p(C), NR, NC, B, _p(shape_dev), _p(col), _p(value), _p(wit), _p(counts), _p(flags),
+        _lib.SH_FLAG_MAXIMIZE if maximize else 0, current_stream_handle(dev))
+    _lib.check(rc, "lbap_check")
+    if bad is not None:  # a tall col that was no assignment before its inversion
+        flags = flags | (bad.to(torch.int32) * _lib.SH_LBCERT_COL)
+    return counts[:, 0], counts[:, 1], flags
 
 
 def _widen(C: np.ndarray) -> np.ndarray:
@@ -97,7 +176,8 @@ def _widen(C: np.ndarray) -> np.ndarray:
     raise TypeError(f"unsupported dtype {C.dtype}")
 
 
-def linear_bottleneck_assignment(cost_matrix, maximize: bool = False, device: int | str = 0):
+def linear_bottleneck_assignment(cost_matrix, maximize: bool = False, device: int | str = 0,
+                                 witness: bool = False):
     """One matrix -> (row_ind, col_ind, value): the assignment of every row of
     the shorter side that minimises the largest chosen cost (maximises the
     smallest with maximize), row_ind and col_ind as
@@ -105,6 +185,11 @@ def linear_bottleneck_assignment(cost_matrix, maximize: bool = False, device: in
     the columns; tall: the rows kept, sorted, with their columns), value a
     numpy scalar of the input's (widened) dtype equal to
     cost_matrix[row_ind, col_ind].max() (min with maximize).
+
+    witness=True returns (row_ind, col_ind, value, wit): wit a bool array over
+    the shorter side (rows of a wide matrix, columns of a tall one) marking a
+    Hall violator, the proof that no assignment beats value (see
+    solve_bottleneck_batched and check_bottleneck).
 
     ValueError("matrix contains invalid numeric entries") on NaN,
     ValueError("cost matrix is infeasible") when no full matching of the
@@ -116,7 +201,7 @@ def linear_bottleneck_assignment(cost_matrix, maximize: bool = False, device: in
     nr, nc = C.shape
     if nr == 0 or nc == 0:
         z = np.zeros(0, dtype=np.int64)
-        return z, z.copy(), C.dtype.type(0)
+        return (z, z.copy(), C.dtype.type(0)) + ((np.zeros(0, dtype=bool),) if witness else ())
     if max(nr, nc) > _lib.SH_MAX_N_LARGE:
         raise ValueError(f"max(nr, nc) = {max(nr, nc)} > {_lib.SH_MAX_N_LARGE}")
     if np.issubdtype(C.dtype, np.floating) and np.isnan(C).any():
@@ -126,9 +211,9 @@ def linear_bottleneck_assignment(cost_matrix, maximize: bool = False, device: in
         C = C.T
     dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
     Ct = torch.from_numpy(np.ascontiguousarray(C)).to(dev)
-    col, value = solve_bottleneck_batched(Ct.unsqueeze(0), maximize=maximize)
+    col, value, *wit = solve_bottleneck_batched(Ct.unsqueeze(0), maximize=maximize, witness=witness)
     col = col[0].cpu().numpy().astype(np.int64)
     if (col < 0).any():
         raise ValueError("cost matrix is infeasible")
     rows, cols = tall_result(col) if tall else (np.arange(col.size, dtype=np.int64), col)
-    return rows, cols, value.cpu().numpy()[0]
+    return (rows, cols, value.cpu().numpy()[0]) + ((wit[0][0].cpu().numpy().astype(bool),) if witness else ())
