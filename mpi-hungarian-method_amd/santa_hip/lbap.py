@@ -28,7 +28,7 @@ import torch
 
 from . import _lib
 from .context import current_stream_handle, require_gpu
-from .lsap import DTYPE_SUFFIX, _p, check_shapes, invert_col, invert_tall, tall_result
+from .lsap import DTYPE_SUFFIX, _p, check_shapes, invert_col, invert_tall, narrow_col, tall_result
 
 
 def _check_batch(C: torch.Tensor, shapes):
@@ -132,6 +132,7 @@ def check_bottleneck(C: torch.Tensor, col: torch.Tensor, value: torch.Tensor, wi
         raise ValueError(f"expected col [{B}, {NR}], value [{B}] and wit [{B}, {min(NR, NC)}]")
     if value.dtype != C.dtype or wit.dtype not in (torch.uint8, torch.bool):
         raise TypeError(f"value must be {C.dtype} and wit uint8 or bool")
+    col = narrow_col(col)
     dev = C.device
     counts = torch.zeros((B, 2), dtype=torch.int32, device=dev)
     flags = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -139,7 +140,6 @@ def check_bottleneck(C: torch.Tensor, col: torch.Tensor, value: torch.Tensor, wi
         return counts[:, 0], counts[:, 1], flags
     require_gpu()
     shape_dev = torch.from_numpy(shape_host).to(dev) if shape_host is not None else None
-    col = col.to(torch.int32)
     bad = None
     if NR > NC:
         C = C.transpose(1, 2)

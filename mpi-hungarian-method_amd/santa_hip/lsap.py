@@ -101,6 +101,24 @@ def invert_col(col: torch.Tensor, n: int):
     return inv, bad
 
 
+_INT32_MIN, _INT32_MAX = -(1 << 31), (1 << 31) - 1
+
+
+def narrow_col(col: torch.Tensor) -> torch.Tensor:
+    """col of any signed integer dtype (or uint8) as the int32 the certificate
+    entries read.  A value outside int32 saturates to INT32_MAX or INT32_MIN,
+    which no kernel takes for a column (they flag it and never index with it);
+    wrapping it would turn 2**32 + 3 into column 3.  TypeError for any other
+    dtype."""
+    if col.dtype == torch.int32:
+        return col
+    if col.dtype == torch.int64:
+        return col.clamp(_INT32_MIN, _INT32_MAX).to(torch.int32)
+    if col.dtype in (torch.int16, torch.int8, torch.uint8):
+        return col.to(torch.int32)
+    raise TypeError(f"col must be an integer tensor, got {col.dtype}")
+
+
 def tall_result(col_t):
     """scipy's (row_ind, col_ind) of a tall matrix from the solution col_t of
     its transpose: rows sorted ascending, each with its column."""
@@ -280,7 +298,9 @@ def check_duals(C: torch.Tensor, col: torch.Tensor, u: torch.Tensor, v: torch.Te
                  instance optimal.
     maximize certifies the negated problem (-C, -u, -v), so the same signs
     hold.  A tall batch is checked as its transpose (a contiguous copy) with
-    the duals swapped and col inverted."""
+    the duals swapped and col inverted.  col may have any integer dtype
+    (TypeError otherwise); an int64 entry outside int32 is no column and sets
+    SH_CERT_COL."""
     return _check_duals(C, col, u, v, shapes, maximize, False)
 
 
@@ -307,6 +327,7 @@ def _check_duals(C, col, u, v, shapes, maximize, large):
         raise ValueError(f"expected col and u of shape [{B}, {NR}] and v of shape [{B}, {NC}]")
     if u.dtype != ddt or v.dtype != ddt:
         raise TypeError(f"the duals of {C.dtype} costs are {ddt}")
+    col = narrow_col(col)
     dev = C.device
     shape_dev = None
     if shapes is not None:
@@ -318,7 +339,6 @@ def _check_duals(C, col, u, v, shapes, maximize, large):
     slack = torch.zeros((B, 3), dtype=ddt, device=dev)
     if B == 0 or NR == 0 or NC == 0:
         return slack[:, 0], slack[:, 1], slack[:, 2], flags
-    col = col.to(torch.int32)
     if maximize:
         C, u, v = -(C.to(torch.int64) if C.dtype == torch.int32 else C), -u, -v
     bad = None
