@@ -3242,6 +3242,23 @@ __global__ __launch_bounds__(TILE_NW * WAVE) __attribute__((amdgpu_waves_per_eu(
 // (64, 16, 4), (16, 4, 1) and none (profiles/r03_sp3_prio_ab.jsonl).
 constexpr int SP3_PRIO_A = 32, SP3_PRIO_B = 8, SP3_PRIO_C = 2;
 
+// wave_min_u32_dpp for santa_sp3_kernel, whose step reads `best` again after
+// the chain (the winner's lane): dpp_min_step ties the level's destination to
+// its source, so the chain's seed was a copy of `best`.  The first level has
+// every row and bank enabled and a quad permutation reads only valid lanes,
+// so no lane keeps an old value: with bound_ctrl it has no tied operand and
+// writes a fresh register from `best` itself.
+__device__ __forceinline__ uint32_t sp3_wave_min_u32_dpp(uint32_t x) {
+  const uint32_t y = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xF, 0xF, true);  // quad_perm [1,0,3,2]
+  x = y < x ? y : x;
+  x = dpp_min_step<0x4E, 0xF>(x);   // quad_perm [2,3,0,1]
+  x = dpp_min_step<0x141, 0xF>(x);  // row_half_mirror
+  x = dpp_min_step<0x140, 0xF>(x);  // row_mirror
+  x = dpp_min_step<0x142, 0xA>(x);  // row_bcast:15 -> rows 1, 3
+  x = dpp_min_step<0x143, 0xC>(x);  // row_bcast:31 -> rows 2, 3
+  return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
+}
+
 // santa_sp3_kernel's LDS (static: every address is a constant offset).
 // Record design (santa_tile_kernel builds the tile, FUSED = false):
 struct Sp3LdsRecord {
@@ -3564,7 +3581,7 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
       __syncthreads();  // (the next batch rewrites the stage)
     }
   }
-  for (int r = lane; r < n; r += WAVE) u_l[r] = 0;
+  for (int r = lane; r < n; r += WAVE) u_l[r] = SP3_BIAS;  // (u = 0: u_l holds u + BIAS, see the solve)
   const int nw1 = a.n_wish + 1;
   const int64_t E = a.E;
   // row values in key units (V << SP3_SH, see the solve below)
@@ -3591,9 +3608,19 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
   //        one min keeps scipy's strict < and needs no compare or path select
   //        (round 4: 3 VALU per column per step instead of 5); the path's row
   //        is the row of step t (rowq, below); ~0: not reached
-  //   W    -v_V (the range check, the outputs), Wp = W << SP3_SH (relaxation)
+  //   W    -v_V (the range check, the outputs), Wp = (W << SP3_SH) + 2^31 (relaxation)
   //   lo   key tie-break bits (class << 10 | pkey << 2 | k); ~0: left
   //        `remaining` this Dijkstra (or j >= n)
+  // The key field's bias is carried in state, not added per step.  A
+  // relaxation value is r = (W + C + BIAS - u~) << SH | t with u~ = u - minVal
+  // and BIAS << SH = 2^31.  Wp holds the 2^31, and u_l holds u + BIAS, so with
+  // mvb = minVal + BIAS a step reads bu = mvb - u_l[i] = -u~ and forms
+  //   r = Wp + C_key + ((bu << SH) | t)
+  //     = (W << SH) + 2^31 + (C << SH) + ((-u~ << SH) | t)          (mod 2^32)
+  // which is the same word, since ((x - 2^20) << 11) = (x << 11) - 2^31 mod
+  // 2^32 and the low SH bits of bu << SH are 0.  The first step (u~ = 0,
+  // t = 0) is Wp + C_key alone; a single-step Dijkstra stores u_l[cur] = mvb
+  // (u = minVal); the range terms and the outputs subtract the constant.
   uint32_t sbp[4];
   int32_t W[4], Wp[4];
   u32x4 lo;            // (one VGPR tuple: a step's book-keeping writes lo[k] by an indexed move)
@@ -3608,7 +3635,7 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     W[k] = 0;
-    Wp[k] = 0;
+    Wp[k] = (int32_t)((uint32_t)SP3_BIAS << SP3_SH);
     const int j = 4 * lane + k;
     LI[k] = j < n ? (((uint32_t)(n - 1 - j) << 2) | (uint32_t)k) ^ 0x3FCu : ~0u;
   }
@@ -3663,6 +3690,10 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
     //  Dijkstra's scalar branches and operands turn into lane masks and VGPRs)
     int np = n;
     asm volatile("" : "+s"(np));
+    // (the factor of an entry's value in key units, a rank a -> -(a << 20):
+    //  it fits the 24-bit multiply's signed operand)
+    int32_t svm = -(1 << (9 + SP3_SH));
+    asm volatile("" : "+s"(svm));
     // Two nested loops over the Dijkstras.  The inner one runs consecutive
     // single-step Dijkstras (the common case) and carries only what that path
     // changes -- c4r, r4c, LI, cur, steps -- so its back edge copies no
@@ -3720,7 +3751,8 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
         // expand the row: hit columns get -a (key units), the rest hold a
         // miss; read this lane's four columns; put the misses back (in-order LDS)
         e.sslot = mine ? (int)__builtin_amdgcn_ubfe(tw, sh, 9) : 256 + x31;
-        e.sval = -(int32_t)(e.ea << (9 + SP3_SH));
+        // (-(ea << 20) as one VALU: a 24-bit multiply by -2^20 held in an SGPR; ea <= 127)
+        asm("v_mul_i32_i24 %0, %1, %2" : "=v"(e.sval) : "s"(svm), "v"(e.ea));
         if constexpr (TIMED) {  // (A1: the tile fetch and the entry's fields)
           asm volatile("" ::"v"(e.sslot), "v"(e.sval));
           stamp(tA1);
@@ -3832,17 +3864,18 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
         }
         const int32_t cc[4] = {c01.x, c01.y, c23.x, c23.y};
         // u~[i] = u[i] - minVal (row i is reached at the current minimum),
-        // its range and the step's value (BIAS - u~) in key units with the
+        // its range and the step's value (-u~) in key units with the
         // step t in the low byte: uniform values left in VGPRs -- four VALU
         // instead of a readfirstlane and seven SALU (the scalar unit is the
         // step's shared resource: every SALU removed shortened the round,
         // profiles/r05t_sp3_valu_addr_ab.jsonl)
-        // (BIAS - u~ = mvb - u: the range term u~ + CU is (BIAS + CU) - that)
-        // (FIRST: u~ = 0 is in range, CU has no bit of MU; the value is BIAS, t = 0)
-        uint32_t bse = (uint32_t)SP3_BIAS << SP3_SH;
+        // (-u~ = mvb - u_l[i], both biased: the range term u~ + CU is CU - that;
+        //  the value's BIAS is in Wp, see the state above)
+        // (FIRST: u~ = 0 is in range, CU has no bit of MU; the step adds nothing, t = 0)
+        uint32_t bse = 0u;
         if constexpr (!FIRST) {
           const uint32_t bu = mvb - (uint32_t)uraw;
-          accU |= ((uint32_t)SP3_BIAS + LR.CU) - bu;
+          accU |= LR.CU - bu;
           bse = (bu << SP3_SH) | (uint32_t)(n - nrem);
         }
         if constexpr (TIMED) {
@@ -3869,7 +3902,16 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
         // the DPP chain's wait states, one readlane of it below gives the next
         // row (the bit-field offset is (best << 3) mod 32)
         rsel = __builtin_amdgcn_ubfe(r4c, best << 3, 8);
-        g = wave_min_u32_dpp(best);
+        // (the mover's decode and the new last position do not depend on the
+        //  argmin: ahead of the chain in source order, for its wait states)
+        int last = 0;
+        if constexpr (!FIRST) {
+          const int mv = __builtin_amdgcn_readfirstlane(mover_v);
+          mmask = 1ull << (mv >> 2);
+          kmv = mv & 3;
+          last = nrem - 1;
+        }
+        g = sp3_wave_min_u32_dpp(best);
         if constexpr (TIMED) {
           asm volatile("" ::"s"(g));
           stamp(tB);
@@ -3879,14 +3921,12 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
         assigned = g & (1u << 10);
         if constexpr (!FIRST) {  // (the peeled step's tail or hand-over decodes the rest, below)
           const uint32_t pkey = (g >> 2) & 255u;
-          const int lw = (int)__builtin_ctzll(__builtin_amdgcn_ballot_w64(best == g));
+          // (the winner's lane is the one lane holding the key: the compare's
+          //  mask is the book-keeping's lane mask as it stands)
+          wmask = __builtin_amdgcn_ballot_w64(best == g);
+          const int lw = (int)__builtin_ctzll(wmask);
           const int pstar = assigned ? (int)pkey : 255 - (int)pkey;
-          const int last = nrem - 1;
           asm("v_lshlrev_b32 %0, 2, %1" : "=v"(kX) : "s"(last ^ pstar));
-          wmask = 1ull << lw;
-          const int mv = __builtin_amdgcn_readfirstlane(mover_v);
-          mmask = 1ull << (mv >> 2);
-          kmv = mv & 3;
           {  // rem[pstar] = mover (every lane, same word; a no-op when pstar == last)
             uint32_t pa;
             asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(pa) : "s"(pstar), "v"(remv));
@@ -3904,9 +3944,14 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
       int lw;
       bool multi = false;
       do {
-        if (cur == np - SP3_PRIO_A) __builtin_amdgcn_s_setprio(2);  // (issue priority, above)
-        if (cur == np - SP3_PRIO_B) __builtin_amdgcn_s_setprio(1);
-        if (cur == np - SP3_PRIO_C) __builtin_amdgcn_s_setprio(0);
+        // (issue priority, above: the three thresholds behind one test, so a
+        //  Dijkstra before the first of them pays one compare and branch; at
+        //  n < 32, np - 32 < 0 <= cur and every Dijkstra takes the three)
+        if (__builtin_expect(cur >= np - SP3_PRIO_A, 0)) {
+          if (cur == np - SP3_PRIO_A) __builtin_amdgcn_s_setprio(2);
+          if (cur == np - SP3_PRIO_B) __builtin_amdgcn_s_setprio(1);
+          if (cur == np - SP3_PRIO_C) __builtin_amdgcn_s_setprio(0);
+        }
         first = true;
         i = cur;  // (the step's row: its overflow range is read by it)
         step(std::true_type{}, fetch(cur, T0[(cur >> 2) & 31], T1[(cur >> 2) & 31]));
@@ -3929,8 +3974,8 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
         {
           uint32_t ua;
           asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(ua) : "s"(cur), "v"(ubv));
-          const int32_t mval = (int32_t)mvb - SP3_BIAS;
-          asm volatile("ds_write_b32 %0, %1" ::"v"(ua), "v"(mval) : "memory");
+          // (u[cur] = minVal: u_l holds u + BIAS, which is mvb itself)
+          asm volatile("ds_write_b32 %0, %1" ::"v"(ua), "v"(mvb) : "memory");
         }
         const uint32_t dl = (uint32_t)cur - 2u * (uint32_t)ro0;  // cur - 4 lane: the row's byte in its lane
         c4r ^= dl < 4u ? (0xFFu ^ (uint32_t)sink) << (8u * dl) : 0u;
@@ -3999,7 +4044,8 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
         if (vk) {
           const int32_t dd = (int32_t)(mvb - (sbp[k] >> SP3_SH));
           W[k] += dd;
-          Wp[k] = (int32_t)((uint32_t)W[k] << SP3_SH);
+          // (compiled as a shift and a v_xor of 2^31, not one v_lshl_add: DESIGN 4.0b)
+          Wp[k] = (int32_t)(((uint32_t)W[k] << SP3_SH) + ((uint32_t)SP3_BIAS << SP3_SH));
           __hip_atomic_fetch_add(u_l + ((r4c >> (8 * k)) & 0xFFu), dd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
           prow[k] = (int32_t)rowq[n - 1 - (int)(sbp[k] & 0xFFu)];
         }
@@ -4053,8 +4099,8 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
   {  // the lattice range (see above): leave the block to the fallback launch
     bool big = bad || ((accU & LR.MU) | (accW & LR.MW)) != 0;
 #pragma unroll
-    for (int k = 0; k < 4; ++k)  // (the output decode's u)
-      if (4 * lq + k < n) big |= (((uint32_t)u_l[4 * lq + k] + LR.CU) & LR.MU) != 0;
+    for (int k = 0; k < 4; ++k)  // (the output decode's u; u_l holds u + BIAS)
+      if (4 * lq + k < n) big |= (((uint32_t)u_l[4 * lq + k] + (LR.CU - (uint32_t)SP3_BIAS)) & LR.MU) != 0;
     if (__builtin_expect(__any(big), 0)) {
       if (lane == 0) leave_to_fallback(a, b);
       return;
@@ -4091,7 +4137,8 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
         cost += single_cost(co, nw1, E);
       } else {
         // C_V = u + v on the matched (tight) edge: a miss (A 0, m 1) or a wish (-a, 0)
-        const int32_t cv = u_l[i] + vcol;
+        // (u_l holds u + BIAS)
+        const int32_t cv = (int32_t)((uint32_t)u_l[i] - (uint32_t)SP3_BIAS + (uint32_t)vcol);
         const int32_t mc = ((cv + 256) & 511) - 256;
         const int32_t ac = (cv - mc) >> 9;
         const int64_t cij = (int64_t)ac * 4294967296LL + (int64_t)mc * E;
