@@ -552,6 +552,60 @@ int lsap_check_duals_large_bf16(const uint16_t *d_C, int nr, int nc, int B, cons
                                double *d_slack, int32_t *d_flags, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Warm start: re-solve a batch from a previous assignment and its column
+ * duals, 1 <= nr <= nc <= SH_MAX_N_LARGE.
+ *
+ *   d_col [B x nr]  in: the previous assignment (col of row i); out: the result
+ *   d_v   [B x nc]  in: the previous column duals; out: the final ones
+ *   d_u   [B x nr]  out: the final row duals (row duals are not an input: they
+ *                   are recomputed from C and v)
+ *   d_cost [B]      out, nullable
+ *   d_kept [B]      out, nullable: the pairs of the previous assignment that
+ *                   were kept; the solve runs exactly nr_b - kept Dijkstras
+ *
+ * The previous state is read as data and may be anything: a value of d_v
+ * outside the window (integers: [-2^56, 0]; floats: finite and <= 0) counts as
+ * 0, an entry of d_col outside [0, nc_b) as "no column", and of two rows on one
+ * column the lower keeps it.  A first launch turns it into a valid state for
+ * THIS d_C (u[i] = min_j (C[i][j] - v[j]); a pair is kept iff it is tight; with
+ * nr < nc the column duals of free and of broken columns are raised to 0, which
+ * may break further pairs), a second one runs the solver of the entries above
+ * from that state.
+ *
+ * Outputs and padding as the _duals_ entries': padded rows get -1, padded slots
+ * 0; an empty or invalid shape gives -1, cost 0, zero duals, kept 0; an
+ * infeasible float instance -1 everywhere, cost 0 and NaN duals in the live
+ * slots (kept 0 where a row holds nothing but +inf); integer duals are exact,
+ * with the signs and equalities lsap_check_duals_large_* tests.  d_col is an
+ * optimal assignment and d_cost the optimum; among several optimal assignments
+ * it need not be the one the cold entries (and scipy) return.  For a given
+ * input the outputs do not depend on the launch configuration.
+ *
+ * flags: SH_FLAG_EXACT_ARGMIN as on the integer entries above.
+ * SH_FLAG_BUILD_ONLY runs the first launch alone and leaves d_col (the kept
+ * pairs, -1 elsewhere), d_u, d_v and d_kept as it made them, d_cost untouched.
+ * SH_FLAG_F64_MW / SH_FLAG_F64_SW are ignored: there is one float kernel per
+ * size.  i64: |C| < 2^50 up to 1024 columns and < 2^48 above, as before.
+ *
+ * The entries allocate nothing and never synchronise.  SH_ERR_ARGS, checked on
+ * the host before any device call, for: nr < 1, nr > nc, nc > SH_MAX_N_LARGE,
+ * B < 0; with B > 0 a null d_C, d_col, d_u or d_v.  B == 0 is a no-op after the
+ * checks.
+ * ------------------------------------------------------------------------ */
+int lsap_warm_i64(const int64_t *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,
+                  int64_t *d_cost, int64_t *d_u, int64_t *d_v, int32_t *d_kept, unsigned flags, void *stream);
+int lsap_warm_i32(const int32_t *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,
+                  int64_t *d_cost, int64_t *d_u, int64_t *d_v, int32_t *d_kept, unsigned flags, void *stream);
+int lsap_warm_f64(const double *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,
+                  double *d_cost, double *d_u, double *d_v, int32_t *d_kept, unsigned flags, void *stream);
+int lsap_warm_f32(const float *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,
+                  double *d_cost, double *d_u, double *d_v, int32_t *d_kept, unsigned flags, void *stream);
+int lsap_warm_f16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,
+                  double *d_cost, double *d_u, double *d_v, int32_t *d_kept, unsigned flags, void *stream);
+int lsap_warm_bf16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,
+                   double *d_cost, double *d_u, double *d_v, int32_t *d_kept, unsigned flags, void *stream);
+
+/* ---------------------------------------------------------------------------
  * The batched float solver on sparse (CSR) costs, a missing entry being a
  * forbidden pair: a sparse instance is solved exactly as the dense float
  * solver solves its densification, the nr x nc float64 matrix that holds each

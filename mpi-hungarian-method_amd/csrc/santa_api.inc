@@ -1149,6 +1149,56 @@ static_assert(lsap_f64_mw_lds(3073, 3073, 8, 12) == 43328);
 static_assert(lsap_f64_mw_lds(4096, 4096, 8, 12) == 57600);
 static_assert(lsap_f64_mw_lds(1, 4096, 8, 12) == 16672);
 
+// The lsap_warm_ entries: warm_prep_kernel over the batch, then (unless
+// SH_FLAG_BUILD_ONLY) the continuation.  One launch table by the column count
+// alone -- the result does not depend on the configuration -- with the cold
+// tables' (NW, K, FB) at each size: one wave up to 64 columns, four waves up to
+// SH_MAX_N, with_large_cfg / with_large_f64_cfg beyond.  SH_FLAG_F64_MW / _SW
+// have nothing to choose between here and are ignored.  The LDS is the cold
+// kernels' (the same lists); warm_prep_kernel's stays below LDS_NO_ATTR.
+static_assert(warm_prep_lds(SH_MAX_N_LARGE, SH_MAX_N_LARGE) == 57344 && warm_prep_lds(1, SH_MAX_N_LARGE) == 32784);
+static_assert(warm_prep_lds(SH_MAX_N_LARGE, SH_MAX_N_LARGE) <= LDS_NO_ATTR);
+
+template <typename S, typename T>
+int launch_warm(const S *C, int nr, int n, int B, const int32_t *shape, int32_t *col, T *cost, T *du, T *dv,
+                int32_t *kept, unsigned flags, hipStream_t s) {
+  HIP_TRY_RC(check_lsap_args(nr, n, B, col, SH_MAX_N_LARGE));
+  if (!C && B > 0) return fail(SH_ERR_ARGS, "null C");
+  if ((!du || !dv) && B > 0) return fail(SH_ERR_ARGS, "null u or v");
+  if (B == 0) return SH_OK;
+  hipLaunchKernelGGL((warm_prep_kernel<S, T>), dim3(B), dim3(PREP_WG), warm_prep_lds(nr, n), s, C, nr, n, shape, col,
+                     du, dv, kept);
+  HIP_TRY(hipGetLastError());
+  if (flags & SH_FLAG_BUILD_ONLY) return SH_OK;
+  auto mw = [&](auto cfg) {
+    using C_ = decltype(cfg);
+    if constexpr (std::is_same<T, int64_t>::value)
+      hipLaunchKernelGGL((warm_i64_kernel<C_::NW, C_::K, S, C_::FB>), dim3(B), dim3(C_::NW * WAVE),
+                         lsap_i64_lds(nr, n, C_::NW, C_::FB), s, C, nr, n, shape, col, cost, du, dv, flags);
+    else
+      hipLaunchKernelGGL((warm_f64_mw_kernel<C_::NW, C_::K, S, C_::FB>), dim3(B), dim3(C_::NW * WAVE),
+                         lsap_f64_mw_lds(nr, n, C_::NW, C_::FB), s, C, nr, n, shape, col, cost, du, dv);
+    return SH_OK;
+  };
+  if (n > SH_MAX_N) {
+    if constexpr (std::is_same<T, int64_t>::value) with_large_cfg(n, mw);
+    else with_large_f64_cfg(n, mw);
+  } else if (n > 512) {
+    mw(BigCfg<4, 4, 10>{});
+  } else if (n > 256) {
+    mw(BigCfg<4, 2, 10>{});
+  } else if (n > WAVE) {
+    mw(BigCfg<4, 1, 10>{});
+  } else if constexpr (std::is_same<T, int64_t>::value) {
+    mw(BigCfg<1, 1, 10>{});
+  } else {
+    hipLaunchKernelGGL((warm_f64_kernel<1, S>), dim3(B), dim3(WAVE), lsap_f64_lds(nr), s, C, nr, n, shape, col, cost,
+                       du, dv);
+  }
+  HIP_TRY(hipGetLastError());
+  return SH_OK;
+}
+
 // The certificate (lsap_cert_kernel, lsap_slack_kernel, lsap_cert_final_kernel):
 // S the stored cost type, T int64_t or double.  The pass over the corners
 // reads 16 bytes per load when every row starts 16-byte aligned; a batch too
@@ -1370,6 +1420,22 @@ SH_LSAP_ENTRIES(f32, float, float, double, solve_f64)
 SH_LSAP_ENTRIES(f16, uint16_t, _Float16, double, solve_f64)
 SH_LSAP_ENTRIES(bf16, uint16_t, sh_bf16, double, solve_f64)
 #undef SH_LSAP_ENTRIES
+
+// The warm-start entry of a dense cost type (launch_warm): d_col and d_v are
+// in / out, d_u out, d_cost and d_kept nullable.
+#define SH_WARM_ENTRY(SUF, CT, KT, T)                                                                          \
+  int lsap_warm_##SUF(const CT *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col, T *d_cost, \
+                      T *d_u, T *d_v, int32_t *d_kept, unsigned flags, void *stream) {                         \
+    return launch_warm((const KT *)d_C, nr, nc, B, d_shape, d_col, d_cost, d_u, d_v, d_kept, flags,            \
+                       (hipStream_t)stream);                                                                   \
+  }
+SH_WARM_ENTRY(i64, int64_t, int64_t, int64_t)
+SH_WARM_ENTRY(i32, int32_t, int32_t, int64_t)
+SH_WARM_ENTRY(f64, double, double, double)
+SH_WARM_ENTRY(f32, float, float, double)
+SH_WARM_ENTRY(f16, uint16_t, _Float16, double)
+SH_WARM_ENTRY(bf16, uint16_t, sh_bf16, double)
+#undef SH_WARM_ENTRY
 
 int lsap_solve_batched_rect_hash(uint64_t seed, int64_t modulus, int nr, int nc, int B,
                                  int32_t *d_col, int64_t *d_cost, unsigned flags, void *stream) {

@@ -120,7 +120,7 @@ struct WithDuals : L {
   T *dv;  // the instance's column duals (global, n live entries)
 };
 
-template <int K, typename T, bool DUALS = false, typename Loader>
+template <int K, typename T, bool DUALS = false, bool WARM = false, typename Loader>
 __device__ int sap_solve(const int nr, const int n, Loader &ld, T *__restrict__ u_l,
                          int16_t *__restrict__ c4r_l, int64_t &steps_out) {
   const int lane = threadIdx.x;
@@ -133,8 +133,27 @@ __device__ int sap_solve(const int nr, const int n, Loader &ld, T *__restrict__ 
     r4c[k] = -1;
     path[k] = -1;
   }
+  if constexpr (WARM) {
+    // the state of warm_prep_kernel in place of the empty one: v from ld.dv,
+    // row4col from the caller's c4r_l (one pass over its nr entries)
+    static_assert(DUALS, "a warm start reads the v it will store");
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int j = lane + WAVE * k;
+      if (j < n) v[k] = ld.dv[j];
+    }
+    for (int i = 0; i < nr; ++i) {
+      const int t = c4r_l[i];
+#pragma unroll
+      for (int k = 0; k < K; ++k)
+        if (lane + WAVE * k == t) r4c[k] = i;
+    }
+  }
   int64_t steps = 0;
   for (int cur = 0; cur < nr; ++cur) {
+    if constexpr (WARM) {
+      if (c4r_l[cur] >= 0) continue;  // the row kept its column
+    }
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       const int j = lane + WAVE * k;
@@ -488,7 +507,8 @@ __device__ __forceinline__ int mw_col(int w, int k, int lane) {
 // mask rm goes to ~0 (a removed column's relaxation r >= minVal >= its spc
 // never updates it; its key's high word is ~0), the mover's position bits
 // flip.  The sink step needs none of it.
-template <int NW, int K, typename Loader, int FB = 10, bool RECT = false, bool DUALS = false, typename... LA>
+template <int NW, int K, typename Loader, int FB = 10, bool RECT = false, bool DUALS = false, bool WARM = false,
+          typename... LA>
 __device__ __forceinline__ void sap_solve_mw(const int n, const Loader &ld, const SolveLds &S, int64_t &steps_out,
                              int &fallbacks, const bool exact, const LA &...la) {
   // RECT (the generic LSAP kernels only; a flag, so that the square
@@ -496,6 +516,9 @@ __device__ __forceinline__ void sap_solve_mw(const int n, const Loader &ld, cons
   // rows (S.u, S.c4r) over n >= ld.nr columns (S.r4c, S.path, `remaining`)
   // DUALS (the same kernels' duals form, a flag for the same reason): at the
   // end every thread stores v = -nv of its columns to ld.dv (WithDuals)
+  // WARM (the warm_ kernels only; a flag for the same reason): the caller
+  // loaded S.u, S.c4r and S.r4c with warm_prep_kernel's state, ld.dv holds its
+  // v, and a row that kept its column runs no Dijkstra
   int nr = n;
   if constexpr (RECT) nr = ld.nr;
   // key fields: FB bits of position and of row/column (n <= 2^FB), 1 class bit
@@ -523,6 +546,14 @@ __device__ __forceinline__ void sap_solve_mw(const int n, const Loader &ld, cons
     nv[k] = 0;
     path[k] = -1;
   }
+  if constexpr (WARM) {
+    static_assert(DUALS && RECT, "a warm start reads the v it will store");
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int j = mw_col<NW, K>(w, k, lane);
+      if (j < n) nv[k] = -ld.dv[j];
+    }
+  }
   auto lo_of = [&](int k, int j) -> uint32_t {
     const uint32_t pos = (uint32_t)(n - 1 - j);
     return (r4c[k] < 0) ? (((FM - pos) << FB) | (uint32_t)j)
@@ -533,6 +564,9 @@ __device__ __forceinline__ void sap_solve_mw(const int n, const Loader &ld, cons
   if (NW > 1 && tid < 3) S.red[tid] = ~0ull;
   __syncthreads();
   for (int cur = 0; cur < nr; ++cur) {
+    if constexpr (WARM) {
+      if (S.c4r[cur] >= 0) continue;  // (block-uniform: written before the last barrier)
+    }
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       const int j = mw_col<NW, K>(w, k, lane);
@@ -5404,7 +5438,7 @@ __device__ __forceinline__ double wave_min_f64_dpp(double x) {
   return __longlong_as_double((long long)readlane_u64((uint64_t)__double_as_longlong(x), 63));
 }
 
-template <int NW, int K, bool DUALS = false, int FB = 10, typename Loader>
+template <int NW, int K, bool DUALS = false, int FB = 10, bool WARM = false, typename Loader>
 __device__ __forceinline__ int sap_solve_mw_f64(const int nr, const int n, const Loader &ld,
                                                 const SolveLdsF64 &S) {
   static_assert(FB >= 10 && FB <= 15, "1 + 2 FB key bits in 32, rows in int16");
@@ -5421,8 +5455,20 @@ __device__ __forceinline__ int sap_solve_mw_f64(const int nr, const int n, const
     v[k] = 0;
     path[k] = -1;
   }
+  if constexpr (WARM) {
+    // (as sap_solve_mw's: S.u, S.c4r, S.r4c hold warm_prep_kernel's state, ld.dv its v)
+    static_assert(DUALS, "a warm start reads the v it will store");
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int j = mw_col<NW, K>(w, k, lane);
+      if (j < n) v[k] = ld.dv[j];
+    }
+  }
   int par = 0;  // slot buffer of the step
   for (int cur = 0; cur < nr; ++cur) {
+    if constexpr (WARM) {
+      if (S.c4r[cur] >= 0) continue;  // the row kept its column (block-uniform)
+    }
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       const int j = mw_col<NW, K>(w, k, lane);
@@ -6299,6 +6345,329 @@ __global__ __launch_bounds__(CERT_WG) void lsap_cert_final_kernel(int B, T *slac
   }
   out[0] = x;
   if (!(x >= 0)) flags[b] = f | SH_CERT_SLACK;
+}
+
+// ---------------------------------------------------------------------------
+// Warm start (the lsap_warm_ entries): two launches on one
+// stream.
+//   warm_prep_kernel  one workgroup per instance turns a previous assignment
+//     col0 (in `col`) and previous column duals v0 (in `dv`), both read as
+//     data that may be anything, into a valid state of the shortest-
+//     augmenting-path run on THIS C: u[i] + v[j] <= C[i][j] everywhere, every
+//     kept pair tight, v <= 0, and with nr < n v == 0 on every free column.
+//       1  v[j] = v0[j] inside the window (integers: [-2^56, 0]; floats:
+//          finite and <= 0), else 0
+//       2  row4col: the lowest row that names a column takes it (atomicMin)
+//       3  nr < n: v = 0 on the columns no row took
+//       4  u[i] = min_j (C[i][j] - v[j]), one wave a row, one subtraction an
+//          entry in the widened type
+//       5  a pair (i, j) of step 2 is kept iff C[i][j] - v[j] == u[i] (the
+//          expression of step 4, so the test is exact in floats too); nr < n:
+//          a dropped column with v < 0 enters the raise queue
+//       6  nr < n: while the queue holds a column j: v[j] = 0, and every row
+//          with C[i][j] < u[i] takes u[i] = C[i][j] and loses its pair, whose
+//          column, if its v < 0, enters the queue
+//     A column enters the queue when it stops being kept, which happens once,
+//     so the loop is bounded by n pops.  The columns raised are the least set
+//     closed under "a raised column breaks a pair, the pair's column (v < 0)
+//     is raised", and u is the minimum of step 4's value and C over the raised
+//     columns: neither depends on the order of the pops, so the queue's order
+//     (that of the atomics) does not show in the result.
+//     With nr == n steps 3 and 6 are skipped on purpose: every column ends
+//     matched and a Dijkstra only lowers v, so v <= 0 holds without them, and
+//     one changed entry costs one dropped row.
+//     Writes col (the kept pairs, -1 elsewhere), du, dv (0 in the padding) and
+//     kept[b]; an empty or invalid shape gets -1 / zero duals / kept 0; a float
+//     instance with a row of +inf (u[i] = +inf) is infeasible: -1, NaN duals in
+//     the live slots, kept 0.
+//   warm_i64_kernel / warm_f64_kernel / warm_f64_mw_kernel  load that state and
+//     run the cold kernels' cores with WARM: one Dijkstra for each row without
+//     a column, the same body otherwise, so the result does not depend on the
+//     launch configuration.  Tails as the cold kernels'.
+// ---------------------------------------------------------------------------
+constexpr int PREP_WG = 512;
+constexpr int64_t WARM_V_MIN = -(1ll << 56);
+
+__device__ __forceinline__ int64_t warm_clean_v(int64_t x) { return (x >= WARM_V_MIN && x <= 0) ? x : 0; }
+__device__ __forceinline__ double warm_clean_v(double x) { return (x <= 0.0 && x > -__builtin_inf()) ? x : 0.0; }
+
+// u's region holds step 2's int32 claims first (n of them), then u (nr values)
+#define WARM_PREP_LDS(X, nr, n)                                                  \
+  X(u_l, T, ((size_t)nr * 8 > (size_t)n * 4 ? (size_t)nr * 8 : (size_t)n * 4))   \
+  X(r4c_l, int16_t, (size_t)n * 2)                                               \
+  X(c4r_l, int16_t, (size_t)nr * 2)                                              \
+  X(q_l, int16_t, (size_t)n * 2) /* the raise queue: a column enters once */
+__host__ __device__ constexpr size_t warm_prep_lds(int nr, int n) { return 0 WARM_PREP_LDS(LDS_BYTES, nr, n); }
+
+template <typename S, typename T>
+__global__ __launch_bounds__(PREP_WG) void warm_prep_kernel(const S *C, int NR, int NC, const int32_t *shape,
+                                                            int32_t *col, T *du, T *dv, int32_t *kept) {
+  constexpr bool FLT = std::is_same<T, double>::value;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ int s_qt, s_bad, s_kept;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  int nr, n;  // live rows and columns (see lsap_i64_kernel)
+  if (!lsap_shape(shape, b, NR, NC, nr, n)) {
+    lsap_no_instance<PREP_WG>(col, (T *)nullptr, b, NR, NC, du, dv);
+    if (tid == 0 && kept) kept[b] = 0;
+    return;
+  }
+  size_t off = 0;
+  T *u_l;
+  int16_t *r4c_l, *c4r_l, *q_l;
+  WARM_PREP_LDS(LDS_CARVE, nr, n)
+  int32_t *claim = (int32_t *)u_l;
+  int32_t *col_b = col + (size_t)b * NR;
+  T *u_b = du + (size_t)b * NR, *v_b = dv + (size_t)b * NC;
+  const S *C_b = C + (size_t)b * NR * NC;
+  const bool wide = nr < n;
+  const T INF = VT<T>::inf();
+  if (tid == 0) s_qt = s_bad = s_kept = 0;
+  for (int j = tid; j < n; j += PREP_WG) {  // 1
+    v_b[j] = warm_clean_v(v_b[j]);
+    claim[j] = INT32_MAX;
+  }
+  __syncthreads();
+  for (int i = tid; i < nr; i += PREP_WG) {  // 2
+    const int j = col_b[i];
+    const bool ok = j >= 0 && j < n;
+    c4r_l[i] = ok ? (int16_t)j : (int16_t)-1;
+    if (ok) atomicMin(&claim[j], i);
+  }
+  __syncthreads();
+  for (int j = tid; j < n; j += PREP_WG) {  // 3
+    const int r = claim[j];
+    r4c_l[j] = (r == INT32_MAX) ? (int16_t)-1 : (int16_t)r;
+    if (wide && r == INT32_MAX) v_b[j] = 0;
+  }
+  __syncthreads();  // (the claims are read: u_l may be written; v is final up to step 6)
+  for (int i = w; i < nr; i += PREP_WG / WAVE) {  // 4 and 5
+    const S *row = C_b + (size_t)i * NC;
+    T m = INF;
+#pragma unroll 4
+    for (int j = lane; j < n; j += WAVE) {
+      const T r = cert_sub(cert_widen<T>(row[j]), v_b[j]);
+      m = (r < m) ? r : m;
+    }
+    m = wave_min(m);
+    if (lane == 0) {
+      u_l[i] = m;
+      if (FLT && !(m < INF)) s_bad = 1;
+      const int j = c4r_l[i];
+      if (j >= 0) {
+        const bool mine = r4c_l[j] == i;  // (only row r4c_l[j] ever writes that slot)
+        const T vj = v_b[j];
+        if (!(mine && cert_sub(cert_widen<T>(row[j]), vj) == m)) {
+          c4r_l[i] = -1;
+          if (mine) {
+            r4c_l[j] = -1;
+            if (wide && vj < 0) q_l[atomicAdd(&s_qt, 1)] = (int16_t)j;
+          }
+        }
+      }
+    }
+  }
+  if (wide) {  // 6
+    for (int pop = 0; pop < n; ++pop) {
+      __syncthreads();  // the pushes and u of the pop before (or of step 5)
+      if (pop >= s_qt) break;  // (block-uniform: nobody pushes between this barrier and the next)
+      const int j = q_l[pop];
+      if (tid == 0) v_b[j] = 0;
+      for (int i = tid; i < nr; i += PREP_WG) {
+        const T c = cert_widen<T>(C_b[(size_t)i * NC + j]);
+        if (c < u_l[i]) {
+          u_l[i] = c;
+          const int jp = c4r_l[i];
+          if (jp >= 0) {
+            c4r_l[i] = -1;
+            r4c_l[jp] = -1;
+            if (v_b[jp] < 0) q_l[atomicAdd(&s_qt, 1)] = (int16_t)jp;
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const bool bad = FLT && s_bad;
+  int k = 0;
+  for (int i = tid; i < NR; i += PREP_WG) {
+    const int c = (i < nr && !bad) ? c4r_l[i] : -1;
+    col_b[i] = c;
+    k += c >= 0;
+    T x = (i < nr) ? u_l[i] : (T)0;
+    if constexpr (FLT) x = (bad && i < nr) ? __builtin_nan("") : x;
+    u_b[i] = x;
+  }
+  for (int j = tid; j < NC; j += PREP_WG) {
+    if (j >= n) v_b[j] = 0;
+    if constexpr (FLT) {
+      if (bad && j < n) v_b[j] = __builtin_nan("");
+    }
+  }
+  if (kept) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) k += __shfl_xor(k, o, WAVE);
+    if (lane == 0 && k) atomicAdd(&s_kept, k);
+    __syncthreads();
+    if (tid == 0) kept[b] = s_kept;
+  }
+}
+
+// The continuation on integer costs: lsap_i64_kernel's duals form with the
+// state loaded in place of the empty one (col, du, dv are in / out).
+template <int NW, int K, typename S, int FB>
+__global__ __launch_bounds__(NW * WAVE) void warm_i64_kernel(const S *C, int NR, int NC, const int32_t *shape,
+                                                             int32_t *col, int64_t *cost, int64_t *du, int64_t *dv,
+                                                             unsigned flags) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int WG = NW * WAVE;
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  int nr, n;
+  if (!lsap_shape(shape, b, NR, NC, nr, n)) {  // (warm_prep_kernel wrote the rest)
+    if (tid == 0 && cost) cost[b] = 0;
+    return;
+  }
+  size_t off = 0;
+  SolveLds Sl;
+  int64_t *part;
+  LSAP_I64_LDS(LDS_CARVE, nr, n, NW)
+  for (int i = tid; i < n; i += WG) {
+    if (i < nr) {
+      Sl.u[i] = du[(size_t)b * NR + i];
+      Sl.c4r[i] = (int16_t)col[(size_t)b * NR + i];
+    }
+    Sl.r4c[i] = -1;
+  }
+  __syncthreads();
+  for (int i = tid; i < nr; i += WG) {
+    const int j = Sl.c4r[i];
+    if (j >= 0) Sl.r4c[j] = (int16_t)i;
+  }
+  __syncthreads();
+  int64_t steps = 0;
+  int fallbacks = 0;
+  const bool exact = (flags & SH_FLAG_EXACT_ARGMIN) != 0;
+  const size_t base = (size_t)b * NR * NC;
+  using LD = WithDuals<GlobalLoader<NW, K, S>, int64_t>;
+  const LD ld{{C + base, n, NC, nr}, dv + (size_t)b * NC};
+  sap_solve_mw<NW, K, LD, FB, true, true, true>(n, ld, Sl, steps, fallbacks, exact);
+  for (int i = tid; i < nr; i += WG) du[(size_t)b * NR + i] = Sl.u[i];
+  duals_fill<int64_t, WG>(du, dv, b, NR, NC, nr, n, 0);
+  int64_t acc = 0;
+  for (int i = tid; i < NR; i += WG) {
+    const int cidx = (i < nr) ? Sl.c4r[i] : -1;
+    col[(size_t)b * NR + i] = cidx;
+    if (cost && i < nr) acc += (int64_t)C[base + (size_t)i * NC + cidx];
+  }
+  acc = wave_sum_i64(acc);
+  if ((tid & 63) == 0) part[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0 && cost) {
+    int64_t t = 0;
+    for (int q = 0; q < NW; ++q) t += part[q];
+    cost[b] = t;
+  }
+}
+
+// An instance the float continuations have nothing to do for: no shape, or one
+// warm_prep_kernel found infeasible (NaN in every live slot of u; no state it
+// writes otherwise holds one).  Block-uniform.
+__device__ __forceinline__ bool warm_f64_done(const int32_t *shape, int b, int NR, int NC, int &nr, int &n,
+                                              const double *du, double *cost) {
+  bool done = !lsap_shape(shape, b, NR, NC, nr, n);
+  if (!done) {
+    const double u0 = du[(size_t)b * NR];
+    done = u0 != u0;
+  }
+  if (done && threadIdx.x == 0 && cost) cost[b] = 0;
+  return done;
+}
+
+// ... on float costs, one wave (lsap_f64_kernel's duals form) ...
+template <int K, typename S>
+__global__ __launch_bounds__(WAVE) void warm_f64_kernel(const S *C, int NR, int NC, const int32_t *shape,
+                                                        int32_t *col, double *cost, double *du, double *dv) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int b = blockIdx.x;
+  const int lane = threadIdx.x;
+  int nr, n;
+  if (warm_f64_done(shape, b, NR, NC, nr, n, du, cost)) return;
+  size_t off = 0;
+  double *u_l;
+  int16_t *c4r_l;
+  LSAP_F64_LDS(LDS_CARVE, nr)
+  for (int i = lane; i < nr; i += WAVE) {
+    u_l[i] = du[(size_t)b * NR + i];
+    c4r_l[i] = (int16_t)col[(size_t)b * NR + i];
+  }
+  __syncthreads();
+  int64_t steps = 0;
+  const size_t base = (size_t)b * NR * NC;
+  using GL = GlobalLoaderF64<1, K, S>;
+  WithDuals<GL, double> ld{GL{C + base, n, NC}};
+  ld.dv = dv + (size_t)b * NC;
+  const int st = sap_solve<K, double, true, true>(nr, n, ld, u_l, c4r_l, steps);
+  __syncthreads();
+  duals_store_f64<WAVE>(du, dv, u_l, st, b, NR, NC, nr, n);
+  double acc = 0;
+  for (int i = lane; i < NR; i += WAVE) {
+    const bool live = st == 0 && i < nr;
+    const int cidx = live ? c4r_l[i] : -1;
+    col[(size_t)b * NR + i] = cidx;
+    if (live && cost) acc += widen_f64(C[base + (size_t)i * NC + cidx]);
+  }
+  if (cost) {  // (lsap_f64_kernel's order)
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, WAVE);
+    if (lane == 0) cost[b] = acc;
+  }
+}
+
+// ... and NW waves (lsap_f64_mw_kernel's duals form).
+template <int NW, int K, typename S, int FB>
+__global__ __launch_bounds__(NW * WAVE) void warm_f64_mw_kernel(const S *C, int NR, int NC, const int32_t *shape,
+                                                                int32_t *col, double *cost, double *du,
+                                                                double *dv) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int WG = NW * WAVE;
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  int nr, n;
+  if (warm_f64_done(shape, b, NR, NC, nr, n, du, cost)) return;
+  size_t off = 0;
+  SolveLdsF64 Sl;
+  LSAP_F64_MW_LDS(LDS_CARVE, nr, n, NW, FB)
+  for (int i = tid; i < n; i += WG) {
+    if (i < nr) {
+      Sl.u[i] = du[(size_t)b * NR + i];
+      Sl.c4r[i] = (int16_t)col[(size_t)b * NR + i];
+    }
+    Sl.r4c[i] = -1;
+    Sl.path[i] = -1;
+  }
+  __syncthreads();
+  for (int i = tid; i < nr; i += WG) {
+    const int j = Sl.c4r[i];
+    if (j >= 0) Sl.r4c[j] = (int16_t)i;
+  }
+  __syncthreads();
+  const size_t base = (size_t)b * NR * NC;
+  using GL = GlobalLoaderF64<NW, K, S>;
+  WithDuals<GL, double> ld{GL{C + base, n, NC}};
+  ld.dv = dv + (size_t)b * NC;
+  const int st = sap_solve_mw_f64<NW, K, true, FB, true>(nr, n, ld, Sl);
+  __syncthreads();
+  duals_store_f64<WG>(du, dv, Sl.u, st, b, NR, NC, nr, n);
+  for (int i = tid; i < NR; i += WG) col[(size_t)b * NR + i] = (st == 0 && i < nr) ? Sl.c4r[i] : -1;
+  if (cost && tid < WAVE) {
+    double acc = 0;
+    for (int i = tid; i < NR; i += WAVE)
+      if (st == 0 && i < nr) acc += widen_f64(C[base + (size_t)i * NC + Sl.c4r[i]]);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, WAVE);
+    if (tid == 0) cost[b] = acc;
+  }
 }
 
 // ---------------------------------------------------------------------------

@@ -22,8 +22,8 @@ from ._lib import (SH_CERT_COL, SH_CERT_GAP, SH_CERT_NONE, SH_CERT_RANGE, SH_CER
                    SH_CERT_SLACK, SH_CERT_TIGHT)
 from .lsap import (check_duals, check_duals_large, csr_transpose, densify,  # noqa: F401
                    linear_sum_assignment, linear_sum_assignment_duals, linear_sum_assignment_large,
-                   linear_sum_assignment_sparse, solve_batched, solve_batched_large, solve_batched_sparse,
-                   solve_hash, validate_csr)
+                   linear_sum_assignment_resolve, linear_sum_assignment_sparse, resolve_batched,
+                   solve_batched, solve_batched_large, solve_batched_sparse, solve_hash, validate_csr)
 from .lbap import check_bottleneck, linear_bottleneck_assignment, solve_bottleneck_batched  # noqa: F401
 
 lib()  # load the C-ABI at import: no silent CPU path
@@ -33,6 +33,7 @@ __all__ = [
     "optimize_block_triplets",
     "linear_sum_assignment", "linear_sum_assignment_duals", "solve_batched", "check_duals", "solve_hash",
     "linear_sum_assignment_large", "solve_batched_large", "check_duals_large",
+    "linear_sum_assignment_resolve", "resolve_batched",
     "linear_sum_assignment_sparse", "solve_batched_sparse", "densify", "csr_transpose", "validate_csr",
     "linear_bottleneck_assignment", "solve_bottleneck_batched", "check_bottleneck",
     "SH_CERT_COL", "SH_CERT_SLACK", "SH_CERT_TIGHT", "SH_CERT_SIGN", "SH_CERT_GAP", "SH_CERT_NONE",

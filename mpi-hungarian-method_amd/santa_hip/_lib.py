@@ -152,6 +152,8 @@ for _suf in ("i64", "i32", "f64", "f32", "f16", "bf16"):  # the duals / check_du
     SIGNATURES["lbap_solve_wit_" + _suf] = (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _U, _P])
     # its certificate: C, nr, nc, B, shape, col, value, wit, counts, flags out, flags, stream
     SIGNATURES["lbap_check_" + _suf] = (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _U, _P])
+    # the warm start: C, nr, nc, B, shape, col (in / out), cost, u, v (in / out), kept, flags, stream
+    SIGNATURES["lsap_warm_" + _suf] = (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _U, _P])
 # the sparse (CSR) float entries: indptr, indices, data, nr, nc, B, shape, col, cost, u, v, work, work_bytes, flags, stream
 SIGNATURES["lsap_csr_work_bytes"] = (ctypes.c_size_t, [_I, _I, _I])
 for _suf in ("f64", "f32"):

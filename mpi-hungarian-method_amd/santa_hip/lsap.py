@@ -16,6 +16,9 @@ against the costs on the device: for integer costs flags == 0 proves optimality.
 solve_batched_large, check_duals_large and linear_sum_assignment_large are the
 same three up to SH_MAX_N_LARGE = 4096 rows or columns (the reference's own
 block sizes, 2000 and 3000), through the lsap_*_large_ entries.
+resolve_batched and linear_sum_assignment_resolve start from a previous
+solution (col, v) of a nearby matrix instead of from nothing (the lsap_warm_
+entries): one Dijkstra for each row whose pair did not survive.
 solve_batched_sparse and linear_sum_assignment_sparse take the costs as CSR, a
 missing entry being a forbidden pair (the lsap_solve_csr_ entries): the dense
 float solve of the densification (densify), without the dense matrix.
@@ -446,6 +449,142 @@ def linear_sum_assignment_large(cost_matrix, maximize: bool = False, device: int
     for any shape up to SH_MAX_N_LARGE = 4096 on the longer side: the same
     routing, results and errors, solved by solve_batched_large."""
     return _lsa(cost_matrix, maximize, device, duals, solve_batched_large, _lib.SH_MAX_N_LARGE)
+
+
+# ---------------------------------------------------------------------------
+# Warm start: re-solve from a previous assignment and its duals (the lsap_warm_
+# entries).  The previous state is data: whatever it holds, the result is an
+# optimal assignment with certified duals; the closer it is to optimal for the
+# new costs, the fewer Dijkstras run (nr - kept of them).
+# ---------------------------------------------------------------------------
+def _check_resolve_args(C, col, u, v, shapes):
+    """resolve_batched's host checks -> (B, NR, NC, duals dtype)."""
+    if C.dim() != 3:
+        raise ValueError("expected [B, NR, NC]")
+    B, NR, NC = C.shape
+    if max(NR, NC) > _lib.SH_MAX_N_LARGE:
+        raise ValueError(f"max(NR, NC) = {max(NR, NC)} > {_lib.SH_MAX_N_LARGE}")
+    if C.dtype not in DTYPE_SUFFIX:
+        raise TypeError(f"unsupported dtype {C.dtype}")
+    ddt = torch.float64 if C.dtype in FLOAT_ENTRIES else torch.int64
+    if tuple(col.shape) != (B, NR) or tuple(u.shape) != (B, NR) or tuple(v.shape) != (B, NC):
+        raise ValueError(f"expected col and u of shape [{B}, {NR}] and v of shape [{B}, {NC}]")
+    if u.dtype != ddt or v.dtype != ddt:
+        raise TypeError(f"the duals of {C.dtype} costs are {ddt}")
+    narrow_col(col[:0])  # (TypeError unless an integer dtype)
+    if shapes is not None and NR > NC:
+        raise ValueError(f"a ragged batch must be padded wide, got [{NR}, {NC}]: "
+                         "transpose the batch so that every instance has nr <= nc")
+    return B, NR, NC, ddt
+
+
+def resolve_batched(C: torch.Tensor, col: torch.Tensor, u: torch.Tensor, v: torch.Tensor,
+                    with_cost: bool = True, flags: int = 0, shapes=None, maximize: bool = False):
+    """solve_batched_large(duals=True) started from a previous solution
+    (col [B, NR] of any integer dtype, u [B, NR], v [B, NC] with the duals'
+    dtype) -> (col, cost, u, v, kept int32 [B]).
+
+    C, shapes, maximize, the outputs' layout, padding and infeasibility are
+    solve_batched_large's.  The previous solution is read as data and is not
+    modified; it may belong to other costs, or be garbage: a column dual outside
+    the window ([-2^56, 0] for integers, finite and <= 0 for floats, in the
+    minimised problem) counts as 0, an entry of col outside [0, nc) as -1, and
+    of two rows on one column the lower keeps it.  Of the two duals only the
+    columns' are read (the rows' of a tall batch, which is solved as its
+    transpose); the others are recomputed.  A tall instance whose col is no
+    partial assignment (invert_col) starts from the empty matching.
+
+    kept[b] pairs of the previous assignment survive and nr_b - kept[b]
+    Dijkstras run.  The result is an optimal assignment with the signs and
+    equalities check_duals_large tests (integer duals exact); among several
+    optimal assignments it need not be the one solve_batched_large returns.
+    flags: SH_FLAG_EXACT_ARGMIN; SH_FLAG_BUILD_ONLY returns the start state
+    itself (the kept pairs, u, v, kept; cost 0)."""
+    B, NR, NC, ddt = _check_resolve_args(C, col, u, v, shapes)
+    shape_host = check_shapes(shapes, B, NR, NC) if shapes is not None else None
+    require_gpu()
+    dev = C.device
+    if B == 0 or NR == 0 or NC == 0:
+        return (torch.full((B, NR), -1, dtype=torch.int32, device=dev),
+                torch.zeros(B, dtype=ddt, device=dev) if with_cost else None,
+                torch.zeros((B, NR), dtype=ddt, device=dev), torch.zeros((B, NC), dtype=ddt, device=dev),
+                torch.zeros(B, dtype=torch.int32, device=dev))
+    col0 = narrow_col(col)
+    if maximize:
+        C, u, v = -(C.to(torch.int64) if C.dtype == torch.int32 else C), -u, -v
+    tall = NR > NC
+    if tall:  # the transpose: the rows' duals are its columns', col its inverse
+        C, v0 = C.transpose(1, 2), u
+        col0, bad = invert_col(col0, NC)
+        col0[bad] = -1
+        nr, nc = NC, NR
+    else:
+        v0, nr, nc = v, NR, NC
+    C = C.contiguous()
+    _check_int64_range(C)
+    col_w = col0.clone().contiguous()
+    v_w = v0.clone().contiguous()
+    u_w = torch.empty((B, nr), dtype=ddt, device=dev)
+    build_only = bool(flags & _lib.SH_FLAG_BUILD_ONLY)
+    cost = (torch.zeros if build_only else torch.empty)(B, dtype=ddt, device=dev) if with_cost else None
+    kept = torch.empty(B, dtype=torch.int32, device=dev)
+    shape_dev = torch.from_numpy(shape_host).to(dev) if shape_host is not None else None
+    rc = getattr(_lib.lib(), "lsap_warm_" + DTYPE_SUFFIX[C.dtype])(
+        _p(C), nr, nc, B, _p(shape_dev), _p(col_w), _p(cost), _p(u_w), _p(v_w), _p(kept),
+        _lib.SH_COMPAT_TIEBREAK | flags, current_stream_handle(dev))
+    _lib.check(rc, "lsap_warm")
+    if tall:
+        col_w, u_w, v_w = invert_tall(col_w, NR), v_w, u_w
+    if maximize:
+        cost = -cost if cost is not None else None
+        u_w, v_w = -u_w, -v_w
+    return col_w, cost, u_w, v_w, kept
+
+
+def linear_sum_assignment_resolve(cost_matrix, col_ind, u, v, maximize: bool = False, device: int | str = 0):
+    """linear_sum_assignment_large(duals=True) started from a previous solution
+    of a nearby matrix -> (row_ind, col_ind, u, v).
+
+    col_ind [nr] holds the previous column of every row, -1 for a row without
+    one (for wide and square input that is the col_ind of an earlier call; from
+    a tall result (r, c): full(nr, -1) with col_ind[r] = c); u [nr] and v [nc]
+    are numpy arrays of the route's dtype, int64 on the exact integer route and
+    float64 otherwise (linear_sum_assignment's routing; TypeError for another
+    dtype).  The result is optimal; on ties it need not be scipy's permutation."""
+    Ct, tall = _route(cost_matrix, maximize, torch.device("cpu"), _lib.SH_MAX_N_LARGE)
+    nr, nc = np.asarray(cost_matrix).shape
+    col_ind, u, v = np.asarray(col_ind), np.asarray(u), np.asarray(v)
+    if col_ind.shape != (nr,) or u.shape != (nr,) or v.shape != (nc,):
+        raise ValueError(f"expected col_ind and u of shape ({nr},) and v of shape ({nc},)")
+    if not np.issubdtype(col_ind.dtype, np.integer):
+        raise TypeError(f"col_ind must be an integer array, got {col_ind.dtype}")
+    if Ct is None:
+        z = np.zeros(0, dtype=np.int64)
+        return z, z.copy(), np.zeros(nr, dtype=np.int64), np.zeros(nc, dtype=np.int64)
+    want = np.int64 if Ct.dtype == torch.int64 else np.float64
+    if u.dtype != want or v.dtype != want:
+        raise TypeError(f"this matrix is solved in {np.dtype(want).name}: u and v must have that dtype, "
+                        f"got {u.dtype} and {v.dtype}")
+    require_gpu()
+    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    col0 = torch.from_numpy(np.clip(col_ind.astype(np.int64), _INT32_MIN, _INT32_MAX).astype(np.int32))[None]
+    v0 = torch.from_numpy(np.ascontiguousarray(u if tall else v))[None]
+    if maximize:
+        v0 = -v0
+    if tall:
+        col0, bad = invert_col(col0, nc)
+        col0[bad] = -1
+    m = Ct.shape[0]
+    col, _, ru, rv, _ = resolve_batched(Ct.unsqueeze(0).to(dev), col0.to(dev), torch.zeros((1, m), dtype=v0.dtype, device=dev),
+                                        v0.to(dev), with_cost=False)
+    col = col[0].cpu().numpy().astype(np.int64)
+    if (col < 0).any():
+        raise ValueError("cost matrix is infeasible")
+    res = tall_result(col) if tall else (np.arange(col.size, dtype=np.int64), col)
+    ru, rv = ru[0].cpu().numpy(), rv[0].cpu().numpy()
+    if maximize:
+        ru, rv = -ru, -rv
+    return res + ((rv, ru) if tall else (ru, rv))
 
 
 # ---------------------------------------------------------------------------
