@@ -28,24 +28,8 @@ import torch
 
 from . import _lib
 from .context import current_stream_handle, require_gpu
-from .lsap import DTYPE_SUFFIX, _p, check_shapes, invert_col, invert_tall, narrow_col, tall_result
-
-
-def _check_batch(C: torch.Tensor, shapes):
-    """The argument errors of the bottleneck entries -> the host shapes or None."""
-    if C.dim() != 3:
-        raise ValueError("expected [B, NR, NC]")
-    B, NR, NC = C.shape
-    if max(NR, NC) > _lib.SH_MAX_N_LARGE:
-        raise ValueError(f"max(NR, NC) = {max(NR, NC)} > {_lib.SH_MAX_N_LARGE}")
-    if C.dtype not in DTYPE_SUFFIX:
-        raise TypeError(f"unsupported dtype {C.dtype}")
-    if shapes is None:
-        return None
-    if NR > NC:
-        raise ValueError(f"a ragged batch must be padded wide, got [{NR}, {NC}]: "
-                         "transpose the batch so that every instance has nr <= nc")
-    return check_shapes(shapes, B, NR, NC)
+from ._batch import (DTYPE_SUFFIX, _p, device_of, empty_result, invert_col, narrow_col, plan, single_empty,
+                     single_result, tall_view, wide_view)
 
 
 def solve_bottleneck_batched(C: torch.Tensor, with_value: bool = True, flags: int = 0, shapes=None,
@@ -79,31 +63,27 @@ def solve_bottleneck_batched(C: torch.Tensor, with_value: bool = True, flags: in
     not forbidden.  wit is [B, min(NR, NC)] over the SHORTER side: rows of a
     wide batch, and, since a tall batch is solved as its transpose, [B, NC]
     over the columns of a tall one.  Padded rows and empty instances are 0."""
-    shape_host = _check_batch(C, shapes)
-    B, NR, NC = C.shape
+    p = plan(C.shape, C.dtype, _lib.SH_MAX_N_LARGE, shapes)
     dev = C.device
-    if B == 0 or NR == 0 or NC == 0:
-        empty = (torch.full((B, NR), -1, dtype=torch.int32, device=dev),
-                 torch.zeros(B, dtype=C.dtype, device=dev) if with_value else None)
-        return empty + (torch.zeros((B, min(NR, NC)), dtype=torch.uint8, device=dev),) if witness else empty
+    if p.empty:
+        empty = empty_result(p, with_value, False, C.dtype, dev)
+        return empty + (torch.zeros((p.B, p.nr), dtype=torch.uint8, device=dev),) if witness else empty
     require_gpu()
-    shape_dev = torch.from_numpy(shape_host).to(dev) if shape_host is not None else None
-    tall = NR > NC
-    Cw = (C.transpose(1, 2) if tall else C).contiguous()
-    _, nr, nc = Cw.shape
-    col = torch.empty((B, nr), dtype=torch.int32, device=dev)
-    value = torch.empty(B, dtype=C.dtype, device=dev) if with_value else None
+    shape_dev = p.shapes_on(dev) if p.shapes is not None else None
+    Cw = (wide_view(C)[0] if p.tall else C).contiguous()
+    col = torch.empty((p.B, p.nr), dtype=torch.int32, device=dev)
+    value = torch.empty(p.B, dtype=C.dtype, device=dev) if with_value else None
     fl = flags | (_lib.SH_FLAG_MAXIMIZE if maximize else 0)
     if witness:
-        wit = torch.empty((B, nr), dtype=torch.uint8, device=dev)
+        wit = torch.empty((p.B, p.nr), dtype=torch.uint8, device=dev)
         rc = getattr(_lib.lib(), "lbap_solve_wit_" + DTYPE_SUFFIX[C.dtype])(
-            _p(Cw), nr, nc, B, _p(shape_dev), _p(col), _p(value), _p(wit), fl, current_stream_handle(dev))
+            _p(Cw), p.nr, p.nc, p.B, _p(shape_dev), _p(col), _p(value), _p(wit), fl, current_stream_handle(dev))
         _lib.check(rc, "lbap_solve_wit")
-        return (invert_tall(col, NR) if tall else col), value, wit
+        return (tall_view(p, col)[0] if p.tall else col), value, wit
     rc = getattr(_lib.lib(), "lbap_solve_" + DTYPE_SUFFIX[C.dtype])(
-        _p(Cw), nr, nc, B, _p(shape_dev), _p(col), _p(value), fl, current_stream_handle(dev))
+        _p(Cw), p.nr, p.nc, p.B, _p(shape_dev), _p(col), _p(value), fl, current_stream_handle(dev))
     _lib.check(rc, "lbap_solve")
-    return (invert_tall(col, NR) if tall else col), value
+    return (tall_view(p, col)[0] if p.tall else col), value
 
 
 def check_bottleneck(C: torch.Tensor, col: torch.Tensor, value: torch.Tensor, wit: torch.Tensor, shapes=None,
@@ -126,29 +106,27 @@ def check_bottleneck(C: torch.Tensor, col: torch.Tensor, value: torch.Tensor, wi
     infeasible, by comparisons alone: every dtype, int64 over its whole range.
     An empty instance gives 0 and (0, 0).  A tall batch is checked as its
     transpose, with col inverted on the device.  Raises as the solver does."""
-    shape_host = _check_batch(C, shapes)
-    B, NR, NC = C.shape
-    if tuple(col.shape) != (B, NR) or tuple(value.shape) != (B,) or tuple(wit.shape) != (B, min(NR, NC)):
-        raise ValueError(f"expected col [{B}, {NR}], value [{B}] and wit [{B}, {min(NR, NC)}]")
+    p = plan(C.shape, C.dtype, _lib.SH_MAX_N_LARGE, shapes)
+    B, NR = p.B, p.NR
+    if tuple(col.shape) != (B, NR) or tuple(value.shape) != (B,) or tuple(wit.shape) != (B, p.nr):
+        raise ValueError(f"expected col [{B}, {NR}], value [{B}] and wit [{B}, {p.nr}]")
     if value.dtype != C.dtype or wit.dtype not in (torch.uint8, torch.bool):
         raise TypeError(f"value must be {C.dtype} and wit uint8 or bool")
     col = narrow_col(col)
     dev = C.device
     counts = torch.zeros((B, 2), dtype=torch.int32, device=dev)
     flags = torch.zeros(B, dtype=torch.int32, device=dev)
-    if B == 0 or NR == 0 or NC == 0:
+    if p.empty:
         return counts[:, 0], counts[:, 1], flags
     require_gpu()
-    shape_dev = torch.from_numpy(shape_host).to(dev) if shape_host is not None else None
+    shape_dev = p.shapes_on(dev) if p.shapes is not None else None
     bad = None
-    if NR > NC:
-        C = C.transpose(1, 2)
-        col, bad = invert_col(col, NC)
-        NR, NC = NC, NR
+    if p.tall:
+        C, col, bad = wide_view(C)[0], *invert_col(col, p.NC)
     C, col, value = C.contiguous(), col.contiguous(), value.contiguous()
     wit = wit.to(torch.uint8).contiguous()
     rc = getattr(_lib.lib(), "lbap_check_" + DTYPE_SUFFIX[C.dtype])(
-        _p(C), NR, NC, B, _p(shape_dev), _p(col), _p(value), _p(wit), _p(counts), _p(flags),
+        _p(C), p.nr, p.nc, B, _p(shape_dev), _p(col), _p(value), _p(wit), _p(counts), _p(flags),
         _lib.SH_FLAG_MAXIMIZE if maximize else 0, current_stream_handle(dev))
     _lib.check(rc, "lbap_check")
     if bad is not None:  # a tall col that was no assignment before its inversion
@@ -200,8 +178,7 @@ def linear_bottleneck_assignment(cost_matrix, maximize: bool = False, device: in
     C = _widen(C)
     nr, nc = C.shape
     if nr == 0 or nc == 0:
-        z = np.zeros(0, dtype=np.int64)
-        return (z, z.copy(), C.dtype.type(0)) + ((np.zeros(0, dtype=bool),) if witness else ())
+        return single_empty(nr, nc, False) + (C.dtype.type(0),) + ((np.zeros(0, dtype=bool),) if witness else ())
     if max(nr, nc) > _lib.SH_MAX_N_LARGE:
         raise ValueError(f"max(nr, nc) = {max(nr, nc)} > {_lib.SH_MAX_N_LARGE}")
     if np.issubdtype(C.dtype, np.floating) and np.isnan(C).any():
@@ -209,11 +186,7 @@ def linear_bottleneck_assignment(cost_matrix, maximize: bool = False, device: in
     tall = nr > nc
     if tall:
         C = C.T
-    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-    Ct = torch.from_numpy(np.ascontiguousarray(C)).to(dev)
+    Ct = torch.from_numpy(np.ascontiguousarray(C)).to(device_of(device))
     col, value, *wit = solve_bottleneck_batched(Ct.unsqueeze(0), maximize=maximize, witness=witness)
-    col = col[0].cpu().numpy().astype(np.int64)
-    if (col < 0).any():
-        raise ValueError("cost matrix is infeasible")
-    rows, cols = tall_result(col) if tall else (np.arange(col.size, dtype=np.int64), col)
-    return (rows, cols, value.cpu().numpy()[0]) + ((wit[0][0].cpu().numpy().astype(bool),) if witness else ())
+    res = single_result(col, tall)
+    return res + (value.cpu().numpy()[0],) + ((wit[0][0].cpu().numpy().astype(bool),) if witness else ())

@@ -31,12 +31,10 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._batch import (DTYPE_SUFFIX, _INT32_MAX, _INT32_MIN, _p, alloc_outputs, check_solution, device_of, empty_result,
+                     invert_col, minimised, narrow_col, plan, single_empty, single_result, tall_view, wide_view)
+from ._batch import check_shapes, invert_tall, tall_result  # noqa: F401  (re-exported: they lived here)
 from .context import current_stream_handle, require_gpu
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
 
 INT64_COST_LIMIT = 1 << 50  # |C| bound that keeps every SAP value < 2^62 (n <= 1024)
 INT64_COST_LIMIT_LARGE = 1 << 48  # the same factor 4n at n <= 4096
@@ -44,90 +42,6 @@ EXACT_INT_LIMIT = 1 << 53   # float64 holds every integer below this exactly
 # floating-point cost dtypes of solve_batched and their C-ABI entries
 FLOAT_ENTRIES = {torch.float64: "lsap_solve_batched_rect_f64", torch.float32: "lsap_solve_batched_rect_f32",
                  torch.float16: "lsap_solve_batched_rect_f16", torch.bfloat16: "lsap_solve_batched_rect_bf16"}
-# every cost dtype -> the suffix of its lsap_solve_batched_duals_ / lsap_check_duals_ entry
-DTYPE_SUFFIX = {torch.int64: "i64", torch.int32: "i32", torch.float64: "f64", torch.float32: "f32",
-                torch.float16: "f16", torch.bfloat16: "bf16"}
-
-
-# ---------------------------------------------------------------------------
-# Host-only pieces (pure: no GPU, no library call).
-# ---------------------------------------------------------------------------
-def check_shapes(shapes, B: int, NR: int, NC: int) -> np.ndarray:
-    """The per-instance shapes of a padded [B, NR, NC] batch as int32 [B, 2]
-    on the host; ValueError unless 0 <= nr_b <= NR and nr_b <= nc_b <= NC."""
-    if isinstance(shapes, torch.Tensor):
-        shapes = shapes.detach().cpu().numpy()
-    sh = np.asarray(shapes)
-    if sh.shape != (B, 2) or not np.issubdtype(sh.dtype, np.integer):
-        raise ValueError(f"shapes must be an integer [B, 2] = [{B}, 2] array, got {sh.dtype} {sh.shape}")
-    sh = sh.astype(np.int64)
-    nr, nc = sh[:, 0], sh[:, 1]
-    bad = np.flatnonzero((nr < 0) | (nr > NR) | (nc < 0) | (nc > NC))
-    if bad.size:
-        b = int(bad[0])
-        raise ValueError(f"shapes[{b}] = ({int(nr[b])}, {int(nc[b])}) is outside the padded "
-                         f"[{NR}, {NC}] matrix")
-    tall = np.flatnonzero(nr > nc)
-    if tall.size:
-        b = int(tall[0])
-        raise ValueError(f"shapes[{b}] = ({int(nr[b])}, {int(nc[b])}) is tall (nr > nc): "
-                         "transpose the batch so that every instance has nr <= nc")
-    return np.ascontiguousarray(sh, dtype=np.int32)
-
-
-def invert_tall(col_t: torch.Tensor, nr: int) -> torch.Tensor:
-    """col_t int32 [B, nc]: the solution of the transposed (wide) batch, i.e.
-    the row of the tall matrix that each of its nc columns took (-1: none).
-    Returns the tall batch's per-row columns, int32 [B, nr], -1 for the
-    nr - nc rows left out (and everywhere for an infeasible instance)."""
-    B, nc = col_t.shape
-    out = torch.full((B, nr + 1), -1, dtype=torch.int32, device=col_t.device)
-    idx = torch.where(col_t >= 0, col_t, torch.full_like(col_t, nr)).long()  # (-1 -> the spare slot)
-    src = torch.arange(nc, dtype=torch.int32, device=col_t.device).expand(B, nc)
-    out.scatter_(1, idx, src)
-    return out[:, :nr].contiguous()
-
-
-def invert_col(col: torch.Tensor, n: int):
-    """col int32 [B, m] with entries in [0, n) or -1 -> (inv int32 [B, n], bad
-    bool [B]): inv[b, col[b, i]] = i and -1 where no row points.  bad marks the
-    instances whose col is no partial assignment (an entry outside [-1, n), or
-    two rows on one column), whose inverse means nothing."""
-    B, m = col.shape
-    ok = (col >= 0) & (col < n)
-    inv = torch.full((B, n + 1), -1, dtype=torch.int32, device=col.device)
-    idx = torch.where(ok, col, torch.full_like(col, n)).long()  # (anything else -> the spare slot)
-    src = torch.arange(m, dtype=torch.int32, device=col.device).expand(B, m)
-    inv.scatter_(1, idx, src)
-    inv = inv[:, :n].contiguous()
-    bad = ((~ok) & (col != -1)).any(1) | ((inv >= 0).sum(1) != ok.sum(1))
-    return inv, bad
-
-
-_INT32_MIN, _INT32_MAX = -(1 << 31), (1 << 31) - 1
-
-
-def narrow_col(col: torch.Tensor) -> torch.Tensor:
-    """col of any signed integer dtype (or uint8) as the int32 the certificate
-    entries read.  A value outside int32 saturates to INT32_MAX or INT32_MIN,
-    which no kernel takes for a column (they flag it and never index with it);
-    wrapping it would turn 2**32 + 3 into column 3.  TypeError for any other
-    dtype."""
-    if col.dtype == torch.int32:
-        return col
-    if col.dtype == torch.int64:
-        return col.clamp(_INT32_MIN, _INT32_MAX).to(torch.int32)
-    if col.dtype in (torch.int16, torch.int8, torch.uint8):
-        return col.to(torch.int32)
-    raise TypeError(f"col must be an integer tensor, got {col.dtype}")
-
-
-def tall_result(col_t):
-    """scipy's (row_ind, col_ind) of a tall matrix from the solution col_t of
-    its transpose: rows sorted ascending, each with its column."""
-    col_t = np.asarray(col_t, dtype=np.int64)
-    order = np.argsort(col_t)
-    return col_t[order], order.astype(np.int64)
 
 
 def int64_cost_limit(n: int) -> int:
@@ -158,29 +72,6 @@ def _check_int64_range(C: torch.Tensor):
     # (max / -min as Python ints: abs() wraps at INT64_MIN)
     if C.dtype == torch.int64 and C.numel() and max(int(C.max()), -int(C.min())) >= limit:
         raise ValueError(f"int64 costs must satisfy |C| < 2**{limit.bit_length() - 1}; pass float64 instead")
-
-
-def _solve_wide(C: torch.Tensor, with_cost: bool, fl: int, shape_dev, duals: bool, large: bool):
-    """C contiguous [B, nr, nc], 1 <= nr <= nc (the square C-ABI entries are
-    the rect ones with nr == nc and no shapes) -> (col, cost, u, v), u and v
-    None without duals.  The entry by (large, duals, dtype): lsap_solve_large_
-    (u and v nullable), lsap_solve_batched_duals_ or lsap_solve_batched_rect_."""
-    B, nr, nc = C.shape
-    dev = C.device
-    if C.dtype not in DTYPE_SUFFIX:
-        raise TypeError(f"unsupported dtype {C.dtype}")
-    _check_int64_range(C)
-    ddt = torch.float64 if C.dtype in FLOAT_ENTRIES else torch.int64
-    col = torch.empty((B, nr), dtype=torch.int32, device=dev)
-    cost = torch.empty(B, dtype=ddt, device=dev) if with_cost else None
-    u = torch.empty((B, nr), dtype=ddt, device=dev) if duals else None
-    v = torch.empty((B, nc), dtype=ddt, device=dev) if duals else None
-    name = "lsap_solve_large" if large else "lsap_solve_batched_duals" if duals else "lsap_solve_batched_rect"
-    uv = (_p(u), _p(v)) if large or duals else ()
-    rc = getattr(_lib.lib(), f"{name}_{DTYPE_SUFFIX[C.dtype]}")(
-        _p(C), nr, nc, B, _p(shape_dev), _p(col), _p(cost), *uv, fl, current_stream_handle(dev))
-    _lib.check(rc, "lsap_solve_batched" if name.endswith("rect") else name)
-    return col, cost, u, v
 
 
 def solve_batched(C: torch.Tensor, with_cost: bool = True, flags: int = 0, shapes=None,
@@ -228,38 +119,31 @@ def solve_batched_large(C: torch.Tensor, with_cost: bool = True, flags: int = 0,
 
 
 def _solve_batched(C, with_cost, flags, shapes, maximize, duals, large):
-    """solve_batched (limit SH_MAX_N) and solve_batched_large (SH_MAX_N_LARGE)."""
-    require_gpu()
-    if C.dim() != 3:
-        raise ValueError("expected [B, NR, NC]")
-    B, NR, NC = C.shape
-    limit = _lib.SH_MAX_N_LARGE if large else _lib.SH_MAX_N
-    if max(NR, NC) > limit:
-        raise ValueError(f"max(NR, NC) = {max(NR, NC)} > {limit}")
-    if C.dtype not in (torch.int64, torch.int32) and C.dtype not in FLOAT_ENTRIES:
-        raise TypeError(f"unsupported dtype {C.dtype}")
+    """solve_batched (limit SH_MAX_N) and solve_batched_large (SH_MAX_N_LARGE).
+    The entry by (large, duals, dtype): lsap_solve_large_ (u and v nullable),
+    lsap_solve_batched_duals_ or lsap_solve_batched_rect_ (the square C-ABI
+    entries are the rect ones with nr == nc and no shapes)."""
+    p = plan(C.shape, C.dtype, _lib.SH_MAX_N_LARGE if large else _lib.SH_MAX_N, shapes)
     dev = C.device
-    shape_dev = None
-    if shapes is not None:
-        if NR > NC:
-            raise ValueError(f"a ragged batch must be padded wide, got [{NR}, {NC}]: "
-                             "transpose the batch so that every instance has nr <= nc")
-        shape_dev = torch.from_numpy(check_shapes(shapes, B, NR, NC)).to(dev)
-    if B == 0 or NR == 0 or NC == 0:
-        cdt = torch.float64 if C.dtype in FLOAT_ENTRIES else torch.int64
-        out = (torch.full((B, NR), -1, dtype=torch.int32, device=dev),
-               torch.zeros(B, dtype=cdt, device=dev) if with_cost else None)
-        if duals:
-            out += (torch.zeros((B, NR), dtype=cdt, device=dev), torch.zeros((B, NC), dtype=cdt, device=dev))
-        return out
-    if maximize:  # (int32: -INT32_MIN wraps, so widen; the int64 bound covers int64)
-        C = -(C.to(torch.int64) if C.dtype == torch.int32 else C)
-    fl = _lib.SH_COMPAT_TIEBREAK | flags
-    if NR > NC:  # the transposed solve's row duals belong to the columns
-        col_t, cost, v, u = _solve_wide(C.transpose(1, 2).contiguous(), with_cost, fl, None, duals, large)
-        col = invert_tall(col_t, NR)
-    else:
-        col, cost, u, v = _solve_wide(C.contiguous(), with_cost, fl, shape_dev, duals, large)
+    if p.empty:
+        return empty_result(p, with_cost, duals, p.ddt, dev)
+    require_gpu()
+    if maximize:
+        C, = minimised(C)
+    if p.tall:
+        C, _, _ = wide_view(C)
+    C = C.contiguous()
+    _check_int64_range(C)
+    col, cost, u, v = alloc_outputs(p, with_cost, duals, p.ddt, dev)
+    shape_dev = p.shapes_on(dev) if p.shapes is not None else None
+    name = "lsap_solve_large" if large else "lsap_solve_batched_duals" if duals else "lsap_solve_batched_rect"
+    uv = (_p(u), _p(v)) if large or duals else ()
+    rc = getattr(_lib.lib(), f"{name}_{DTYPE_SUFFIX[C.dtype]}")(
+        _p(C), p.nr, p.nc, p.B, _p(shape_dev), _p(col), _p(cost), *uv,
+        _lib.SH_COMPAT_TIEBREAK | flags, current_stream_handle(dev))
+    _lib.check(rc, "lsap_solve_batched" if name.endswith("rect") else name)
+    if p.tall:
+        col, u, v = tall_view(p, col, u, v)
     if maximize and cost is not None:
         cost = -cost
     if not duals:
@@ -272,7 +156,7 @@ def solve_hash(seed: int, modulus: int, n: int, B: int, device: int | str = 0, w
     """Solve B device-generated n x n matrices (sampler.hash_matrix on the host);
     with nr, the first nr rows of each (an nr x n instance, nr <= n)."""
     require_gpu()
-    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    dev = device_of(device)
     col = torch.empty((B, n if nr is None else nr), dtype=torch.int32, device=dev)
     cost = torch.empty(B, dtype=torch.int64, device=dev) if with_cost else None
     L = _lib.lib()
@@ -316,42 +200,24 @@ def check_duals_large(C: torch.Tensor, col: torch.Tensor, u: torch.Tensor, v: to
 
 def _check_duals(C, col, u, v, shapes, maximize, large):
     """check_duals (limit SH_MAX_N) and check_duals_large (SH_MAX_N_LARGE)."""
-    require_gpu()
-    if C.dim() != 3:
-        raise ValueError("expected [B, NR, NC]")
-    B, NR, NC = C.shape
-    limit = _lib.SH_MAX_N_LARGE if large else _lib.SH_MAX_N
-    if max(NR, NC) > limit:
-        raise ValueError(f"max(NR, NC) = {max(NR, NC)} > {limit}")
-    if C.dtype not in DTYPE_SUFFIX:
-        raise TypeError(f"unsupported dtype {C.dtype}")
-    ddt = torch.float64 if C.dtype in FLOAT_ENTRIES else torch.int64
-    if tuple(col.shape) != (B, NR) or tuple(u.shape) != (B, NR) or tuple(v.shape) != (B, NC):
-        raise ValueError(f"expected col and u of shape [{B}, {NR}] and v of shape [{B}, {NC}]")
-    if u.dtype != ddt or v.dtype != ddt:
-        raise TypeError(f"the duals of {C.dtype} costs are {ddt}")
-    col = narrow_col(col)
+    p = plan(C.shape, C.dtype, _lib.SH_MAX_N_LARGE if large else _lib.SH_MAX_N, shapes)
+    check_solution(p, C.dtype, col, u, v)
     dev = C.device
-    shape_dev = None
-    if shapes is not None:
-        if NR > NC:
-            raise ValueError(f"a ragged batch must be padded wide, got [{NR}, {NC}]: "
-                             "transpose the batch so that every instance has nr <= nc")
-        shape_dev = torch.from_numpy(check_shapes(shapes, B, NR, NC)).to(dev)
-    flags = torch.zeros(B, dtype=torch.int32, device=dev)
-    slack = torch.zeros((B, 3), dtype=ddt, device=dev)
-    if B == 0 or NR == 0 or NC == 0:
+    flags = torch.zeros(p.B, dtype=torch.int32, device=dev)
+    slack = torch.zeros((p.B, 3), dtype=p.ddt, device=dev)
+    if p.empty:
         return slack[:, 0], slack[:, 1], slack[:, 2], flags
+    require_gpu()
+    col, bad = narrow_col(col), None
     if maximize:
-        C, u, v = -(C.to(torch.int64) if C.dtype == torch.int32 else C), -u, -v
-    bad = None
-    if NR > NC:
-        C, u, v = C.transpose(1, 2), v, u
-        col, bad = invert_col(col, NC)
-        NR, NC = NC, NR
+        C, u, v = minimised(C, u, v)
+    if p.tall:
+        C, u, v = wide_view(C, u, v)
+        col, bad = invert_col(col, p.NC)
     C, col, u, v = C.contiguous(), col.contiguous(), u.contiguous(), v.contiguous()
+    shape_dev = p.shapes_on(dev) if p.shapes is not None else None
     entry = getattr(_lib.lib(), ("lsap_check_duals_large_" if large else "lsap_check_duals_") + DTYPE_SUFFIX[C.dtype])
-    rc = entry(_p(C), NR, NC, B, _p(shape_dev), _p(col), _p(u), _p(v), _p(slack), _p(flags),
+    rc = entry(_p(C), p.nr, p.nc, p.B, _p(shape_dev), _p(col), _p(u), _p(v), _p(slack), _p(flags),
                current_stream_handle(dev))
     _lib.check(rc, "lsap_check_duals")
     if bad is not None:  # a tall col that was no assignment before its inversion
@@ -398,28 +264,13 @@ def _route(cost_matrix, maximize: bool, dev, limit: int = _lib.SH_MAX_N):
 def _lsa(cost_matrix, maximize, device, duals, solve, limit):
     """The front ends' body: `solve` is solve_batched or solve_batched_large
     (looked up by the caller at call time), `limit` its size limit."""
-    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-    Ct, tall = _route(cost_matrix, maximize, dev, limit)
+    Ct, tall = _route(cost_matrix, maximize, device_of(device), limit)
     if Ct is None:
-        z = np.zeros(0, dtype=np.int64)
-        if not duals:
-            return z, z.copy()
-        nr, nc = np.asarray(cost_matrix).shape
-        return z, z.copy(), np.zeros(nr, dtype=np.int64), np.zeros(nc, dtype=np.int64)
+        return single_empty(*np.asarray(cost_matrix).shape, duals)
     if not duals:
-        col, _ = solve(Ct.unsqueeze(0), with_cost=False)
-    else:
-        col, _, u, v = solve(Ct.unsqueeze(0), with_cost=False, duals=True)
-    col = col[0].cpu().numpy().astype(np.int64)
-    if (col < 0).any():
-        raise ValueError("cost matrix is infeasible")
-    res = tall_result(col) if tall else (np.arange(col.size, dtype=np.int64), col)
-    if not duals:
-        return res
-    u, v = u[0].cpu().numpy(), v[0].cpu().numpy()
-    if maximize:
-        u, v = -u, -v
-    return res + ((v, u) if tall else (u, v))
+        return single_result(solve(Ct.unsqueeze(0), with_cost=False)[0], tall)
+    col, _, u, v = solve(Ct.unsqueeze(0), with_cost=False, duals=True)
+    return single_result(col, tall, u, v, negate=maximize)
 
 
 def linear_sum_assignment_duals(cost_matrix, maximize: bool = False, device: int | str = 0):
@@ -457,27 +308,6 @@ def linear_sum_assignment_large(cost_matrix, maximize: bool = False, device: int
 # optimal assignment with certified duals; the closer it is to optimal for the
 # new costs, the fewer Dijkstras run (nr - kept of them).
 # ---------------------------------------------------------------------------
-def _check_resolve_args(C, col, u, v, shapes):
-    """resolve_batched's host checks -> (B, NR, NC, duals dtype)."""
-    if C.dim() != 3:
-        raise ValueError("expected [B, NR, NC]")
-    B, NR, NC = C.shape
-    if max(NR, NC) > _lib.SH_MAX_N_LARGE:
-        raise ValueError(f"max(NR, NC) = {max(NR, NC)} > {_lib.SH_MAX_N_LARGE}")
-    if C.dtype not in DTYPE_SUFFIX:
-        raise TypeError(f"unsupported dtype {C.dtype}")
-    ddt = torch.float64 if C.dtype in FLOAT_ENTRIES else torch.int64
-    if tuple(col.shape) != (B, NR) or tuple(u.shape) != (B, NR) or tuple(v.shape) != (B, NC):
-        raise ValueError(f"expected col and u of shape [{B}, {NR}] and v of shape [{B}, {NC}]")
-    if u.dtype != ddt or v.dtype != ddt:
-        raise TypeError(f"the duals of {C.dtype} costs are {ddt}")
-    narrow_col(col[:0])  # (TypeError unless an integer dtype)
-    if shapes is not None and NR > NC:
-        raise ValueError(f"a ragged batch must be padded wide, got [{NR}, {NC}]: "
-                         "transpose the batch so that every instance has nr <= nc")
-    return B, NR, NC, ddt
-
-
 def resolve_batched(C: torch.Tensor, col: torch.Tensor, u: torch.Tensor, v: torch.Tensor,
                     with_cost: bool = True, flags: int = 0, shapes=None, maximize: bool = False):
     """solve_batched_large(duals=True) started from a previous solution
@@ -500,41 +330,34 @@ def resolve_batched(C: torch.Tensor, col: torch.Tensor, u: torch.Tensor, v: torc
     optimal assignments it need not be the one solve_batched_large returns.
     flags: SH_FLAG_EXACT_ARGMIN; SH_FLAG_BUILD_ONLY returns the start state
     itself (the kept pairs, u, v, kept; cost 0)."""
-    B, NR, NC, ddt = _check_resolve_args(C, col, u, v, shapes)
-    shape_host = check_shapes(shapes, B, NR, NC) if shapes is not None else None
-    require_gpu()
+    p = plan(C.shape, C.dtype, _lib.SH_MAX_N_LARGE, shapes)
+    check_solution(p, C.dtype, col, u, v)
     dev = C.device
-    if B == 0 or NR == 0 or NC == 0:
-        return (torch.full((B, NR), -1, dtype=torch.int32, device=dev),
-                torch.zeros(B, dtype=ddt, device=dev) if with_cost else None,
-                torch.zeros((B, NR), dtype=ddt, device=dev), torch.zeros((B, NC), dtype=ddt, device=dev),
-                torch.zeros(B, dtype=torch.int32, device=dev))
+    if p.empty:
+        return empty_result(p, with_cost, True, p.ddt, dev) + (torch.zeros(p.B, dtype=torch.int32, device=dev),)
+    require_gpu()
     col0 = narrow_col(col)
     if maximize:
-        C, u, v = -(C.to(torch.int64) if C.dtype == torch.int32 else C), -u, -v
-    tall = NR > NC
-    if tall:  # the transpose: the rows' duals are its columns', col its inverse
-        C, v0 = C.transpose(1, 2), u
-        col0, bad = invert_col(col0, NC)
+        C, u, v = minimised(C, u, v)
+    if p.tall:  # the transpose: the rows' duals are its columns', col its inverse
+        C, u, v = wide_view(C, u, v)
+        col0, bad = invert_col(col0, p.NC)
         col0[bad] = -1
-        nr, nc = NC, NR
-    else:
-        v0, nr, nc = v, NR, NC
     C = C.contiguous()
     _check_int64_range(C)
-    col_w = col0.clone().contiguous()
-    v_w = v0.clone().contiguous()
-    u_w = torch.empty((B, nr), dtype=ddt, device=dev)
+    # the C entry works in place on col and v: it gets copies, and only u and the cost are new
+    col_w, v_w = col0.clone().contiguous(), v.clone().contiguous()
+    u_w = torch.empty((p.B, p.nr), dtype=p.ddt, device=dev)
     build_only = bool(flags & _lib.SH_FLAG_BUILD_ONLY)
-    cost = (torch.zeros if build_only else torch.empty)(B, dtype=ddt, device=dev) if with_cost else None
-    kept = torch.empty(B, dtype=torch.int32, device=dev)
-    shape_dev = torch.from_numpy(shape_host).to(dev) if shape_host is not None else None
+    cost = (torch.zeros if build_only else torch.empty)(p.B, dtype=p.ddt, device=dev) if with_cost else None
+    kept = torch.empty(p.B, dtype=torch.int32, device=dev)
+    shape_dev = p.shapes_on(dev) if p.shapes is not None else None
     rc = getattr(_lib.lib(), "lsap_warm_" + DTYPE_SUFFIX[C.dtype])(
-        _p(C), nr, nc, B, _p(shape_dev), _p(col_w), _p(cost), _p(u_w), _p(v_w), _p(kept),
+        _p(C), p.nr, p.nc, p.B, _p(shape_dev), _p(col_w), _p(cost), _p(u_w), _p(v_w), _p(kept),
         _lib.SH_COMPAT_TIEBREAK | flags, current_stream_handle(dev))
     _lib.check(rc, "lsap_warm")
-    if tall:
-        col_w, u_w, v_w = invert_tall(col_w, NR), v_w, u_w
+    if p.tall:
+        col_w, u_w, v_w = tall_view(p, col_w, u_w, v_w)
     if maximize:
         cost = -cost if cost is not None else None
         u_w, v_w = -u_w, -v_w
@@ -559,14 +382,13 @@ def linear_sum_assignment_resolve(cost_matrix, col_ind, u, v, maximize: bool = F
     if not np.issubdtype(col_ind.dtype, np.integer):
         raise TypeError(f"col_ind must be an integer array, got {col_ind.dtype}")
     if Ct is None:
-        z = np.zeros(0, dtype=np.int64)
-        return z, z.copy(), np.zeros(nr, dtype=np.int64), np.zeros(nc, dtype=np.int64)
+        return single_empty(nr, nc, True)
     want = np.int64 if Ct.dtype == torch.int64 else np.float64
     if u.dtype != want or v.dtype != want:
         raise TypeError(f"this matrix is solved in {np.dtype(want).name}: u and v must have that dtype, "
                         f"got {u.dtype} and {v.dtype}")
     require_gpu()
-    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    dev = device_of(device)
     col0 = torch.from_numpy(np.clip(col_ind.astype(np.int64), _INT32_MIN, _INT32_MAX).astype(np.int32))[None]
     v0 = torch.from_numpy(np.ascontiguousarray(u if tall else v))[None]
     if maximize:
@@ -577,14 +399,7 @@ def linear_sum_assignment_resolve(cost_matrix, col_ind, u, v, maximize: bool = F
     m = Ct.shape[0]
     col, _, ru, rv, _ = resolve_batched(Ct.unsqueeze(0).to(dev), col0.to(dev), torch.zeros((1, m), dtype=v0.dtype, device=dev),
                                         v0.to(dev), with_cost=False)
-    col = col[0].cpu().numpy().astype(np.int64)
-    if (col < 0).any():
-        raise ValueError("cost matrix is infeasible")
-    res = tall_result(col) if tall else (np.arange(col.size, dtype=np.int64), col)
-    ru, rv = ru[0].cpu().numpy(), rv[0].cpu().numpy()
-    if maximize:
-        ru, rv = -ru, -rv
-    return res + ((rv, ru) if tall else (ru, rv))
+    return single_result(col, tall, ru, rv, negate=maximize)
 
 
 # ---------------------------------------------------------------------------
@@ -710,37 +525,27 @@ def solve_batched_sparse(crow, col_indices=None, values=None, shape=None, with_c
         raise ValueError(f"negative size in shape {shape}")
     if NR > NC:
         raise ValueError(f"a sparse batch must be wide, got [{NR}, {NC}]: transpose it so that NR <= NC")
-    if NC > _lib.SH_MAX_N_LARGE:
-        raise ValueError(f"max(NR, NC) = {NC} > {_lib.SH_MAX_N_LARGE}")
     if values.is_complex():
         raise TypeError(f"unsupported dtype {values.dtype}")
     if values.dtype not in (torch.float64, torch.float32):
         values = values.to(torch.float64)
-    shape_host = check_shapes(shapes, B, NR, NC) if shapes is not None else None
+    p = plan(shape, values.dtype, _lib.SH_MAX_N_LARGE, shapes)
     if validate:
-        validate_csr(crow, col_indices, values, shape, shape_host)
+        validate_csr(crow, col_indices, values, shape, p.shapes)
     elif crow.numel() != B * NR + 1 or col_indices.numel() != values.numel():
         raise ValueError("crow must have B * NR + 1 entries, col_indices and values equal lengths")
-    require_gpu()
     dev = values.device
-    if B == 0 or NR == 0:
-        out = (torch.full((B, NR), -1, dtype=torch.int32, device=dev),
-               torch.zeros(B, dtype=torch.float64, device=dev) if with_cost else None)
-        if duals:
-            out += (torch.zeros((B, NR), dtype=torch.float64, device=dev),
-                    torch.zeros((B, NC), dtype=torch.float64, device=dev))
-        return out
+    if p.empty:
+        return empty_result(p, with_cost, duals, torch.float64, dev)
+    require_gpu()
     crow = crow.to(torch.int64).contiguous()
     col_indices = col_indices.to(torch.int32).contiguous()
     values = (-values if maximize else values).contiguous()
-    shape_dev = torch.from_numpy(shape_host).to(dev) if shape_host is not None else None
+    shape_dev = p.shapes_on(dev) if p.shapes is not None else None
     L = _lib.lib()
     nbytes = int(L.lsap_csr_work_bytes(NR, NC, B))
     work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    col = torch.empty((B, NR), dtype=torch.int32, device=dev)
-    cost = torch.empty(B, dtype=torch.float64, device=dev) if with_cost else None
-    u = torch.empty((B, NR), dtype=torch.float64, device=dev) if duals else None
-    v = torch.empty((B, NC), dtype=torch.float64, device=dev) if duals else None
+    col, cost, u, v = alloc_outputs(p, with_cost, duals, torch.float64, dev)
     entry = getattr(L, "lsap_solve_csr_" + DTYPE_SUFFIX[values.dtype])
     nnz = values.numel()
     rc = entry(_p(crow), _p(col_indices) if nnz else None, _p(values) if nnz else None, NR, NC, B,
@@ -785,8 +590,7 @@ def linear_sum_assignment_sparse(A, maximize: bool = False, device: int | str = 
     arrays."""
     indptr, indices, data, (nr, nc) = _csr_of(A)
     if nr == 0 or nc == 0:
-        z = np.zeros(0, dtype=np.int64)
-        return (z, z.copy(), np.zeros(nr), np.zeros(nc)) if duals else (z, z.copy())
+        return single_empty(nr, nc, duals, np.float64)
     if max(nr, nc) > _lib.SH_MAX_N_LARGE:
         raise ValueError(f"max(nr, nc) = {max(nr, nc)} > {_lib.SH_MAX_N_LARGE}")
     if data.dtype not in (np.float64, np.float32):
@@ -794,16 +598,9 @@ def linear_sum_assignment_sparse(A, maximize: bool = False, device: int | str = 
     tall = nr > nc
     if tall:
         indptr, indices, data, (nr, nc) = csr_transpose(indptr, indices, data, (nr, nc))
-    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    dev = device_of(device)
     out = solve_batched_sparse(torch.from_numpy(np.ascontiguousarray(indptr, dtype=np.int64)).to(dev),
                                torch.from_numpy(np.ascontiguousarray(indices, dtype=np.int32)).to(dev),
                                torch.from_numpy(np.ascontiguousarray(data)).to(dev), shape=(1, nr, nc),
                                with_cost=False, maximize=maximize, duals=duals)
-    col = out[0][0].cpu().numpy().astype(np.int64)
-    if (col < 0).any():
-        raise ValueError("cost matrix is infeasible")
-    res = tall_result(col) if tall else (np.arange(col.size, dtype=np.int64), col)
-    if not duals:
-        return res
-    u, v = out[2][0].cpu().numpy(), out[3][0].cpu().numpy()
-    return res + ((v, u) if tall else (u, v))
+    return single_result(out[0], tall, *out[2:])  # (the duals come back in the matrix's own signs)

@@ -2,10 +2,11 @@
 the CPU so that it also returns the dual variables it ends with.
 
 `replay(C)` is the vectorised form (one numpy expression per Dijkstra step over
-the `remaining` array, in the style of lsap_families.sap_trace); `replay_scalar`
-is the plain loop, kept for cross-checking.  Both take an int64 or a float64
-matrix with nr <= nc and return (col4row [nr], u [nr], v [nc]) in the matrix's
-dtype, or raise ValueError for an infeasible (float, +inf) instance.
+the `remaining` array, in the style of lsap_families.sap_trace), `replay_state`
+its loop from any state (the warm start's, lsap_warm_ref); `replay_scalar`
+is the plain loop, kept for cross-checking.  replay and replay_scalar take an
+int64 or a float64 matrix with nr <= nc and return (col4row [nr], u [nr],
+v [nc]) in the matrix's dtype, or raise ValueError for an infeasible (float, +inf) instance.
 
 The relaxation is `minVal + C[i, j] - u[i] - v[j]` evaluated left to right and
 the dual update `u += minVal - spc`, `v -= minVal - spc`, which are the IEEE
@@ -49,15 +50,20 @@ def _prepare(C):
     return C, C.dtype.type, inf, nr, nc
 
 
-def replay(C):
+def replay_state(C, col4row, row4col, u, v):
+    """The loop from a state (col4row [nr], row4col [nc], u [nr], v [nc]; it is
+    not modified): one search for every row without a column, rows ascending
+    -> (col4row, u, v, searches)."""
     C, T, inf, nr, nc = _prepare(C)
-    u = np.zeros(nr, dtype=C.dtype)
-    v = np.zeros(nc, dtype=C.dtype)
+    u, v = np.array(u, dtype=C.dtype), np.array(v, dtype=C.dtype)
+    col4row, row4col = np.array(col4row, dtype=np.int64), np.array(row4col, dtype=np.int64)
     path = -np.ones(nc, dtype=np.int64)
-    col4row = -np.ones(nr, dtype=np.int64)
-    row4col = -np.ones(nc, dtype=np.int64)
+    searches = 0
     with np.errstate(over="ignore", invalid="ignore"):
         for cur in range(nr):
+            if col4row[cur] >= 0:
+                continue
+            searches += 1
             remaining = np.arange(nc - 1, -1, -1)
             spc = np.full(nc, inf, dtype=C.dtype)
             SR, SC = [], []
@@ -97,7 +103,14 @@ def replay(C):
                 col4row[i], j = j, int(col4row[i])
                 if i == cur:
                     break
-    return col4row, u, v
+    return col4row, u, v, searches
+
+
+def replay(C):
+    """The whole run: the loop from the empty state -> (col4row, u, v)."""
+    C, _, _, nr, nc = _prepare(C)
+    return replay_state(C, -np.ones(nr, dtype=np.int64), -np.ones(nc, dtype=np.int64),
+                        np.zeros(nr, dtype=C.dtype), np.zeros(nc, dtype=C.dtype))[:3]
 
 
 def replay_scalar(C):

@@ -29,7 +29,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from lsap_duals_ref import _prepare
+from lsap_duals_ref import _prepare, replay_state
 
 V_MIN = -(1 << 56)
 
@@ -95,56 +95,7 @@ def prologue(C, col0, v0, order="fifo"):
 
 def replay_from(C, col4row, row4col, u, v):
     """lsap_duals_ref.replay's loop from a state; the state is not modified."""
-    C, T, inf, nr, nc = _prepare(C)
-    u, v = np.array(u, dtype=C.dtype), np.array(v, dtype=C.dtype)
-    col4row, row4col = np.array(col4row, dtype=np.int64), np.array(row4col, dtype=np.int64)
-    path = -np.ones(nc, dtype=np.int64)
-    searches = 0
-    with np.errstate(over="ignore", invalid="ignore"):
-        for cur in range(nr):
-            if col4row[cur] >= 0:
-                continue
-            searches += 1
-            remaining = np.arange(nc - 1, -1, -1)
-            spc = np.full(nc, inf, dtype=C.dtype)
-            SR, SC = [], []
-            minVal, i = T(0), cur
-            while True:
-                SR.append(i)
-                r = minVal + C[i, remaining] - u[i] - v[remaining]
-                old = spc[remaining]
-                upd = r < old
-                s = np.where(upd, r, old)
-                spc[remaining] = s
-                path[remaining[upd]] = i
-                lowest = s.min()
-                if not lowest < inf:
-                    raise ValueError("cost matrix is infeasible")
-                at = np.flatnonzero(s == lowest)
-                free = at[row4col[remaining[at]] < 0]
-                index = free[-1] if free.size else at[0]
-                minVal = s[index]
-                j = int(remaining[index])
-                SC.append(j)
-                remaining[index] = remaining[-1]
-                remaining = remaining[:-1]
-                if row4col[j] < 0:
-                    sink = j
-                    break
-                i = int(row4col[j])
-            u[cur] = u[cur] + minVal
-            others = np.array(SR[1:], dtype=np.int64)
-            u[others] = u[others] + (minVal - spc[col4row[others]])
-            SCa = np.array(SC, dtype=np.int64)
-            v[SCa] = v[SCa] - (minVal - spc[SCa])
-            j = sink
-            while True:
-                i = int(path[j])
-                row4col[j] = i
-                col4row[i], j = j, int(col4row[i])
-                if i == cur:
-                    break
-    return col4row, u, v, searches
+    return replay_state(C, col4row, row4col, u, v)
 
 
 def warm(C, col0, v0):

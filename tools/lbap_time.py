@@ -11,7 +11,8 @@ whose warm-up takes longer than --slow-s seconds is recorded from that single ru
 --context-lib: a libsanta_hip.so of another commit (the parent's).  Its lsap_solve_large_ entry is
 timed the same way on the same tensor ("lsap_large_ms"): context only -- a min-sum search takes
 other steps than a bottleneck search on the same matrix, so the ratio says nothing about either.
-One JSON line per (n, B, dtype), appended to --out."""
+One JSON line per (n, B, dtype), appended to --out.  SANTA_HIP_PKG and SANTA_HIP_LIB select the
+package and the library as in tools/lsap_time.py."""
 import argparse
 import ctypes
 import json
@@ -20,7 +21,7 @@ import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "mpi-hungarian-method_amd"))
+sys.path.insert(0, os.environ.get("SANTA_HIP_PKG") or os.path.join(ROOT, "mpi-hungarian-method_amd"))
 import torch  # noqa: E402
 import santa_hip  # noqa: E402
 from santa_hip import _lib  # noqa: E402
