@@ -3369,6 +3369,69 @@ struct Sp3LdsFused {
 #define DT_PROW_V 8
 #define DT_PROW_VE 11
 
+// The fused build's wishlist walk.  A child's packed wishlist is one 128-byte
+// line, gift r at bits 10 r .. 10 r + 9, held by the row's lane in 32 VGPRs.
+__device__ __forceinline__ void sp4_wish_line(u32x32 &G, const uint32_t *wish10, int child, bool live) {
+  const uint4 *s4 = (const uint4 *)(wish10 + (size_t)child * 32);
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    const uint4 v = live ? s4[q] : make_uint4(0, 0, 0, 0);
+    G[4 * q] = v.x;
+    G[4 * q + 1] = v.y;
+    G[4 * q + 2] = v.z;
+    G[4 * q + 3] = v.w;
+  }
+}
+
+// f(r, A, g, h) for every wish r in order: A = (n_wish - r) << 9 (an entry's
+// rank field), g the gift type and h = thead[g].  Sixteen gifts are exactly
+// five dwords: a group's dwords G[5k .. 5k + 4] are the loop's only
+// GPR-indexed moves (five per 16 wishes; a loop over 4 wishes with a
+// run-time bit position took twelve, and the scalar work to form their
+// indices), and its gifts are decoded with compile-time shifts, four per
+// sub-step (their four type-table reads issue together).  The last group
+// ends at n_wish (a multiple of 4, at most 100), not at what the line's
+// unused bits hold: gift 0 is a real type.  Group 6 is dwords 30 and 31
+// alone; it is fetched as 27 .. 31 so that no index leaves the line.
+template <class F>
+__device__ __forceinline__ void sp4_walk(const u32x32 &G, const uint32_t *thead, int nw, F &&f) {
+  int k5 = 0;
+#pragma unroll 1
+  for (int r0 = 0; r0 < nw; r0 += 16, k5 += 5) {
+    const int i5 = min(k5, 27);
+    uint32_t w[5];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) w[j] = G[i5 + j];
+    if (k5 > 27) {
+      w[0] = w[3];
+      w[1] = w[4];
+    }
+    const uint32_t A0 = (uint32_t)(nw - r0) << 9;
+    auto sub = [&](auto sc) __attribute__((always_inline)) {  // gifts 4s .. 4s + 3 of the group: bits 40s .. 40s + 39
+      constexpr int s = decltype(sc)::value;
+      const uint32_t x = s ? __builtin_amdgcn_alignbit(w[s + 1], w[s], 8 * s) : w[0];
+      const uint32_t y = w[s + 1] >> (8 * s);
+      int g[4];
+      g[0] = (int)(x & 1023u);
+      g[1] = (int)((x >> 10) & 1023u);
+      g[2] = (int)((x >> 20) & 1023u);
+      g[3] = (int)(__builtin_amdgcn_alignbit(y, x, 30) & 1023u);
+      uint32_t h[4];
+#pragma unroll
+      for (int z = 0; z < 4; ++z) h[z] = thead[g[z]];
+#pragma unroll
+      for (int z = 0; z < 4; ++z) f(r0 + 4 * s + z, A0 - ((uint32_t)(4 * s + z) << 9), g[z], h[z]);
+    };
+    sub(std::integral_constant<int, 0>{});
+    if (r0 + 4 >= nw) break;
+    sub(std::integral_constant<int, 1>{});
+    if (r0 + 8 >= nw) break;
+    sub(std::integral_constant<int, 2>{});
+    if (r0 + 12 >= nw) break;
+    sub(std::integral_constant<int, 3>{});
+  }
+}
+
 template <bool TIMED, bool FUSED>
 __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const unsigned char *rec_all) {
   if constexpr (FUSED) round_prologue(a, blockIdx.x, 0);  // (else santa_tile_kernel ran it)
@@ -3477,11 +3540,13 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
     // the types' head words, in place
     for (int t = lane; t < a.ng; t += WAVE) thead[t] = type_head_word(thead[t], csort);
     __syncthreads();
-    // -- four batches of 64 rows: pass 1 (hit count, own code), pass 2 (entries) -----
+    // -- four batches of 64 rows, one walk of the wishlist per row: the entries
+    //    0..31 to the stage, the hit count and the own code; the rows with
+    //    more than 32 hits are walked again after the last batch (below) -------------
     const int nw = a.n_wish;
-    const int ndw = (nw + 1) >> 1;
     const int cap = a.cap;  // (SP4_OVF_CAP, or lower under a test budget)
     bool fits = true;
+    uint64_t om[4];  // per batch: the lanes whose row overflows
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const int R = 64 * c + lane;
@@ -3492,99 +3557,59 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
         child = a.rows[(size_t)b * n + R];
         myt = a.types[child];
       }
-      {  // the packed wishlist: gift r at bits 10 r .. 10 r + 9 of one 128-byte line
-        const uint4 *s4 = (const uint4 *)(a.wish10 + (size_t)child * 32);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const uint4 v = live ? s4[q] : make_uint4(0, 0, 0, 0);
-          G[4 * q] = v.x;
-          G[4 * q + 1] = v.y;
-          G[4 * q + 2] = v.z;
-          G[4 * q + 3] = v.w;
-        }
-      }
-      auto gifts4 = [&](int d, int (&g)[4]) {  // gifts 2d .. 2d + 3: bits 20d .. 20d + 39
-        const int bit = 20 * d, dw = bit >> 5, sh = bit & 31;
-        const uint32_t w0 = G[dw & 31], w1 = G[(dw + 1) & 31], w2 = G[(dw + 2) & 31];
-        const uint32_t x = __builtin_amdgcn_alignbit(w1, w0, sh);
-        const uint32_t y = __builtin_amdgcn_alignbit(w2, w1, sh);
-        g[0] = (int)(x & 1023u);
-        g[1] = (int)((x >> 10) & 1023u);
-        g[2] = (int)((x >> 20) & 1023u);
-        g[3] = (int)(__builtin_amdgcn_alignbit(y, x, 30) & 1023u);
-      };
-      int lim = 32, obase = 0;
+      sp4_wish_line(G, a.wish10, child, live);
+      bool over = false;
       if (live) {
-        uint32_t total = 0;
         int ownc = 0;
+        uint16_t *srow = stage + lane * (2 * SP4_PITCH);
+        const uint32_t sa = lds_addr(srow), xlim = sa + 64u;
+        uint32_t xa = sa;  // the LDS byte address of the row's next entry: sa + 2 * (hits so far)
+        sp4_walk(G, thead, nw, [&](int r, uint32_t A, int g, uint32_t hz) __attribute__((always_inline)) {
+          const int cg = (int)(hz >> 24);
+          ownc = (g == myt) ? r + 1 : ownc;  // (the last occurrence, as the reference's overwrite)
+          // the type's first two columns at x, x + 1 whatever cg is: a slot
+          // past the row's hits so far is rewritten by the next hit or lies
+          // past the row's count (the transpose masks it by rcnt); positions
+          // from 32 on fall on the dump slots 32 and 33 (the row's pad), and
+          // an overflowing row's slot 31 is its marker (set by the transpose)
+          // (an entry is slot | a << 9, a = n_wish - rank: A; hz's bytes 0 and 1
+          //  spread to the halves of one word, stored as two 16-bit halves from
+          //  one address.  As C++ the compiler joins the two stores into one
+          //  dword store at a two-byte aligned address: the build-only launch
+          //  0.155 -> 0.242 ms.  The wave's LDS accesses complete in order, so
+          //  the compiler's wait counts stay sufficient.)
+          const uint32_t e01 = __builtin_amdgcn_perm(hz, hz, 0x0c010c00u) | (A * 0x10001u);
+          asm volatile("ds_write_b16 %0, %1\n\tds_write_b16_d16_hi %0, %1 offset:2"
+                       :
+                       : "v"(min(xa, xlim)), "v"(e01)
+                       : "memory");
+          if (__any(cg >= 3)) {
+            const int x = (int)(xa - sa) >> 1;
+            if (cg == 3) {
+              srow[x + 2 < 32 ? x + 2 : 32] = (uint16_t)(((hz >> 16) & 0xFFu) | A);
+            } else if (cg >= 4) {  // the type's columns 2.. from csort
+              const int e = (int)((hz >> 16) & 0xFFu);
 #pragma unroll 1
-        for (int d = 0; d < ndw; d += 2) {
-          int g[4];
-          gifts4(d, g);
-          uint32_t h[4];
-#pragma unroll
-          for (int z = 0; z < 4; ++z) h[z] = thead[g[z]];
-#pragma unroll
-          for (int z = 0; z < 4; ++z) {
-            total += h[z] >> 24;
-            ownc = (g[z] == myt) ? 2 * d + z + 1 : ownc;  // (the last occurrence, as the reference's overwrite)
+              for (int m = 2; m < cg; ++m) srow[x + m < 32 ? x + m : 32] = (uint16_t)((uint32_t)csort[e + m] | A);
+            }
           }
-        }
+          xa += 2u * (uint32_t)cg;
+        });
+        const uint32_t total = (xa - sa) >> 1;
         ownb |= (uint32_t)ownc << (8 * c);
-        if (total > 32u) {  // entries 31.. to the overflow list, the marker in entry 31
-          lim = 31;
+        int obase = 0;
+        over = total > 32u;
+        if (over) {  // entries 31.. to the overflow list, the marker in entry 31
           const int extra = (int)total - 31;
           obase = atomicAdd(ocnt, extra);
           if (obase + extra > cap || extra > 127) fits = false;
         }
-        ovfr[R] = lim == 31 ? (uint16_t)(obase | ((int)(total - 31u) << 9)) : (uint16_t)0;  // (0: no overflow)
-        rcnt[lane] = (uint8_t)(total > 32u ? 0x80u | 31u : total);
+        ovfr[R] = over ? (uint16_t)(obase | ((int)(total - 31u) << 9)) : (uint16_t)0;  // (0: no overflow)
+        rcnt[lane] = (uint8_t)(over ? 0x80u | 31u : total);
       } else {
         rcnt[lane] = 0;
       }
-      if (live && fits) {  // pass 2: the entries (slot | a << 9, a = n_wish - rank) in wish order
-        uint16_t *srow = stage + lane * (2 * SP4_PITCH);
-        uint16_t *orow = ovf + obase - lim;  // entry x >= lim goes to orow[x]
-        int x = 0;
-#pragma unroll 1
-        for (int d = 0; d < ndw; d += 2) {
-          int g[4];
-          gifts4(d, g);
-          uint32_t h[4];
-#pragma unroll
-          for (int z = 0; z < 4; ++z) h[z] = thead[g[z]];
-#pragma unroll
-          for (int z = 0; z < 4; ++z) {
-            const int r = 2 * d + z;
-            const uint32_t hz = h[z];
-            const uint32_t A = (uint32_t)(nw - r) << 9;
-            const int cg = (int)(hz >> 24);
-            // the type's first two columns at x, x + 1 whatever cg is: a
-            // slot past the row's hits so far is rewritten by the next hit or
-            // lies past the row's count (the transpose masks it by rcnt);
-            // positions from 32 on fall on the dump slot 32, and an
-            // overflowing row's slot 31 is its marker (set by the transpose)
-            srow[min(x, 32)] = (uint16_t)((hz & 0xFFu) | A);
-            srow[min(x, 31) + 1] = (uint16_t)(((hz >> 8) & 0xFFu) | A);
-            if (__any(cg >= 3)) {
-              if (cg == 3) {
-                srow[x + 2 < lim ? x + 2 : 32] = (uint16_t)(((hz >> 16) & 0xFFu) | A);
-              } else if (cg >= 4) {  // the type's columns 2.. from csort
-                const int e = (int)((hz >> 16) & 0xFFu);
-                for (int m = 2; m < cg; ++m) srow[x + m < lim ? x + m : 32] = (uint16_t)((uint32_t)csort[e + m] | A);
-              }
-            }
-            if (__any(x + cg > lim)) {  // entries lim.. of this row to the overflow list
-              for (int m = max(lim - x, 0); m < cg; ++m) {
-                const uint32_t cc = (m < 2 || cg == 3) ? ((hz >> (8 * m)) & 0xFFu)
-                                                       : (uint32_t)csort[((hz >> 16) & 0xFFu) + m];
-                orow[x + m] = (uint16_t)(cc | A);
-              }
-            }
-            x += cg;
-          }
-        }
-      }
+      om[c] = __ballot(over);
       if (__any(!fits)) {  // does not fit: leave the block to the fallback kernel
         if (lane == 0) leave_to_fallback(a, b);
         return;
@@ -3613,6 +3638,50 @@ __global__ __launch_bounds__(WAVE, 4) void santa_sp3_kernel(SantaArgs a, const u
           T1[16 * c + q - 32] = dw;
       }
       __syncthreads();  // (the next batch rewrites the stage)
+    }
+    // -- the rows with more than 32 hits, one per lane: entries 31.. to the
+    //    overflow list, in wish order.  (Such a row is one in eleven on the
+    //    bench's states, so walking them inside their batches would cost every
+    //    batch a second walk by a handful of lanes.) ---------------------------------
+    if (om[0] | om[1] | om[2] | om[3]) {
+      uint8_t *olist = (uint8_t *)stage;  // (the stage is free: the last transpose has read it)
+      int no = 0;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const uint32_t before =  // (overflowing rows of this batch in lower lanes)
+            __builtin_amdgcn_mbcnt_hi((uint32_t)(om[c] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)om[c], 0u));
+        if ((om[c] >> lane) & 1) olist[no + (int)before] = (uint8_t)(64 * c + lane);
+        no += __popcll(om[c]);
+      }
+      __syncthreads();
+#pragma unroll 1
+      for (int i0 = 0; i0 < no; i0 += WAVE) {
+        const bool act = i0 + lane < no;
+        int child = 0, R = 0;
+        if (act) {
+          R = olist[i0 + lane];
+          child = a.rows[(size_t)b * n + R];
+        }
+        u32x32 G;
+        sp4_wish_line(G, a.wish10, child, act);
+        if (act) {
+          uint16_t *orow = ovf + (ovfr[R] & 511u) - 31;  // entry x >= 31 goes to orow[x]
+          int x = 0;
+          sp4_walk(G, thead, nw, [&](int, uint32_t A, int, uint32_t hz) __attribute__((always_inline)) {
+            const int cg = (int)(hz >> 24);
+            if (__any(x + cg > 31)) {
+#pragma unroll 1
+              for (int m = max(31 - x, 0); m < cg; ++m) {
+                const uint32_t cc = (m < 2 || cg == 3) ? ((hz >> (8 * m)) & 0xFFu)
+                                                       : (uint32_t)csort[((hz >> 16) & 0xFFu) + m];
+                orow[x + m] = (uint16_t)(cc | A);
+              }
+            }
+            x += cg;
+          });
+        }
+      }
+      __syncthreads();  // (the solve's buffers alias the type table)
     }
   }
   for (int r = lane; r < n; r += WAVE) u_l[r] = SP3_BIAS;  // (u = 0: u_l holds u + BIAS, see the solve)
