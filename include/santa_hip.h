@@ -659,6 +659,96 @@ int lsap_solve_csr_f32(const int64_t *d_indptr, const int32_t *d_indices, const 
                        double *d_v, void *d_work, size_t work_bytes, unsigned flags, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Certificates on the CSR itself: optimality of a sparse solve, and a proof
+ * that a sparsity pattern has, or has not, a perfect matching of its rows.
+ * Nothing is densified.  Batch layout, d_shape, sizes, canonical rows and the
+ * memory-safety rule are those of lsap_solve_csr_ (an index outside [0, nc_b)
+ * never forms an address; reads for row r stay in [d_indptr[r],
+ * d_indptr[r + 1]); a row that is not canonical gives an unspecified result).
+ * The entries allocate nothing and never synchronise.  SH_ERR_ARGS, on the
+ * host before any device call, for: nr < 1, nr > nc, nc > SH_MAX_N_LARGE,
+ * B < 0; with B > 0 a null d_indptr or a null array other than d_indices,
+ * d_data and d_shape; lsap_match_csr_: work_bytes too small, d_work not
+ * 8-byte aligned.  B == 0 is a no-op after the checks; d_indices and d_data
+ * may be null when there are no entries.
+ *
+ * An EDGE of instance b is a stored entry in a live row (i < nr_b) whose column
+ * lies in [0, nc_b) and whose value is not +inf.  A stored 0.0 is an edge, a
+ * stored +inf is not; a NaN (the caller's to reject, as on the solver) counts
+ * as an edge.
+ *
+ * lsap_check_duals_csr_*: d_slack [B x 3] and d_flags [B] are bit for bit what
+ * lsap_check_duals_large_f64 / _f32 write for the densification (stored values,
+ * +inf elsewhere) with the same d_shape, d_col, d_u and d_v: the same SH_CERT_*
+ * bits, the same three values, the gap's fixed order of summation, -0.0 below
+ * +0.0 and NaN in the minimum, 0s and SH_CERT_COL for a shape outside the
+ * matrix, 0s and SH_CERT_NONE when every live col is -1, 0 for slack[0] of an
+ * empty shape.  A missing live entry has slack +inf; a chosen pair (i, col[i])
+ * that is not stored has matched slack +inf, which sets SH_CERT_TIGHT.  One
+ * rule is added, because (+inf - u) - v is not +inf for every u and v: if any
+ * live u[i] or v[j] is not finite (NaN or an infinity), and the instance is
+ * neither SH_CERT_NONE nor of a shape outside the matrix, then slack[0] is NaN
+ * and SH_CERT_SLACK is set; slack[1], slack[2] and the other bits follow the
+ * formulas over the stored entries.  d_col, d_u and d_v are read as data.
+ * Three launches, as the dense certificate: the chosen entries and the sums
+ * per instance, one pass over the stored entries, the decoding of slack[0].
+ *
+ * lsap_match_csr_*: a maximum-cardinality matching of the edges.  d_data may
+ * be null: every stored entry with a live column is then an edge.  d_work as
+ * on lsap_solve_csr_ (lsap_csr_work_bytes; it receives the edge bitmap, one
+ * 64-bit word per row and 64 columns).
+ *   d_match int32 [B x nr]: the column of each live row or -1; -1 in padded
+ *     rows.  Matched pairs are edges and no column is taken twice.  Which
+ *     maximum matching it is, is unspecified.
+ *   d_card int32 [B]: its size, the maximum.
+ *   d_wit uint8 [B x nr]: the canonical Hall violator: 1 on every live row
+ *     that an alternating path (any edge from a row, the matched edge back
+ *     from a column) reaches from an unmatched live row, the unmatched rows
+ *     included; 0 elsewhere.  All 0 when card == nr_b.  The set is the same
+ *     for every maximum matching, so d_card and d_wit are determined by the
+ *     pattern alone.
+ *   An empty or invalid shape gives card 0, -1 and 0.  `flags` is reserved: no
+ *   bit is defined (there is one launch configuration) and it is not read.
+ * Two launches: the edge bitmap, then one wave per instance.
+ *
+ * lsap_check_hall_csr_*: d_match and d_wit as lsap_match_csr_ wrote them, or
+ * anything else: they are read as data.  d_data nullable as above.
+ *   d_counts int32 [B x 3]: nM, the live rows with match != -1; nR, the live
+ *     rows with wit != 0; nN, the live columns that an edge joins to one of
+ *     those rows.
+ *   d_flags int32 [B]: SH_HALL_* bits.  Any set R of rows bounds every
+ *     matching by nr_b - (|R| - |N(R)|), so 0 proves a perfect matching of the
+ *     rows and exhibits it, and SH_HALL_DEFICIENT alone proves that there is
+ *     none and that nM is the maximum.  An empty shape gives counts 0 (and
+ *     SH_HALL_MATCH if some row's match is not -1); a shape outside the matrix
+ *     counts 0 and SH_HALL_MATCH.
+ * One launch, one workgroup per instance.
+ * ------------------------------------------------------------------------ */
+#define SH_HALL_MATCH 1     /* some match[i] of a live row is neither -1 nor an edge of row i, a
+                               column is taken twice, a padded row's match is not -1, or the
+                               shape lies outside the matrix */
+#define SH_HALL_WITNESS 2   /* nR - nN != nr_b - nM: wit does not prove that nM is the maximum */
+#define SH_HALL_DEFICIENT 4 /* nM < nr_b */
+int lsap_check_duals_csr_f64(const int64_t *d_indptr, const int32_t *d_indices, const double *d_data, int nr,
+                             int nc, int B, const int32_t *d_shape, const int32_t *d_col, const double *d_u,
+                             const double *d_v, double *d_slack, int32_t *d_flags, void *stream);
+int lsap_check_duals_csr_f32(const int64_t *d_indptr, const int32_t *d_indices, const float *d_data, int nr,
+                             int nc, int B, const int32_t *d_shape, const int32_t *d_col, const double *d_u,
+                             const double *d_v, double *d_slack, int32_t *d_flags, void *stream);
+int lsap_match_csr_f64(const int64_t *d_indptr, const int32_t *d_indices, const double *d_data, int nr,
+                       int nc, int B, const int32_t *d_shape, int32_t *d_match, int32_t *d_card,
+                       uint8_t *d_wit, void *d_work, size_t work_bytes, unsigned flags, void *stream);
+int lsap_match_csr_f32(const int64_t *d_indptr, const int32_t *d_indices, const float *d_data, int nr,
+                       int nc, int B, const int32_t *d_shape, int32_t *d_match, int32_t *d_card,
+                       uint8_t *d_wit, void *d_work, size_t work_bytes, unsigned flags, void *stream);
+int lsap_check_hall_csr_f64(const int64_t *d_indptr, const int32_t *d_indices, const double *d_data, int nr,
+                            int nc, int B, const int32_t *d_shape, const int32_t *d_match,
+                            const uint8_t *d_wit, int32_t *d_counts, int32_t *d_flags, void *stream);
+int lsap_check_hall_csr_f32(const int64_t *d_indptr, const int32_t *d_indices, const float *d_data, int nr,
+                            int nc, int B, const int32_t *d_shape, const int32_t *d_match,
+                            const uint8_t *d_wit, int32_t *d_counts, int32_t *d_flags, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Batched linear bottleneck assignment (min-max matching): for each nr x nc
  * instance, nr <= nc, the assignment of every row to a column of its own whose
  * LARGEST chosen cost is as small as possible; with SH_FLAG_MAXIMIZE the one

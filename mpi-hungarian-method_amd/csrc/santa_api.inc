@@ -1272,6 +1272,77 @@ int launch_lsap_csr(const int64_t *indptr, const int32_t *indices, const S *data
 }
 
 // ---------------------------------------------------------------------------
+// The certificates on the CSR (DESIGN.md §18): lsap_check_duals_csr_
+// (csr_cert_kernel, csr_slack_kernel, lsap_cert_final_kernel), lsap_match_csr_
+// (csr_edges_kernel into d_work, then csr_match_kernel) and
+// lsap_check_hall_csr_ (csr_hall_check_kernel).
+// The sizes and indptr are checked as on lsap_solve_csr_; `out` is the entry's
+// first required array (check_lsap_args names it col).
+// ---------------------------------------------------------------------------
+int check_csr_args(const int64_t *indptr, int nr, int n, int B, const void *out) {
+  HIP_TRY_RC(check_lsap_args(nr, n, B, (const int32_t *)out, SH_MAX_N_LARGE));
+  if (!indptr && B > 0) return fail(SH_ERR_ARGS, "null indptr");
+  return SH_OK;
+}
+
+template <typename S>
+int launch_csr_cert(const int64_t *indptr, const int32_t *indices, const S *data, int nr, int n, int B,
+                    const int32_t *shape, const int32_t *col, const double *u, const double *v, double *slack,
+                    int32_t *flg, hipStream_t s) {
+  HIP_TRY_RC(check_csr_args(indptr, nr, n, B, col));
+  if (B > 0 && (!u || !v || !slack || !flg)) return fail(SH_ERR_ARGS, "null u, v, slack or flags");
+  if (B == 0) return SH_OK;
+  static_assert(csr_cert_lds(SH_MAX_N_LARGE, SH_MAX_N_LARGE) + 512 <= 65536, "csr_cert_kernel's LDS");
+  hipLaunchKernelGGL((csr_cert_kernel<S>), dim3(B), dim3(CSR_CERT_WG), csr_cert_lds(nr, n), s, indptr, indices, data,
+                     nr, n, shape, col, u, v, slack, flg);
+  // launch_lsap_check's split: about 2048 workgroups when the batch allows, CSR_SLACK_ROWS rows each at least
+  const int chunks = std::min(std::max(1, 2048 / B), (nr + CSR_SLACK_ROWS - 1) / CSR_SLACK_ROWS);
+  const int rows_per = (nr + chunks - 1) / chunks;
+  hipLaunchKernelGGL((csr_slack_kernel<S>), dim3(B, (nr + rows_per - 1) / rows_per), dim3(CERT_WG), (size_t)n * 8, s,
+                     indptr, indices, data, nr, n, shape, u, v, slack, flg, rows_per);
+  hipLaunchKernelGGL((lsap_cert_final_kernel<double>), dim3((B + CERT_WG - 1) / CERT_WG), dim3(CERT_WG), 0, s, B,
+                     slack, flg);
+  HIP_TRY(hipGetLastError());
+  return SH_OK;
+}
+
+template <typename S>
+int launch_csr_match(const int64_t *indptr, const int32_t *indices, const S *data, int nr, int n, int B,
+                     const int32_t *shape, int32_t *match, int32_t *card, uint8_t *wit, void *work,
+                     size_t work_bytes, hipStream_t s) {
+  HIP_TRY_RC(check_csr_args(indptr, nr, n, B, match));
+  if (B > 0 && (!card || !wit)) return fail(SH_ERR_ARGS, "null card or wit");
+  if (work_bytes < lsap_csr_work_bytes(nr, n, B) || (B > 0 && !work))
+    return fail(SH_ERR_ARGS, "work buffer smaller than lsap_csr_work_bytes");
+  if ((uintptr_t)work % 8) return fail(SH_ERR_ARGS, "work buffer not 8-byte aligned");
+  const int64_t rows = (int64_t)B * nr;
+  constexpr int PREP_ROWS = CSR_PREP_WG / WAVE;
+  if ((rows + PREP_ROWS - 1) / PREP_ROWS > INT32_MAX) return fail(SH_ERR_ARGS, "B * nr too large");
+  if (B == 0) return SH_OK;
+  static_assert(csr_match_lds(SH_MAX_N_LARGE, SH_MAX_N_LARGE) <= 65536, "csr_match_kernel's LDS");
+  uint64_t *mask = (uint64_t *)work;  // (the first 8 of lsap_csr_work_bytes' 10 bytes a word)
+  hipLaunchKernelGGL((csr_edges_kernel<S>), dim3((unsigned)((rows + PREP_ROWS - 1) / PREP_ROWS)), dim3(CSR_PREP_WG),
+                     0, s, indptr, indices, data, nr, n, rows, shape, mask);
+  hipLaunchKernelGGL(csr_match_kernel, dim3(B), dim3(WAVE), csr_match_lds(nr, n), s, mask, nr, n, shape, match, card,
+                     wit);
+  HIP_TRY(hipGetLastError());
+  return SH_OK;
+}
+
+template <typename S>
+int launch_csr_hall_check(const int64_t *indptr, const int32_t *indices, const S *data, int nr, int n, int B,
+                          const int32_t *shape, const int32_t *match, const uint8_t *wit, int32_t *counts,
+                          int32_t *flg, hipStream_t s) {
+  HIP_TRY_RC(check_csr_args(indptr, nr, n, B, match));
+  if (B > 0 && (!wit || !counts || !flg)) return fail(SH_ERR_ARGS, "null wit, counts or flags");
+  if (B == 0) return SH_OK;
+  hipLaunchKernelGGL((csr_hall_check_kernel<S>), dim3(B), dim3(CERT_WG), 0, s, indptr, indices, data, nr, n, shape,
+                     match, wit, counts, flg);
+  HIP_TRY(hipGetLastError());
+  return SH_OK;
+}
+
+// ---------------------------------------------------------------------------
 // The lbap_solve_ entries (bottleneck assignment, lbap_kernel).
 // ---------------------------------------------------------------------------
 // Whether a batch of B instances with nc columns runs the multi-wave design by
@@ -1463,6 +1534,33 @@ int lsap_solve_csr_f32(const int64_t *d_indptr, const int32_t *d_indices, const 
   return launch_lsap_csr(d_indptr, d_indices, d_data, nr, nc, B, d_shape, d_col, d_cost, d_u, d_v, d_work,
                          work_bytes, flags, (hipStream_t)stream);
 }
+
+// The certificates of a CSR value type (launch_csr_cert, launch_csr_match,
+// launch_csr_hall_check).  The matching takes no launch-forcing flag: it has
+// one configuration, and `flags` is not read.
+#define SH_CSR_CERT_ENTRIES(SUF, CT)                                                                             \
+  int lsap_check_duals_csr_##SUF(const int64_t *d_indptr, const int32_t *d_indices, const CT *d_data, int nr,    \
+                                 int nc, int B, const int32_t *d_shape, const int32_t *d_col, const double *d_u, \
+                                 const double *d_v, double *d_slack, int32_t *d_flags, void *stream) {           \
+    return launch_csr_cert(d_indptr, d_indices, d_data, nr, nc, B, d_shape, d_col, d_u, d_v, d_slack, d_flags,   \
+                           (hipStream_t)stream);                                                                 \
+  }                                                                                                              \
+  int lsap_match_csr_##SUF(const int64_t *d_indptr, const int32_t *d_indices, const CT *d_data, int nr, int nc,  \
+                           int B, const int32_t *d_shape, int32_t *d_match, int32_t *d_card, uint8_t *d_wit,     \
+                           void *d_work, size_t work_bytes, unsigned flags, void *stream) {                      \
+    (void)flags;                                                                                                 \
+    return launch_csr_match(d_indptr, d_indices, d_data, nr, nc, B, d_shape, d_match, d_card, d_wit, d_work,     \
+                            work_bytes, (hipStream_t)stream);                                                    \
+  }                                                                                                              \
+  int lsap_check_hall_csr_##SUF(const int64_t *d_indptr, const int32_t *d_indices, const CT *d_data, int nr,     \
+                                int nc, int B, const int32_t *d_shape, const int32_t *d_match,                   \
+                                const uint8_t *d_wit, int32_t *d_counts, int32_t *d_flags, void *stream) {       \
+    return launch_csr_hall_check(d_indptr, d_indices, d_data, nr, nc, B, d_shape, d_match, d_wit, d_counts,      \
+                                 d_flags, (hipStream_t)stream);                                                  \
+  }
+SH_CSR_CERT_ENTRIES(f64, double)
+SH_CSR_CERT_ENTRIES(f32, float)
+#undef SH_CSR_CERT_ENTRIES
 
 #define SH_LBAP_ENTRY(SUF, CT, DT)                                                                       \
   int lbap_solve_##SUF(const CT *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,     \

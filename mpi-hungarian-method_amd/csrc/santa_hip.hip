@@ -6417,6 +6417,469 @@ __global__ __launch_bounds__(CERT_WG) void lsap_cert_final_kernel(int B, T *slac
 }
 
 // ---------------------------------------------------------------------------
+// The certificates of the sparse (CSR) entries.  None of these
+// kernels reads what lsap_csr_prep_kernel wrote; `indices` is read as data: an
+// index forms an address only after 0 <= j < nc_b, and every read of indices
+// and data for row r stays inside [indptr[r], indptr[r + 1]).
+//
+// lsap_check_duals_csr_ is the dense certificate's three launches on the
+// densification, without it:
+//   csr_cert_kernel   lsap_cert_kernel's work, one workgroup per instance: is
+//     col an assignment, the matched slacks, the signs of v and the three sums
+//     in that kernel's order (256 threads, the butterfly, the waves), so the
+//     bits are its bits.  The chosen entry of row i is found by bisection of
+//     the row's (sorted) indices for col[i], by all 16 waves; a pair that is
+//     not stored costs +inf.  It arms slack[0] for the minimum below with the
+//     key of +inf, the slack of a missing entry: +inf is the identity of the
+//     minimum over numbers, so "some live entry is missing" changes the result
+//     only when no live entry is stored at all, and then this is the result.
+//     (An empty shape keeps lsap_cert_kernel's "nothing", which decodes to 0.)
+//     The one added rule: a live u or v that is not finite arms it with the
+//     key of NaN, below every number.
+//   csr_slack_kernel  the pass over the stored entries: a workgroup takes
+//     `rows_per` rows of one instance with v of the instance in LDS, a wave a
+//     row at a time; the keys (cert_key) of (data - u[i]) - v[j] over the live
+//     entries meet in slack[0] with one atomic min per workgroup.
+//   lsap_cert_final_kernel<double>, as it is, decodes slack[0].
+// ---------------------------------------------------------------------------
+constexpr int CSR_CERT_WG = 1024;
+constexpr size_t csr_cert_lds(int nr, int nc) { return (size_t)nr * 4 + (size_t)((nc + 31) / 32) * 4; }
+
+__device__ __forceinline__ bool cert_finite(double x) { return __builtin_fabs(x) < VT<double>::inf(); }
+
+template <typename S>
+__global__ __launch_bounds__(CSR_CERT_WG) void csr_cert_kernel(const int64_t *__restrict__ indptr,
+                                                               const int32_t *__restrict__ indices,
+                                                               const S *__restrict__ data, int NR, int NC,
+                                                               const int32_t *shape, const int32_t *col,
+                                                               const double *u, const double *v, double *slack,
+                                                               int32_t *flags) {
+  extern __shared__ __align__(16) unsigned char csr_cert_smem[];
+  int32_t *off_l = (int32_t *)csr_cert_smem;  // [NR] the chosen entry's offset in its row, -1: not stored
+  uint32_t *bits = (uint32_t *)(off_l + NR);  // [ceil(NC / 32)] the columns taken
+  __shared__ double part[4][CERT_WG / WAVE];
+  __shared__ int s_flags, s_none, s_wild;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  double *out = slack + 3 * (size_t)b;
+  int nr, nc;
+  if (!lsap_shape(shape, b, NR, NC, nr, nc)) {
+    const bool empty = nr == 0 && nc >= 0 && nc <= NC;
+    if (!empty) {  // not a shape of this matrix
+      if (tid == 0) {
+        *(uint64_t *)out = ~0ull;  // (lsap_cert_final_kernel: nothing certified, 0)
+        out[1] = out[2] = 0;
+        flags[b] = SH_CERT_COL;
+      }
+      return;
+    }
+  }
+  for (int j = tid; j < (NC + 31) / 32; j += CSR_CERT_WG) bits[j] = 0;
+  if (tid == 0) s_flags = s_none = s_wild = 0;
+  __syncthreads();
+  int f = 0, none = 0, wild = 0;
+  for (int i = tid; i < NR; i += CSR_CERT_WG) {
+    off_l[i] = -1;
+    const int c = col[(size_t)b * NR + i];
+    if (i >= nr) {
+      if (c != -1) f |= SH_CERT_COL;
+      continue;
+    }
+    wild |= !cert_finite(u[(size_t)b * NR + i]);
+    if (c == -1) {
+      ++none;
+      continue;
+    }
+    if (c < 0 || c >= nc) {
+      f |= SH_CERT_COL;
+      continue;
+    }
+    const uint32_t bit = 1u << (c & 31);
+    if (atomicOr(&bits[c >> 5], bit) & bit) f |= SH_CERT_COL;
+    // the entry of column c in the row, if it is stored: the interval halves, 64 turns at most
+    const int64_t e0 = indptr[(size_t)b * NR + i];
+    int64_t lo = e0, hi = indptr[(size_t)b * NR + i + 1];
+    for (int turn = 0; turn < 64 && lo < hi; ++turn) {
+      const int64_t mid = lo + ((hi - lo) >> 1);
+      const int j = indices[mid];
+      if (j == c) {
+        if (mid - e0 <= INT32_MAX) off_l[i] = (int32_t)(mid - e0);
+        break;
+      }
+      if (j < c) lo = mid + 1;
+      else hi = mid;
+    }
+  }
+  for (int j = tid; j < nc; j += CSR_CERT_WG) wild |= !cert_finite(v[(size_t)b * NC + j]);
+  if (none) atomicAdd(&s_none, none);
+  if (wild) atomicOr(&s_wild, 1);
+  __syncthreads();
+  const int n_none = s_none;
+  if (nr >= 1 && n_none == nr) {  // no assignment at all (an infeasible solve): nothing to certify
+    if (tid == 0) {
+      *(uint64_t *)out = ~0ull;
+      out[1] = out[2] = 0;
+      flags[b] = SH_CERT_NONE;
+    }
+    return;
+  }
+  if (n_none) f |= SH_CERT_COL;
+  // lsap_cert_kernel's sums, in its order: 256 threads, then the butterfly, then the waves
+  if (tid < CERT_WG) {
+    double tmax = 0, su = 0, sv = 0, sc = 0;
+    for (int i = tid; i < nr; i += CERT_WG) {
+      const double ui = u[(size_t)b * NR + i];
+      su = su + ui;
+      const int c = col[(size_t)b * NR + i];
+      if (c < 0 || c >= nc) continue;
+      const int32_t o = off_l[i];
+      const double cc = o >= 0 ? widen_f64(data[indptr[(size_t)b * NR + i] + o]) : VT<double>::inf();
+      tmax = cert_max(tmax, cert_abs(cert_sub(cert_sub(cc, ui), v[(size_t)b * NC + c])));
+      sc = sc + cc;
+    }
+    for (int j = tid; j < nc; j += CERT_WG) {
+      const double vj = v[(size_t)b * NC + j];
+      sv = sv + vj;
+      const bool taken = (bits[j >> 5] >> (j & 31)) & 1u;
+      if (vj > 0 || (!taken && vj != 0)) f |= SH_CERT_SIGN;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      su = su + __shfl_xor(su, o, WAVE);
+      sv = sv + __shfl_xor(sv, o, WAVE);
+      sc = sc + __shfl_xor(sc, o, WAVE);
+      tmax = cert_max(tmax, __shfl_xor(tmax, o, WAVE));
+    }
+    if ((tid & 63) == 0) {
+      part[0][tid >> 6] = su;
+      part[1][tid >> 6] = sv;
+      part[2][tid >> 6] = sc;
+      part[3][tid >> 6] = tmax;
+    }
+  }
+  if (f) atomicOr(&s_flags, f);
+  __syncthreads();
+  if (tid == 0) {
+    double su = part[0][0], sv = part[1][0], sc = part[2][0], tmax = part[3][0];
+    for (int q = 1; q < CERT_WG / WAVE; ++q) {
+      su = su + part[0][q];
+      sv = sv + part[1][q];
+      sc = sc + part[2][q];
+      tmax = cert_max(tmax, part[3][q]);
+    }
+    f = s_flags;
+    if (!(tmax == 0)) f |= SH_CERT_TIGHT;
+    // the identity of csr_slack_kernel's minimum: nothing (an empty shape), +inf, or NaN
+    *(uint64_t *)out = s_wild ? 0ull : nr >= 1 ? cert_key(VT<double>::inf()) : ~0ull;
+    out[1] = tmax;
+    out[2] = (su + sv) - sc;
+    flags[b] = f;
+  }
+}
+
+constexpr int CSR_SLACK_ROWS = 32;  // a workgroup's least rows: v (8 nc bytes) is loaded once for them
+
+template <typename S>
+__global__ __launch_bounds__(CERT_WG) void csr_slack_kernel(const int64_t *__restrict__ indptr,
+                                                            const int32_t *__restrict__ indices,
+                                                            const S *__restrict__ data, int NR, int NC,
+                                                            const int32_t *shape, const double *u, const double *v,
+                                                            double *slack, const int32_t *flags, int rows_per) {
+  extern __shared__ __align__(16) unsigned char csr_slack_smem[];
+  double *v_l = (double *)csr_slack_smem;  // [nc_b] the instance's v
+  __shared__ uint64_t part[CERT_WG / WAVE];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  int nr, nc;
+  if (!lsap_shape(shape, b, NR, NC, nr, nc)) return;
+  if (flags[b] & SH_CERT_NONE) return;
+  const int r0 = blockIdx.y * rows_per, r1 = min(nr, r0 + rows_per);
+  if (r0 >= r1) return;
+  for (int j = tid; j < nc; j += CERT_WG) v_l[j] = v[(size_t)b * NC + j];
+  __syncthreads();
+  uint64_t best = ~0ull;
+  for (int i = r0 + w; i < r1; i += CERT_WG / WAVE) {  // (a wave a row)
+    const double ui = u[(size_t)b * NR + i];
+    const int64_t e1 = indptr[(size_t)b * NR + i + 1];
+    // (bounded by the row's stored entries)
+    for (int64_t e = indptr[(size_t)b * NR + i] + lane; e < e1; e += WAVE) {
+      const int j = indices[e];
+      if (j >= 0 && j < nc) best = umin64(best, cert_key((widen_f64(data[e]) - ui) - v_l[j]));
+    }
+  }
+  best = wave_min_u64_dpp(best);
+  if (lane == 0) part[w] = best;
+  __syncthreads();
+  if (tid == 0) {
+    for (int q = 1; q < CERT_WG / WAVE; ++q) best = umin64(best, part[q]);
+    if (best != ~0ull) atomicMin((unsigned long long *)(slack + 3 * (size_t)b), (unsigned long long)best);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// lsap_match_csr_ (two launches) and lsap_check_hall_csr_ (one):
+//   csr_edges_kernel  lsap_csr_prep_kernel's carve-up (a wave a row) for the
+//     matching: one 64-bit word per row and 64 columns, bit j set when the row
+//     stores column j, 0 <= j < nc_b, with a value that is not +inf (no data:
+//     every stored entry).  Padded rows get 0.
+//   csr_match_kernel  one wave per instance over those words: a maximum
+//     matching by one breadth-first augmenting-path search per row, then the
+//     canonical Hall violator.  Lane l owns word l of every row, i.e. columns
+//     64 l .. 64 l + 63: the sets of visited, taken and dead columns are one
+//     64-bit register each.  row4col, the parent row of each visited column,
+//     col4row and the row queue sit in LDS (int16: 2 (2 NC + 2 NR) bytes).  A
+//     search pops a row, loads its words (one coalesced 512-byte read), and
+//     either finds a free new column (the lowest) and augments along the
+//     parents, or queues the rows matched to the new columns.  The columns of a
+//     search that failed stay dead: no alternating path from them reaches a
+//     free column, now or after any later augmentation (which never enters
+//     them), so a deficient instance pays its reachable set once.  The witness
+//     is a last search from all unmatched rows at once under the final
+//     matching, with nothing dead: the rows it reaches are the same for every
+//     maximum matching (Dulmage-Mendelsohn).
+//   csr_hall_check_kernel  lsap_check_hall_csr_: one workgroup per instance,
+//     the taken columns and the neighbourhood of the witness as bitmaps in LDS.
+// ---------------------------------------------------------------------------
+template <typename S>
+__global__ __launch_bounds__(CSR_PREP_WG) void csr_edges_kernel(const int64_t *__restrict__ indptr,
+                                                                const int32_t *__restrict__ indices,
+                                                                const S *__restrict__ data, int NR, int NC,
+                                                                int64_t rows, const int32_t *__restrict__ shape,
+                                                                uint64_t *__restrict__ mask) {
+  __shared__ unsigned long long bits[CSR_PREP_WG / WAVE][WAVE];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int nw = (NC + 63) >> 6;
+  const int64_t g = (int64_t)blockIdx.x * (CSR_PREP_WG / WAVE) + w;  // the batch's row
+  const bool on = g < rows;                                           // (wave-uniform)
+  bits[w][lane] = 0;
+  __syncthreads();
+  if (on) {
+    int n = NC, live = NR;  // live columns and rows of the row's instance
+    if (shape) {
+      n = min(shape[2 * (size_t)(g / NR) + 1], NC);
+      live = shape[2 * (size_t)(g / NR)];
+    }
+    if (g % NR < live) {
+      const int64_t e1 = indptr[g + 1];
+      // (bounded by the row's stored entries)
+      for (int64_t e = indptr[g] + lane; e < e1; e += WAVE) {
+        const int j = indices[e];
+        if (j >= 0 && j < n && (!data || widen_f64(data[e]) != VT<double>::inf()))
+          atomicOr(&bits[w][j >> 6], 1ull << (j & 63));
+      }
+    }
+  }
+  __syncthreads();
+  if (on && lane < nw) mask[(size_t)g * nw + lane] = bits[w][lane];
+}
+
+constexpr size_t csr_match_lds(int nr, int nc) { return 2 * (2 * (size_t)nc + 2 * (size_t)nr); }
+
+// The rows matched to the columns of `nv` (this lane's new columns, all taken)
+// join the queue at `tail`, each column's parent being row r; returns the new
+// tail.  WIT: the rows are marked in wit.
+template <bool WIT>
+__device__ __forceinline__ int csr_match_push(uint64_t nv, int r, int tail, const int16_t *row4col, int16_t *parent,
+                                              int16_t *queue, uint8_t *wit) {
+  const int lane = threadIdx.x;
+  const int c = __popcll(nv);
+  int incl = c;  // inclusive scan of the lanes' counts
+#pragma unroll
+  for (int o = 1; o < WAVE; o <<= 1) {
+    const int t = __shfl_up(incl, o, WAVE);
+    if (lane >= o) incl += t;
+  }
+  int at = tail + incl - c;
+  // (at most 64 turns: one per bit of the word)
+  for (uint64_t m = nv; m; m &= m - 1) {
+    const int j = 64 * lane + __builtin_ctzll(m);
+    const int i = row4col[j];
+    if (!WIT) parent[j] = (int16_t)r;
+    queue[at++] = (int16_t)i;
+    if (WIT) wit[i] = 1;
+  }
+  return tail + __shfl(incl, WAVE - 1, WAVE);
+}
+
+__global__ __launch_bounds__(WAVE) void csr_match_kernel(const uint64_t *__restrict__ mask, int NR, int NC,
+                                                         const int32_t *shape, int32_t *match, int32_t *card,
+                                                         uint8_t *wit) {
+  extern __shared__ __align__(16) unsigned char csr_match_smem[];
+  int16_t *row4col = (int16_t *)csr_match_smem;  // [NC] the row of a taken column
+  int16_t *parent = row4col + NC;                // [NC] the row a search reached the column from
+  int16_t *col4row = parent + NC;                // [NR] -1: unmatched
+  int16_t *queue = col4row + NR;                 // [NR] the rows a search has reached, in order
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int nw = (NC + 63) >> 6;
+  int32_t *mb = match + (size_t)b * NR;
+  uint8_t *wb = wit + (size_t)b * NR;
+  int nr, nc;
+  if (!lsap_shape(shape, b, NR, NC, nr, nc)) {  // empty or invalid
+    for (int i = lane; i < NR; i += WAVE) {
+      mb[i] = -1;
+      wb[i] = 0;
+    }
+    if (lane == 0) card[b] = 0;
+    return;
+  }
+  for (int j = lane; j < NC; j += WAVE) row4col[j] = -1;
+  for (int i = lane; i < NR; i += WAVE) {
+    col4row[i] = -1;
+    wb[i] = 0;
+  }
+  __syncthreads();
+  const uint64_t *M = mask + (size_t)b * NR * nw;
+  uint64_t taken = 0, dead = 0;  // this lane's 64 columns
+  int cnt = 0;
+  // One search per row: nr turns.
+  for (int root = 0; root < nr; ++root) {
+    uint64_t vis = dead;
+    int head = 0, tail = 0, r = root, found = -1;
+    // A turn pops one row.  A row joins the queue through its own column, and a
+    // column is visited once, so there are at most nr turns.
+    for (;;) {
+      const uint64_t wd = lane < nw ? M[(size_t)r * nw + lane] : 0;
+      const uint64_t nv = wd & ~vis;
+      const uint64_t fr = nv & ~taken;
+      const uint64_t any = __ballot(fr != 0);
+      if (any) {  // (wave-uniform) the lowest free column ends the search
+        const int l = __builtin_ctzll(any);
+        const uint64_t fw = (uint64_t)__shfl((unsigned long long)fr, l, WAVE);
+        found = 64 * l + __builtin_ctzll(fw);
+        if (lane == 0) parent[found] = (int16_t)r;
+        break;
+      }
+      vis |= nv;
+      tail = csr_match_push<false>(nv, r, tail, row4col, parent, queue, nullptr);
+      __syncthreads();
+      if (head == tail) break;
+      r = __builtin_amdgcn_readfirstlane((int)queue[head++]);
+    }
+    __syncthreads();
+    if (found >= 0) {
+      if (lane == (found >> 6)) taken |= 1ull << (found & 63);
+      if (lane == 0) {
+        int j = found;
+        // The path back to the root: every hop is a row of this search, at most nr.
+        for (int hop = 0; hop < nr; ++hop) {
+          const int i = parent[j];
+          const int pj = col4row[i];
+          col4row[i] = (int16_t)j;
+          row4col[j] = (int16_t)i;
+          if (pj < 0) break;  // (the root: the only unmatched row of the search)
+          j = pj;
+        }
+      }
+      ++cnt;
+    } else {
+      dead = vis;
+    }
+    __syncthreads();
+  }
+  for (int i = lane; i < NR; i += WAVE) mb[i] = i < nr ? (int)col4row[i] : -1;
+  if (lane == 0) card[b] = cnt;
+  // The witness: the unmatched rows, then every row an alternating path reaches.
+  int tail = 0;
+  for (int i0 = 0; i0 < nr; i0 += WAVE) {  // (nr / 64 turns)
+    const int i = i0 + lane;
+    const bool un = i < nr && col4row[i] < 0;
+    const uint64_t bal = __ballot(un);
+    if (un) {
+      const int at = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+      queue[tail + at] = (int16_t)i;
+      wb[i] = 1;
+    }
+    tail += __popcll(bal);
+  }
+  __syncthreads();
+  uint64_t vis = 0;
+  // A turn pops one row and no row is queued twice: at most nr turns.
+  for (int head = 0; head < tail; ++head) {
+    const int r = __builtin_amdgcn_readfirstlane((int)queue[head]);
+    const uint64_t wd = lane < nw ? M[(size_t)r * nw + lane] : 0;
+    const uint64_t nv = wd & ~vis & taken;  // (a maximum matching: no free column is reachable)
+    vis |= nv;
+    tail = csr_match_push<true>(nv, r, tail, row4col, parent, queue, wb);
+    __syncthreads();
+  }
+}
+
+template <typename S>
+__global__ __launch_bounds__(CERT_WG) void csr_hall_check_kernel(const int64_t *__restrict__ indptr,
+                                                                 const int32_t *__restrict__ indices,
+                                                                 const S *__restrict__ data, int NR, int NC,
+                                                                 const int32_t *shape, const int32_t *match,
+                                                                 const uint8_t *wit, int32_t *counts,
+                                                                 int32_t *flags) {
+  __shared__ uint32_t taken[SH_MAX_N_LARGE / 32], nbr[SH_MAX_N_LARGE / 32];
+  __shared__ int s_flags, s_nm, s_nr, s_nn;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  int nr, nc;
+  if (!lsap_shape(shape, b, NR, NC, nr, nc)) {
+    const bool empty = nr == 0 && nc >= 0 && nc <= NC;
+    if (!empty) {  // not a shape of this matrix
+      if (tid == 0) {
+        counts[3 * (size_t)b] = counts[3 * (size_t)b + 1] = counts[3 * (size_t)b + 2] = 0;
+        flags[b] = SH_HALL_MATCH;
+      }
+      return;
+    }
+  }
+  for (int j = tid; j < SH_MAX_N_LARGE / 32; j += CERT_WG) taken[j] = nbr[j] = 0;
+  if (tid == 0) s_flags = s_nm = s_nr = s_nn = 0;
+  __syncthreads();
+  int f = 0, nm = 0, nw_ = 0;
+  for (int i = tid; i < NR; i += CERT_WG) {
+    const int m = match[(size_t)b * NR + i];
+    if (i >= nr) {
+      if (m != -1) f |= SH_HALL_MATCH;
+      continue;
+    }
+    if (wit[(size_t)b * NR + i]) ++nw_;
+    if (m == -1) continue;
+    ++nm;
+    if (m < 0 || m >= nc) {
+      f |= SH_HALL_MATCH;
+      continue;
+    }
+    const uint32_t bit = 1u << (m & 31);
+    if (atomicOr(&taken[m >> 5], bit) & bit) f |= SH_HALL_MATCH;
+  }
+  // The pass over the stored entries, a wave a row: is match[i] an edge of row
+  // i, and the columns the edges of a witness row reach.
+  for (int i = w; i < nr; i += CERT_WG / WAVE) {
+    const int m = match[(size_t)b * NR + i];
+    const bool in_r = wit[(size_t)b * NR + i] != 0, need = m >= 0 && m < nc;
+    if (!in_r && !need) continue;  // (wave-uniform)
+    bool hit = false;
+    const int64_t e1 = indptr[(size_t)b * NR + i + 1];
+    // (bounded by the row's stored entries)
+    for (int64_t e = indptr[(size_t)b * NR + i] + lane; e < e1; e += WAVE) {
+      const int j = indices[e];
+      if (j < 0 || j >= nc) continue;
+      if (data && !(widen_f64(data[e]) != VT<double>::inf())) continue;
+      if (in_r) atomicOr(&nbr[j >> 5], 1u << (j & 31));
+      hit |= j == m;
+    }
+    if (need && !__any(hit)) f |= SH_HALL_MATCH;
+  }
+  if (nm) atomicAdd(&s_nm, nm);
+  if (nw_) atomicAdd(&s_nr, nw_);
+  if (f) atomicOr(&s_flags, f);
+  __syncthreads();
+  if (tid < SH_MAX_N_LARGE / 32 && nbr[tid]) atomicAdd(&s_nn, __popc(nbr[tid]));
+  __syncthreads();
+  if (tid == 0) {
+    const int nM = s_nm, nR = s_nr, nN = s_nn;
+    f = s_flags;
+    if (nR - nN != nr - nM) f |= SH_HALL_WITNESS;
+    if (nM < nr) f |= SH_HALL_DEFICIENT;
+    counts[3 * (size_t)b] = nM;
+    counts[3 * (size_t)b + 1] = nR;
+    counts[3 * (size_t)b + 2] = nN;
+    flags[b] = f;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Warm start (the lsap_warm_ entries): two launches on one
 // stream.
 //   warm_prep_kernel  one workgroup per instance turns a previous assignment

@@ -19,8 +19,9 @@ from .api import (avg_normalized_happiness, init, optimize_block,  # noqa: F401
 from .context import SantaGPU, score_from_sums  # noqa: F401
 from .driver import my_optimizer, run_rounds  # noqa: F401
 from ._lib import (SH_CERT_COL, SH_CERT_GAP, SH_CERT_NONE, SH_CERT_RANGE, SH_CERT_SIGN,  # noqa: F401
-                   SH_CERT_SLACK, SH_CERT_TIGHT)
-from .lsap import (check_duals, check_duals_large, csr_transpose, densify,  # noqa: F401
+                   SH_CERT_SLACK, SH_CERT_TIGHT, SH_HALL_DEFICIENT, SH_HALL_MATCH, SH_HALL_WITNESS)
+from .lsap import (check_duals, check_duals_large, check_duals_sparse, check_matching_sparse,  # noqa: F401
+                   csr_transpose, densify, maximum_bipartite_matching, maximum_matching_sparse,
                    linear_sum_assignment, linear_sum_assignment_duals, linear_sum_assignment_large,
                    linear_sum_assignment_resolve, linear_sum_assignment_sparse, resolve_batched,
                    solve_batched, solve_batched_large, solve_batched_sparse, solve_hash, validate_csr)
@@ -35,8 +36,9 @@ __all__ = [
     "linear_sum_assignment_large", "solve_batched_large", "check_duals_large",
     "linear_sum_assignment_resolve", "resolve_batched",
     "linear_sum_assignment_sparse", "solve_batched_sparse", "densify", "csr_transpose", "validate_csr",
+    "check_duals_sparse", "maximum_matching_sparse", "check_matching_sparse", "maximum_bipartite_matching",
     "linear_bottleneck_assignment", "solve_bottleneck_batched", "check_bottleneck",
     "SH_CERT_COL", "SH_CERT_SLACK", "SH_CERT_TIGHT", "SH_CERT_SIGN", "SH_CERT_GAP", "SH_CERT_NONE",
-    "SH_CERT_RANGE", "my_optimizer", "run_rounds",
+    "SH_CERT_RANGE", "SH_HALL_MATCH", "SH_HALL_WITNESS", "SH_HALL_DEFICIENT", "my_optimizer", "run_rounds",
     "SantaGPU", "score_from_sums", "SantaHipError",
 ]

@@ -51,6 +51,10 @@ SH_LBCERT_COL = 1
 SH_LBCERT_VALUE = 2
 SH_LBCERT_WITNESS = 4
 SH_LBCERT_NONE = 8
+# lsap_check_hall_csr_ flag bits
+SH_HALL_MATCH = 1
+SH_HALL_WITNESS = 2
+SH_HALL_DEFICIENT = 4
 SH_ERRF_ROWS = 1
 SH_ERRF_INFEASIBLE = 2
 SH_ERRF_TYPE = 4
@@ -159,6 +163,12 @@ SIGNATURES["lsap_csr_work_bytes"] = (ctypes.c_size_t, [_I, _I, _I])
 for _suf in ("f64", "f32"):
     SIGNATURES["lsap_solve_csr_" + _suf] = (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, ctypes.c_size_t,
                                                  _U, _P])
+    # the certificate on the CSR: indptr, indices, data, nr, nc, B, shape, col, u, v, slack, flags out, stream
+    SIGNATURES["lsap_check_duals_csr_" + _suf] = (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P])
+    # the matching: indptr, indices, data, nr, nc, B, shape, match, card, wit, work, work_bytes, flags, stream
+    SIGNATURES["lsap_match_csr_" + _suf] = (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_size_t, _U, _P])
+    # its check: indptr, indices, data, nr, nc, B, shape, match, wit, counts, flags out, stream
+    SIGNATURES["lsap_check_hall_csr_" + _suf] = (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P])
 
 
 class RoundExt(ctypes.Structure):

@@ -22,6 +22,11 @@ entries): one Dijkstra for each row whose pair did not survive.
 solve_batched_sparse and linear_sum_assignment_sparse take the costs as CSR, a
 missing entry being a forbidden pair (the lsap_solve_csr_ entries): the dense
 float solve of the densification (densify), without the dense matrix.
+check_duals_sparse certifies such a solve on the CSR itself, and
+maximum_matching_sparse, check_matching_sparse and maximum_bipartite_matching
+find and prove a maximum-cardinality matching of the sparsity pattern: a
+perfect matching of the rows, or a Hall violator where there is none (the
+lsap_check_duals_csr_, lsap_match_csr_ and lsap_check_hall_csr_ entries).
 """
 from __future__ import annotations
 
@@ -496,6 +501,49 @@ def _csr_parts(crow, col_indices, values, shape):
     return crow, col_indices, values, tuple(int(s) for s in shape)
 
 
+def _sparse_batch(crow, col_indices, values, shape, shapes, validate, pattern=False):
+    """The argument checks of a sparse batched call, in solve_batched_sparse's
+    order -> (crow, col_indices, values, (B, NR, NC), its Batch); values
+    float64 or float32.  pattern: values may be None (every stored entry counts),
+    and stays None."""
+    crow, col_indices, values, shape = _csr_parts(crow, col_indices, values, shape)
+    B, NR, NC = shape
+    if B < 0 or NR < 0 or NC < 0:
+        raise ValueError(f"negative size in shape {shape}")
+    if NR > NC:
+        raise ValueError(f"a sparse batch must be wide, got [{NR}, {NC}]: transpose it so that NR <= NC")
+    if values is None and pattern:
+        p = plan(shape, torch.float64, _lib.SH_MAX_N_LARGE, shapes)
+        if validate:
+            validate_csr(crow, col_indices, torch.zeros(col_indices.numel(), dtype=torch.float32,
+                                                        device=col_indices.device), shape, p.shapes)
+        elif crow.numel() != B * NR + 1:
+            raise ValueError("crow must have B * NR + 1 entries")
+        return crow, col_indices, None, shape, p
+    if values.is_complex():
+        raise TypeError(f"unsupported dtype {values.dtype}")
+    if values.dtype not in (torch.float64, torch.float32):
+        values = values.to(torch.float64)
+    p = plan(shape, values.dtype, _lib.SH_MAX_N_LARGE, shapes)
+    if validate:
+        validate_csr(crow, col_indices, values, shape, p.shapes)
+    elif crow.numel() != B * NR + 1 or col_indices.numel() != values.numel():
+        raise ValueError("crow must have B * NR + 1 entries, col_indices and values equal lengths")
+    return crow, col_indices, values, shape, p
+
+
+def _sparse_operands(p, crow, col_indices, values, maximize):
+    """What the CSR entries read, after require_gpu(): int64 crow, int32
+    indices, the values of the problem to minimise (None stays None) and the
+    shapes on the device (None: not ragged)."""
+    crow = crow.to(torch.int64).contiguous()
+    col_indices = col_indices.to(torch.int32).contiguous()
+    if values is not None:
+        values = (-values if maximize else values).contiguous()
+    dev = values.device if values is not None else crow.device
+    return crow, col_indices, values, (p.shapes_on(dev) if p.shapes is not None else None)
+
+
 def solve_batched_sparse(crow, col_indices=None, values=None, shape=None, with_cost: bool = True,
                          flags: int = 0, shapes=None, maximize: bool = False, duals: bool = False,
                          validate: bool = True):
@@ -519,29 +567,13 @@ def solve_batched_sparse(crow, col_indices=None, values=None, shape=None, with_c
     result, but nothing outside the buffers is touched.  flags: SH_FLAG_F64_MW /
     SH_FLAG_F64_SW as in solve_batched_large; SH_FLAG_BUILD_ONLY runs the first
     pass over the CSR alone and leaves the outputs unwritten (phase timing)."""
-    crow, col_indices, values, shape = _csr_parts(crow, col_indices, values, shape)
+    crow, col_indices, values, shape, p = _sparse_batch(crow, col_indices, values, shape, shapes, validate)
     B, NR, NC = shape
-    if B < 0 or NR < 0 or NC < 0:
-        raise ValueError(f"negative size in shape {shape}")
-    if NR > NC:
-        raise ValueError(f"a sparse batch must be wide, got [{NR}, {NC}]: transpose it so that NR <= NC")
-    if values.is_complex():
-        raise TypeError(f"unsupported dtype {values.dtype}")
-    if values.dtype not in (torch.float64, torch.float32):
-        values = values.to(torch.float64)
-    p = plan(shape, values.dtype, _lib.SH_MAX_N_LARGE, shapes)
-    if validate:
-        validate_csr(crow, col_indices, values, shape, p.shapes)
-    elif crow.numel() != B * NR + 1 or col_indices.numel() != values.numel():
-        raise ValueError("crow must have B * NR + 1 entries, col_indices and values equal lengths")
     dev = values.device
     if p.empty:
         return empty_result(p, with_cost, duals, torch.float64, dev)
     require_gpu()
-    crow = crow.to(torch.int64).contiguous()
-    col_indices = col_indices.to(torch.int32).contiguous()
-    values = (-values if maximize else values).contiguous()
-    shape_dev = p.shapes_on(dev) if p.shapes is not None else None
+    crow, col_indices, values, shape_dev = _sparse_operands(p, crow, col_indices, values, maximize)
     L = _lib.lib()
     nbytes = int(L.lsap_csr_work_bytes(NR, NC, B))
     work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -557,6 +589,118 @@ def solve_batched_sparse(crow, col_indices=None, values=None, shape=None, with_c
         if duals:
             u, v = -u, -v
     return (col, cost, u, v) if duals else (col, cost)
+
+
+# ---------------------------------------------------------------------------
+# Certificates on the CSR itself: nothing is densified.  An
+# edge is a stored entry of the live corner whose value is not +inf.
+# ---------------------------------------------------------------------------
+def check_duals_sparse(crow, col_indices, values, shape, col, u, v, shapes=None, maximize: bool = False,
+                       validate: bool = True):
+    """Certify (col, u, v) -- as solve_batched_sparse(duals=True) returns them,
+    for the same batch, shapes and maximize -- in one pass over the stored
+    entries: (slack float64 [B, 3], flags int32 [B]), bit for bit the
+    (slack_min, tight_max, gap) and flags of check_duals_large on the
+    densification (densify), a missing entry having slack +inf.  One rule is
+    added: a live u or v that is not finite makes slack[:, 0] NaN and sets
+    SH_CERT_SLACK (unless the instance is SH_CERT_NONE).  maximize certifies the
+    negated problem, as check_duals does.  col may have any integer dtype; u and
+    v are float64.  The batch, `shapes` and `validate` are solve_batched_sparse's."""
+    crow, col_indices, values, shape, p = _sparse_batch(crow, col_indices, values, shape, shapes, validate)
+    check_solution(p, values.dtype, col, u, v)
+    dev = values.device
+    flags = torch.zeros(p.B, dtype=torch.int32, device=dev)
+    slack = torch.zeros((p.B, 3), dtype=torch.float64, device=dev)
+    if p.empty:
+        return slack, flags
+    require_gpu()
+    crow, col_indices, values, shape_dev = _sparse_operands(p, crow, col_indices, values, maximize)
+    if maximize:
+        u, v = -u, -v
+    col, u, v = narrow_col(col).contiguous(), u.contiguous(), v.contiguous()
+    nnz = values.numel()
+    rc = getattr(_lib.lib(), "lsap_check_duals_csr_" + DTYPE_SUFFIX[values.dtype])(
+        _p(crow), _p(col_indices) if nnz else None, _p(values) if nnz else None, p.NR, p.NC, p.B, _p(shape_dev),
+        _p(col), _p(u), _p(v), _p(slack), _p(flags), current_stream_handle(dev))
+    _lib.check(rc, "lsap_check_duals_csr")
+    return slack, flags
+
+
+def maximum_matching_sparse(crow, col_indices=None, values=None, shape=None, shapes=None, maximize: bool = False,
+                            validate: bool = True, flags: int = 0):
+    """A maximum-cardinality matching of every instance's edges, batched
+    (scipy.sparse.csgraph.maximum_bipartite_matching's problem), with the proof
+    of its size: (match int32 [B, NR], card int32 [B], wit uint8 [B, NR]).
+
+    The batch is solve_batched_sparse's: the triple with shape = (B, NR, NC), or
+    one 2-D torch.sparse_csr tensor.  An edge is a stored entry whose value is
+    not +inf (with maximize: not -inf); values=None means pattern only, every
+    stored entry an edge.  match[b, i] is the column of row i or -1 (-1 in
+    padded rows), card[b] the number of matched rows, the maximum.  wit[b] is the
+    canonical Hall violator: 1 on every live row that an alternating path
+    reaches from an unmatched row, all 0 when card == nr_b.  card and wit do
+    not depend on which maximum matching was found; match need only be valid.
+    check_matching_sparse checks the three against the CSR.  It is independent
+    of the cost solver: card == nr_b exactly when solve_batched_sparse finds an
+    assignment.  flags is reserved (one launch configuration)."""
+    crow, col_indices, values, shape = _csr_parts(crow, col_indices, values, shape)
+    if values is not None and maximize:
+        values = -values  # (before the validation: the forbidden value is +inf from here on)
+    crow, col_indices, values, shape, p = _sparse_batch(crow, col_indices, values, shape, shapes, validate, pattern=True)
+    dev = crow.device
+    match = torch.full((p.B, p.NR), -1, dtype=torch.int32, device=dev)
+    card = torch.zeros(p.B, dtype=torch.int32, device=dev)
+    wit = torch.zeros((p.B, p.NR), dtype=torch.uint8, device=dev)
+    if p.empty:
+        return match, card, wit
+    require_gpu()
+    crow, col_indices, values, shape_dev = _sparse_operands(p, crow, col_indices, values, False)
+    L = _lib.lib()
+    nbytes = int(L.lsap_csr_work_bytes(p.NR, p.NC, p.B))
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    entry = getattr(L, "lsap_match_csr_" + (DTYPE_SUFFIX[values.dtype] if values is not None else "f64"))
+    nnz = col_indices.numel()
+    rc = entry(_p(crow), _p(col_indices) if nnz else None, _p(values) if nnz else None, p.NR, p.NC, p.B,
+               _p(shape_dev), _p(match), _p(card), _p(wit), _p(work), nbytes, flags, current_stream_handle(dev))
+    _lib.check(rc, "lsap_match_csr")
+    return match, card, wit
+
+
+def check_matching_sparse(crow, col_indices, values, shape, match, wit, shapes=None, maximize: bool = False):
+    """Check (match, wit) -- as maximum_matching_sparse returns them for the same
+    batch, shapes and maximize, or anything else: they are read as data --
+    against the CSR: (counts int32 [B, 3], flags int32 [B]).
+
+    counts = (nM, nR, nN): the live rows with match != -1, the live rows with
+    wit != 0, and the live columns an edge joins to one of those rows.  flags:
+    SH_HALL_MATCH (match is no matching of the edges), SH_HALL_WITNESS
+    (nR - nN != nr_b - nM) and SH_HALL_DEFICIENT (nM < nr_b).  Any row set R
+    bounds every matching by nr_b - (|R| - |N(R)|): flags == 0 proves a perfect
+    matching of the rows and exhibits it, SH_HALL_DEFICIENT alone proves there
+    is none and that nM is the maximum.  match [B, NR] may have any integer
+    dtype, wit [B, NR] is uint8 or bool; values may be None (pattern only)."""
+    if values is not None and maximize:
+        values = -values
+    crow, col_indices, values, shape, p = _sparse_batch(crow, col_indices, values, shape, shapes, False, pattern=True)
+    if tuple(match.shape) != (p.B, p.NR) or tuple(wit.shape) != (p.B, p.NR):
+        raise ValueError(f"expected match and wit of shape [{p.B}, {p.NR}]")
+    if wit.dtype not in (torch.uint8, torch.bool):
+        raise TypeError("wit must be uint8 or bool")
+    dev = crow.device
+    counts = torch.zeros((p.B, 3), dtype=torch.int32, device=dev)
+    flags = torch.zeros(p.B, dtype=torch.int32, device=dev)
+    match = narrow_col(match)
+    if p.empty:
+        return counts, flags
+    require_gpu()
+    crow, col_indices, values, shape_dev = _sparse_operands(p, crow, col_indices, values, False)
+    match, wit = match.contiguous(), wit.to(torch.uint8).contiguous()
+    entry = getattr(_lib.lib(), "lsap_check_hall_csr_" + (DTYPE_SUFFIX[values.dtype] if values is not None else "f64"))
+    nnz = col_indices.numel()
+    rc = entry(_p(crow), _p(col_indices) if nnz else None, _p(values) if nnz else None, p.NR, p.NC, p.B,
+               _p(shape_dev), _p(match), _p(wit), _p(counts), _p(flags), current_stream_handle(dev))
+    _lib.check(rc, "lsap_check_hall_csr")
+    return counts, flags
 
 
 def _csr_of(A):
@@ -604,3 +748,28 @@ def linear_sum_assignment_sparse(A, maximize: bool = False, device: int | str = 
                                torch.from_numpy(np.ascontiguousarray(data)).to(dev), shape=(1, nr, nc),
                                with_cost=False, maximize=maximize, duals=duals)
     return single_result(out[0], tall, *out[2:])  # (the duals come back in the matrix's own signs)
+
+
+def maximum_bipartite_matching(A, device: int | str = 0):
+    """scipy.sparse.csgraph.maximum_bipartite_matching(A, perm_type="column")
+    on the GPU: an int64 numpy array [nr] with the column matched to each row, -1
+    for a row without one.  Every stored entry is an edge, whatever its value,
+    as in scipy.  A: the operands of linear_sum_assignment_sparse, up to
+    SH_MAX_N_LARGE on the longer side; tall input is matched as its transpose
+    and inverted.  The size of the matching is scipy's; which maximum matching
+    it is, is not."""
+    indptr, indices, _, (nr, nc) = _csr_of(A)
+    if nr == 0 or nc == 0:
+        return np.full(nr, -1, dtype=np.int64)
+    if max(nr, nc) > _lib.SH_MAX_N_LARGE:
+        raise ValueError(f"max(nr, nc) = {max(nr, nc)} > {_lib.SH_MAX_N_LARGE}")
+    tall = nr > nc
+    if tall:
+        indptr, indices, _, (nr, nc) = csr_transpose(indptr, indices, np.zeros(indices.size), (nr, nc))
+    dev = device_of(device)
+    match, _, _ = maximum_matching_sparse(torch.from_numpy(np.ascontiguousarray(indptr, dtype=np.int64)).to(dev),
+                                          torch.from_numpy(np.ascontiguousarray(indices, dtype=np.int32)).to(dev),
+                                          None, shape=(1, nr, nc))
+    if tall:
+        match = invert_tall(match, nc)
+    return match[0].cpu().numpy().astype(np.int64)
