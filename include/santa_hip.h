@@ -659,6 +659,56 @@ int lsap_solve_csr_f32(const int64_t *d_indptr, const int32_t *d_indices, const 
                        double *d_v, void *d_work, size_t work_bytes, unsigned flags, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Warm start on sparse (CSR) costs: lsap_warm_f64 / _f32 on the
+ * densification (the stored values, +inf elsewhere), without densifying.  For
+ * the same d_shape, previous d_col and previous d_v the outputs are those of
+ * the dense warm entry on that matrix: d_col and d_kept the same integers,
+ * d_cost the same bits (the same chosen values in the same fixed order), d_u
+ * and d_v equal by value (of two zeros of different sign either may be stored:
+ * the stored entries are met in another order than a dense row's; no decision
+ * depends on it).
+ *
+ * Batch layout, d_shape, canonical rows, d_work (lsap_csr_work_bytes, 8-byte
+ * aligned) and the memory-safety rule are those of lsap_solve_csr_: an index
+ * outside [0, nc_b) never forms an address, and reads of d_indices and d_data
+ * for row r stay inside [d_indptr[r], d_indptr[r + 1]).  d_col and d_v are in /
+ * out, d_u is out, d_cost and d_kept are nullable, as on lsap_warm_, and
+ * everything said there holds: the previous state is data and may be anything
+ * (columns out of range, duplicates with the lower row winning, NaN, infinite
+ * or positive duals counting as 0); padded rows get -1, padded slots 0; an
+ * empty or invalid shape -1, cost 0, zero duals, kept 0; an instance without a
+ * perfect matching of its rows -1 everywhere, cost 0 and NaN duals in its live
+ * slots, with kept 0 when the first pass itself meets a row without an edge
+ * and the first pass's count otherwise; the result is optimal, independent of
+ * the launch configuration, and on ties need not be the cold entries'
+ * permutation.  A change of the pattern is data like any other: a previously
+ * chosen pair that is no longer stored (or stored as +inf) is not tight and is
+ * dropped, a new entry is an edge.
+ *
+ * Three launches on the stream: the pass over the CSR that fills d_work (as on
+ * lsap_solve_csr_), the first pass of lsap_warm_ on the stored entries, and the
+ * continuation, chosen by nc alone (one wave up to 64 columns, four waves up
+ * to 1024, eight above).  Nothing is allocated and no call synchronises.
+ *
+ * flags: SH_FLAG_BUILD_ONLY has lsap_warm_'s meaning, not lsap_solve_csr_'s: it
+ * stops after the second launch and leaves the start state in d_col, d_u, d_v
+ * and d_kept, d_cost untouched.  SH_FLAG_F64_MW / SH_FLAG_F64_SW are ignored.
+ *
+ * SH_ERR_ARGS, checked on the host before any device call, for: nr < 1,
+ * nr > nc, nc > SH_MAX_N_LARGE, B < 0; with B > 0 a null d_indptr, d_col, d_u
+ * or d_v; work_bytes too small, d_work null or not 8-byte aligned; B * nr too
+ * large for the first pass's grid.  B == 0 is a no-op after the checks;
+ * d_indices and d_data may be null when there are no entries (every non-empty
+ * instance is then infeasible).
+ * ------------------------------------------------------------------------ */
+int lsap_warm_csr_f64(const int64_t *d_indptr, const int32_t *d_indices, const double *d_data, int nr, int nc,
+                      int B, const int32_t *d_shape, int32_t *d_col, double *d_cost, double *d_u, double *d_v,
+                      int32_t *d_kept, void *d_work, size_t work_bytes, unsigned flags, void *stream);
+int lsap_warm_csr_f32(const int64_t *d_indptr, const int32_t *d_indices, const float *d_data, int nr, int nc,
+                      int B, const int32_t *d_shape, int32_t *d_col, double *d_cost, double *d_u, double *d_v,
+                      int32_t *d_kept, void *d_work, size_t work_bytes, unsigned flags, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Certificates on the CSR itself: optimality of a sparse solve, and a proof
  * that a sparsity pattern has, or has not, a perfect matching of its rows.
  * Nothing is densified.  Batch layout, d_shape, sizes, canonical rows and the

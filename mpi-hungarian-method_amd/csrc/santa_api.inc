@@ -1271,6 +1271,51 @@ int launch_lsap_csr(const int64_t *indptr, const int32_t *indices, const S *data
   return launch_f64(CsrF64<S>{indptr, data, mask, pre}, nr, n, B, shape, col, cost, du, dv, flags, s);
 }
 
+// The lsap_warm_csr_ entries (DESIGN.md §19): three launches on the stream,
+// the prep above, warm_csr_prep_kernel and (unless SH_FLAG_BUILD_ONLY, which
+// here has launch_warm's meaning: the start state) the continuation by
+// launch_warm's float table, which goes by the column count alone.
+// SH_FLAG_F64_MW / _SW are ignored.  Every check precedes the first launch.
+template <typename S>
+int launch_warm_csr(const int64_t *indptr, const int32_t *indices, const S *data, int nr, int n, int B,
+                    const int32_t *shape, int32_t *col, double *cost, double *du, double *dv, int32_t *kept,
+                    void *work, size_t work_bytes, unsigned flags, hipStream_t s) {
+  HIP_TRY_RC(check_lsap_args(nr, n, B, col, SH_MAX_N_LARGE));
+  if (!indptr && B > 0) return fail(SH_ERR_ARGS, "null indptr");
+  if ((!du || !dv) && B > 0) return fail(SH_ERR_ARGS, "null u or v");
+  if (work_bytes < lsap_csr_work_bytes(nr, n, B) || (B > 0 && !work))
+    return fail(SH_ERR_ARGS, "work buffer smaller than lsap_csr_work_bytes");
+  if ((uintptr_t)work % 8) return fail(SH_ERR_ARGS, "work buffer not 8-byte aligned");
+  const int64_t rows = (int64_t)B * nr;
+  constexpr int PREP_ROWS = CSR_PREP_WG / WAVE;
+  if ((rows + PREP_ROWS - 1) / PREP_ROWS > INT32_MAX) return fail(SH_ERR_ARGS, "B * nr too large");
+  if (B == 0) return SH_OK;
+  uint64_t *mask = (uint64_t *)work;
+  uint16_t *pre = (uint16_t *)(mask + csr_words(nr, n, B));
+  hipLaunchKernelGGL(lsap_csr_prep_kernel, dim3((unsigned)((rows + PREP_ROWS - 1) / PREP_ROWS)), dim3(CSR_PREP_WG),
+                     0, s, indptr, indices, nr, n, rows, shape, mask, pre);
+  hipLaunchKernelGGL((warm_csr_prep_kernel<S>), dim3(B), dim3(PREP_WG), warm_prep_lds(nr, n), s, indptr, data, mask,
+                     pre, nr, n, shape, col, du, dv, kept);
+  HIP_TRY(hipGetLastError());
+  if (flags & SH_FLAG_BUILD_ONLY) return SH_OK;
+  auto mw = [&](auto cfg) {
+    using C_ = decltype(cfg);
+    hipLaunchKernelGGL((warm_csr_mw_kernel<C_::NW, C_::K, S, C_::FB>), dim3(B), dim3(C_::NW * WAVE),
+                       lsap_f64_mw_lds(nr, n, C_::NW, C_::FB), s, indptr, data, mask, pre, nr, n, shape, col, cost, du,
+                       dv);
+    return SH_OK;
+  };
+  if (n > SH_MAX_N) with_large_f64_cfg(n, mw);
+  else if (n > 512) mw(BigCfg<4, 4, 10>{});
+  else if (n > 256) mw(BigCfg<4, 2, 10>{});
+  else if (n > WAVE) mw(BigCfg<4, 1, 10>{});
+  else
+    hipLaunchKernelGGL((warm_csr_kernel<1, S>), dim3(B), dim3(WAVE), lsap_f64_lds(nr), s, indptr, data, mask, pre, nr,
+                       n, shape, col, cost, du, dv);
+  HIP_TRY(hipGetLastError());
+  return SH_OK;
+}
+
 // ---------------------------------------------------------------------------
 // The certificates on the CSR (DESIGN.md §18): lsap_check_duals_csr_
 // (csr_cert_kernel, csr_slack_kernel, lsap_cert_final_kernel), lsap_match_csr_
@@ -1534,6 +1579,20 @@ int lsap_solve_csr_f32(const int64_t *d_indptr, const int32_t *d_indices, const 
   return launch_lsap_csr(d_indptr, d_indices, d_data, nr, nc, B, d_shape, d_col, d_cost, d_u, d_v, d_work,
                          work_bytes, flags, (hipStream_t)stream);
 }
+
+// The warm-start entry of a CSR value type (launch_warm_csr): d_col and d_v are
+// in / out, d_u out, d_cost and d_kept nullable.
+#define SH_WARM_CSR_ENTRY(SUF, CT)                                                                              \
+  int lsap_warm_csr_##SUF(const int64_t *d_indptr, const int32_t *d_indices, const CT *d_data, int nr, int nc,  \
+                          int B, const int32_t *d_shape, int32_t *d_col, double *d_cost, double *d_u,           \
+                          double *d_v, int32_t *d_kept, void *d_work, size_t work_bytes, unsigned flags,        \
+                          void *stream) {                                                                       \
+    return launch_warm_csr(d_indptr, d_indices, d_data, nr, nc, B, d_shape, d_col, d_cost, d_u, d_v, d_kept,    \
+                           d_work, work_bytes, flags, (hipStream_t)stream);                                     \
+  }
+SH_WARM_CSR_ENTRY(f64, double)
+SH_WARM_CSR_ENTRY(f32, float)
+#undef SH_WARM_CSR_ENTRY
 
 // The certificates of a CSR value type (launch_csr_cert, launch_csr_match,
 // launch_csr_hall_check).  The matching takes no launch-forcing flag: it has

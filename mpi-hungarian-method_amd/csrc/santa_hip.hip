@@ -7045,6 +7045,152 @@ __global__ __launch_bounds__(PREP_WG) void warm_prep_kernel(const S *C, int NR, 
   }
 }
 
+// warm_prep_kernel on CSR costs (the lsap_warm_csr_ entries):
+// the same seven steps on the densification (the stored values, +inf
+// elsewhere), after lsap_csr_prep_kernel, in float64.
+//   4  one wave a row: its lanes load the row's nw <= 64 (mask, prefix) words
+//      at once, then the wave walks the words that hold an entry; the lane of a
+//      set bit reads its value (CsrLoader's address: data[indptr[i] + pre +
+//      rank]) and does the one subtraction.  A missing entry would give +inf -
+//      v[j] = +inf, which no minimum keeps: it is skipped.  A row without a
+//      live edge keeps u = +inf and makes the instance infeasible.
+//   5  the value of (i, col0[i]) is CsrLoader::at's: +inf when not stored, so
+//      the pair is dropped.
+//   6  column j of every row is CsrLoader::at(i, j), three dependent loads.
+// The entries are met in another order than the dense wave's, so of two zeros
+// of different sign the minimum may keep the other one; nothing else differs.
+// Memory safety is lsap_csr_kernel's: `indices` is not read here at all, a
+// value's address comes from the prep's words alone (a set bit is a column
+// in [0, nc_b), and pre + rank stays below the row's entry count), and v is
+// indexed by 64 q + lane only under a set bit.
+template <typename S>
+__global__ __launch_bounds__(PREP_WG) void warm_csr_prep_kernel(const int64_t *indptr, const S *data,
+                                                                const uint64_t *mask, const uint16_t *pre, int NR,
+                                                                int NC, const int32_t *shape, int32_t *col,
+                                                                double *du, double *dv, int32_t *kept) {
+  using T = double;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ int s_qt, s_bad, s_kept;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  int nr, n;  // live rows and columns (see lsap_i64_kernel)
+  if (!lsap_shape(shape, b, NR, NC, nr, n)) {
+    lsap_no_instance<PREP_WG>(col, (T *)nullptr, b, NR, NC, du, dv);
+    if (tid == 0 && kept) kept[b] = 0;
+    return;
+  }
+  size_t off = 0;
+  T *u_l;
+  int16_t *r4c_l, *c4r_l, *q_l;
+  WARM_PREP_LDS(LDS_CARVE, nr, n)
+  int32_t *claim = (int32_t *)u_l;
+  int32_t *col_b = col + (size_t)b * NR;
+  T *u_b = du + (size_t)b * NR, *v_b = dv + (size_t)b * NC;
+  const int nw = (NC + 63) >> 6;
+  const CsrLoader<1, 1, S> ld{indptr + (size_t)b * NR, data, mask + (size_t)b * NR * nw, pre + (size_t)b * NR * nw,
+                              nw};
+  const bool wide = nr < n;
+  const T INF = VT<T>::inf();
+  if (tid == 0) s_qt = s_bad = s_kept = 0;
+  for (int j = tid; j < n; j += PREP_WG) {  // 1
+    v_b[j] = warm_clean_v(v_b[j]);
+    claim[j] = INT32_MAX;
+  }
+  __syncthreads();
+  for (int i = tid; i < nr; i += PREP_WG) {  // 2
+    const int j = col_b[i];
+    const bool ok = j >= 0 && j < n;
+    c4r_l[i] = ok ? (int16_t)j : (int16_t)-1;
+    if (ok) atomicMin(&claim[j], i);
+  }
+  __syncthreads();
+  for (int j = tid; j < n; j += PREP_WG) {  // 3
+    const int r = claim[j];
+    r4c_l[j] = (r == INT32_MAX) ? (int16_t)-1 : (int16_t)r;
+    if (wide && r == INT32_MAX) v_b[j] = 0;
+  }
+  __syncthreads();  // (the claims are read: u_l may be written; v is final up to step 6)
+  for (int i = w; i < nr; i += PREP_WG / WAVE) {  // 4 and 5
+    const size_t r = (size_t)i * nw;
+    const S *row = ld.data + ld.indptr[i];
+    const int ql = min(lane, nw - 1);  // (a lane past the row's last word holds an empty one)
+    const uint64_t mw = (lane < nw) ? ld.mask[r + ql] : 0;
+    const int pw = ld.pre[r + ql];
+    // (Walking all nw words without a branch, four words' loads in flight as in
+    // CsrLoader::load, measured 3 % to 60 % slower than skipping the empty
+    // words: DESIGN.md §19.)
+    uint64_t words = __ballot(mw != 0);  // the words that hold an entry
+    T m = INF;
+    while (words) {
+      const int q = __builtin_ctzll(words);
+      words &= words - 1;
+      const uint64_t mq = readlane_u64(mw, q);
+      const int pq = __builtin_amdgcn_readlane(pw, q);
+      if ((mq >> lane) & 1) {
+        const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mq >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mq, 0u));
+        const T x = cert_sub(widen_f64(row[pq + rank]), v_b[64 * q + lane]);
+        m = (x < m) ? x : m;
+      }
+    }
+    m = wave_min(m);
+    if (lane == 0) {
+      u_l[i] = m;
+      if (!(m < INF)) s_bad = 1;
+      const int j = c4r_l[i];
+      if (j >= 0) {
+        const bool mine = r4c_l[j] == i;  // (only row r4c_l[j] ever writes that slot)
+        const T vj = v_b[j];
+        if (!(mine && cert_sub(ld.at(i, j), vj) == m)) {
+          c4r_l[i] = -1;
+          if (mine) {
+            r4c_l[j] = -1;
+            if (wide && vj < 0) q_l[atomicAdd(&s_qt, 1)] = (int16_t)j;
+          }
+        }
+      }
+    }
+  }
+  if (wide) {  // 6
+    for (int pop = 0; pop < n; ++pop) {
+      __syncthreads();  // the pushes and u of the pop before (or of step 5)
+      if (pop >= s_qt) break;  // (block-uniform: nobody pushes between this barrier and the next)
+      const int j = q_l[pop];
+      if (tid == 0) v_b[j] = 0;
+      for (int i = tid; i < nr; i += PREP_WG) {
+        const T c = ld.at(i, j);
+        if (c < u_l[i]) {
+          u_l[i] = c;
+          const int jp = c4r_l[i];
+          if (jp >= 0) {
+            c4r_l[i] = -1;
+            r4c_l[jp] = -1;
+            if (v_b[jp] < 0) q_l[atomicAdd(&s_qt, 1)] = (int16_t)jp;
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const bool bad = s_bad;
+  int k = 0;
+  for (int i = tid; i < NR; i += PREP_WG) {
+    const int c = (i < nr && !bad) ? c4r_l[i] : -1;
+    col_b[i] = c;
+    k += c >= 0;
+    u_b[i] = (i < nr) ? (bad ? __builtin_nan("") : u_l[i]) : 0.0;
+  }
+  for (int j = tid; j < NC; j += PREP_WG) {
+    if (j >= n) v_b[j] = 0;
+    else if (bad) v_b[j] = __builtin_nan("");
+  }
+  if (kept) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) k += __shfl_xor(k, o, WAVE);
+    if (lane == 0 && k) atomicAdd(&s_kept, k);
+    __syncthreads();
+    if (tid == 0) kept[b] = s_kept;
+  }
+}
+
 // The continuation on integer costs: lsap_i64_kernel's duals form with the
 // state loaded in place of the empty one (col, du, dv are in / out).
 template <int NW, int K, typename S, int FB>
@@ -7196,6 +7342,102 @@ __global__ __launch_bounds__(NW * WAVE) void warm_f64_mw_kernel(const S *C, int 
     double acc = 0;
     for (int i = tid; i < NR; i += WAVE)
       if (st == 0 && i < nr) acc += widen_f64(C[base + (size_t)i * NC + Sl.c4r[i]]);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, WAVE);
+    if (tid == 0) cost[b] = acc;
+  }
+}
+
+// The float continuations on CSR costs (the lsap_warm_csr_ entries, DESIGN.md
+// §19), after lsap_csr_prep_kernel and warm_csr_prep_kernel: the two kernels
+// above with CsrLoader in place of GlobalLoaderF64 and CsrLoader::at in the
+// cost tail (the same chosen values in the same order), as lsap_csr_kernel and
+// lsap_csr_mw_kernel stand beside lsap_f64_kernel and lsap_f64_mw_kernel.
+// (One body for both sources, templated on the loader, was built and changed
+// the register allocation of all 28 dense warm_f64_ kernels; they are left as
+// they were.)  warm_f64_done reads what either prologue wrote.
+template <int K, typename S>
+__global__ __launch_bounds__(WAVE) void warm_csr_kernel(const int64_t *indptr, const S *data, const uint64_t *mask,
+                                                        const uint16_t *pre, int NR, int NC, const int32_t *shape,
+                                                        int32_t *col, double *cost, double *du, double *dv) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int b = blockIdx.x;
+  const int lane = threadIdx.x;
+  int nr, n;
+  if (warm_f64_done(shape, b, NR, NC, nr, n, du, cost)) return;
+  size_t off = 0;
+  double *u_l;
+  int16_t *c4r_l;
+  LSAP_F64_LDS(LDS_CARVE, nr)
+  for (int i = lane; i < nr; i += WAVE) {
+    u_l[i] = du[(size_t)b * NR + i];
+    c4r_l[i] = (int16_t)col[(size_t)b * NR + i];
+  }
+  __syncthreads();
+  int64_t steps = 0;
+  const int nw = (NC + 63) >> 6;
+  using CL = CsrLoader<1, K, S>;
+  WithDuals<CL, double> ld{
+      CL{indptr + (size_t)b * NR, data, mask + (size_t)b * NR * nw, pre + (size_t)b * NR * nw, nw}};
+  ld.dv = dv + (size_t)b * NC;
+  const int st = sap_solve<K, double, true, true>(nr, n, ld, u_l, c4r_l, steps);
+  __syncthreads();
+  duals_store_f64<WAVE>(du, dv, u_l, st, b, NR, NC, nr, n);
+  double acc = 0;
+  for (int i = lane; i < NR; i += WAVE) {
+    const bool live = st == 0 && i < nr;
+    const int cidx = live ? c4r_l[i] : -1;
+    col[(size_t)b * NR + i] = cidx;
+    if (live && cost) acc += ld.at(i, cidx);
+  }
+  if (cost) {  // (lsap_f64_kernel's order)
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, WAVE);
+    if (lane == 0) cost[b] = acc;
+  }
+}
+
+template <int NW, int K, typename S, int FB>
+__global__ __launch_bounds__(NW * WAVE) void warm_csr_mw_kernel(const int64_t *indptr, const S *data,
+                                                                const uint64_t *mask, const uint16_t *pre, int NR,
+                                                                int NC, const int32_t *shape, int32_t *col,
+                                                                double *cost, double *du, double *dv) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int WG = NW * WAVE;
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  int nr, n;
+  if (warm_f64_done(shape, b, NR, NC, nr, n, du, cost)) return;
+  size_t off = 0;
+  SolveLdsF64 Sl;
+  LSAP_F64_MW_LDS(LDS_CARVE, nr, n, NW, FB)
+  for (int i = tid; i < n; i += WG) {
+    if (i < nr) {
+      Sl.u[i] = du[(size_t)b * NR + i];
+      Sl.c4r[i] = (int16_t)col[(size_t)b * NR + i];
+    }
+    Sl.r4c[i] = -1;
+    Sl.path[i] = -1;
+  }
+  __syncthreads();
+  for (int i = tid; i < nr; i += WG) {
+    const int j = Sl.c4r[i];
+    if (j >= 0) Sl.r4c[j] = (int16_t)i;
+  }
+  __syncthreads();
+  const int nw = (NC + 63) >> 6;
+  using CL = CsrLoader<NW, K, S>;
+  WithDuals<CL, double> ld{
+      CL{indptr + (size_t)b * NR, data, mask + (size_t)b * NR * nw, pre + (size_t)b * NR * nw, nw}};
+  ld.dv = dv + (size_t)b * NC;
+  const int st = sap_solve_mw_f64<NW, K, true, FB, true>(nr, n, ld, Sl);
+  __syncthreads();
+  duals_store_f64<WG>(du, dv, Sl.u, st, b, NR, NC, nr, n);
+  for (int i = tid; i < NR; i += WG) col[(size_t)b * NR + i] = (st == 0 && i < nr) ? Sl.c4r[i] : -1;
+  if (cost && tid < WAVE) {
+    double acc = 0;
+    for (int i = tid; i < NR; i += WAVE)
+      if (st == 0 && i < nr) acc += ld.at(i, Sl.c4r[i]);
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, WAVE);
     if (tid == 0) cost[b] = acc;

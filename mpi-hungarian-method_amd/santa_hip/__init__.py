@@ -23,7 +23,8 @@ from ._lib import (SH_CERT_COL, SH_CERT_GAP, SH_CERT_NONE, SH_CERT_RANGE, SH_CER
 from .lsap import (check_duals, check_duals_large, check_duals_sparse, check_matching_sparse,  # noqa: F401
                    csr_transpose, densify, maximum_bipartite_matching, maximum_matching_sparse,
                    linear_sum_assignment, linear_sum_assignment_duals, linear_sum_assignment_large,
-                   linear_sum_assignment_resolve, linear_sum_assignment_sparse, resolve_batched,
+                   linear_sum_assignment_resolve, linear_sum_assignment_sparse,
+                   linear_sum_assignment_sparse_resolve, resolve_batched, resolve_batched_sparse,
                    solve_batched, solve_batched_large, solve_batched_sparse, solve_hash, validate_csr)
 from .lbap import check_bottleneck, linear_bottleneck_assignment, solve_bottleneck_batched  # noqa: F401
 
@@ -36,6 +37,7 @@ __all__ = [
     "linear_sum_assignment_large", "solve_batched_large", "check_duals_large",
     "linear_sum_assignment_resolve", "resolve_batched",
     "linear_sum_assignment_sparse", "solve_batched_sparse", "densify", "csr_transpose", "validate_csr",
+    "resolve_batched_sparse", "linear_sum_assignment_sparse_resolve",
     "check_duals_sparse", "maximum_matching_sparse", "check_matching_sparse", "maximum_bipartite_matching",
     "linear_bottleneck_assignment", "solve_bottleneck_batched", "check_bottleneck",
     "SH_CERT_COL", "SH_CERT_SLACK", "SH_CERT_TIGHT", "SH_CERT_SIGN", "SH_CERT_GAP", "SH_CERT_NONE",

@@ -163,6 +163,10 @@ SIGNATURES["lsap_csr_work_bytes"] = (ctypes.c_size_t, [_I, _I, _I])
 for _suf in ("f64", "f32"):
     SIGNATURES["lsap_solve_csr_" + _suf] = (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, ctypes.c_size_t,
                                                  _U, _P])
+    # the warm start on the CSR: indptr, indices, data, nr, nc, B, shape, col (in / out), cost, u, v (in / out),
+    # kept, work, work_bytes, flags, stream
+    SIGNATURES["lsap_warm_csr_" + _suf] = (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t,
+                                                _U, _P])
     # the certificate on the CSR: indptr, indices, data, nr, nc, B, shape, col, u, v, slack, flags out, stream
     SIGNATURES["lsap_check_duals_csr_" + _suf] = (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P])
     # the matching: indptr, indices, data, nr, nc, B, shape, match, card, wit, work, work_bytes, flags, stream

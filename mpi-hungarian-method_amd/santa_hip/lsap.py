@@ -27,6 +27,9 @@ maximum_matching_sparse, check_matching_sparse and maximum_bipartite_matching
 find and prove a maximum-cardinality matching of the sparsity pattern: a
 perfect matching of the rows, or a Hall violator where there is none (the
 lsap_check_duals_csr_, lsap_match_csr_ and lsap_check_hall_csr_ entries).
+resolve_batched_sparse and linear_sum_assignment_sparse_resolve are the warm
+start on the CSR (the lsap_warm_csr_ entries): resolve_batched on the
+densification, from a previous (col, v), without the dense matrix.
 """
 from __future__ import annotations
 
@@ -748,6 +751,99 @@ def linear_sum_assignment_sparse(A, maximize: bool = False, device: int | str = 
                                torch.from_numpy(np.ascontiguousarray(data)).to(dev), shape=(1, nr, nc),
                                with_cost=False, maximize=maximize, duals=duals)
     return single_result(out[0], tall, *out[2:])  # (the duals come back in the matrix's own signs)
+
+
+# ---------------------------------------------------------------------------
+# Warm start on the CSR (the lsap_warm_csr_ entries):
+# resolve_batched on the densification, without the dense matrix.
+# ---------------------------------------------------------------------------
+def resolve_batched_sparse(crow, col_indices, values, shape, col, u, v, with_cost: bool = True, flags: int = 0,
+                           shapes=None, maximize: bool = False, validate: bool = True):
+    """solve_batched_sparse(duals=True) started from a previous solution (col
+    [B, NR] of any integer dtype, u [B, NR], v [B, NC] float64) -> (col, cost,
+    u, v, kept int32 [B]): what resolve_batched returns for the densification
+    (densify) with the same shapes and the same previous col and v -- the same
+    col and kept, the same bits in cost, u and v equal by value (a zero may
+    carry the other sign) -- without building it.
+
+    The batch, `shapes`, `validate` and maximize are solve_batched_sparse's (the
+    triple with shape = (B, NR, NC), or one 2-D torch.sparse_csr tensor in place
+    of crow); the previous solution is resolve_batched's: read as data, not
+    modified, of any content, and of the two duals only v is read.  The pattern
+    may have changed as well as the values: a previous pair that is no longer
+    stored is dropped, a new entry is an edge.  An instance without a perfect
+    matching of its rows gets -1, cost 0 and NaN duals.  flags:
+    SH_FLAG_BUILD_ONLY returns the start state itself (the kept pairs, u, v,
+    kept; cost 0), as on resolve_batched."""
+    crow, col_indices, values, shape, p = _sparse_batch(crow, col_indices, values, shape, shapes, validate)
+    check_solution(p, values.dtype, col, u, v)
+    dev = values.device
+    if p.empty:
+        return empty_result(p, with_cost, True, p.ddt, dev) + (torch.zeros(p.B, dtype=torch.int32, device=dev),)
+    require_gpu()
+    crow, col_indices, values, shape_dev = _sparse_operands(p, crow, col_indices, values, maximize)
+    # the C entry works in place on col and v: it gets copies, and only u and the cost are new
+    col_w = narrow_col(col).clone().contiguous()
+    v_w = (-v if maximize else v.clone()).contiguous()
+    u_w = torch.empty((p.B, p.NR), dtype=torch.float64, device=dev)
+    build_only = bool(flags & _lib.SH_FLAG_BUILD_ONLY)
+    cost = (torch.zeros if build_only else torch.empty)(p.B, dtype=torch.float64, device=dev) if with_cost else None
+    kept = torch.empty(p.B, dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    nbytes = int(L.lsap_csr_work_bytes(p.NR, p.NC, p.B))
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    nnz = values.numel()
+    rc = getattr(L, "lsap_warm_csr_" + DTYPE_SUFFIX[values.dtype])(
+        _p(crow), _p(col_indices) if nnz else None, _p(values) if nnz else None, p.NR, p.NC, p.B, _p(shape_dev),
+        _p(col_w), _p(cost), _p(u_w), _p(v_w), _p(kept), _p(work), nbytes, _lib.SH_COMPAT_TIEBREAK | flags,
+        current_stream_handle(dev))
+    _lib.check(rc, "lsap_warm_csr")
+    if maximize:
+        cost = -cost if cost is not None else None
+        u_w, v_w = -u_w, -v_w
+    return col_w, cost, u_w, v_w, kept
+
+
+def linear_sum_assignment_sparse_resolve(A, col_ind, u, v, maximize: bool = False, device: int | str = 0):
+    """linear_sum_assignment_sparse(duals=True) started from a previous solution
+    of a nearby matrix -> (row_ind, col_ind, u, v).
+
+    A is linear_sum_assignment_sparse's; col_ind [nr], u [nr] and v [nc] are
+    linear_sum_assignment_resolve's, the duals float64 numpy arrays (TypeError
+    otherwise).  Tall input is solved as its transpose (csr_transpose) from the
+    inverse of col_ind and from u.  The result is optimal; on ties it need not
+    be scipy's permutation.  ValueError("cost matrix is infeasible") where no
+    full matching of the shorter side exists."""
+    indptr, indices, data, (nr, nc) = _csr_of(A)
+    col_ind, u, v = np.asarray(col_ind), np.asarray(u), np.asarray(v)
+    if col_ind.shape != (nr,) or u.shape != (nr,) or v.shape != (nc,):
+        raise ValueError(f"expected col_ind and u of shape ({nr},) and v of shape ({nc},)")
+    if not np.issubdtype(col_ind.dtype, np.integer):
+        raise TypeError(f"col_ind must be an integer array, got {col_ind.dtype}")
+    if nr == 0 or nc == 0:
+        return single_empty(nr, nc, True, np.float64)
+    if max(nr, nc) > _lib.SH_MAX_N_LARGE:
+        raise ValueError(f"max(nr, nc) = {max(nr, nc)} > {_lib.SH_MAX_N_LARGE}")
+    if u.dtype != np.float64 or v.dtype != np.float64:
+        raise TypeError(f"a sparse matrix is solved in float64: u and v must have that dtype, "
+                        f"got {u.dtype} and {v.dtype}")
+    if data.dtype not in (np.float64, np.float32):
+        data = data.astype(np.float64)
+    require_gpu()
+    dev = device_of(device)
+    col0 = torch.from_numpy(np.clip(col_ind.astype(np.int64), _INT32_MIN, _INT32_MAX).astype(np.int32))[None]
+    tall = nr > nc
+    v0 = torch.from_numpy(np.ascontiguousarray(u if tall else v))[None]
+    if tall:
+        indptr, indices, data, (nr, nc) = csr_transpose(indptr, indices, data, (nr, nc))
+        col0, bad = invert_col(col0, nr)
+        col0[bad] = -1
+    col, _, ru, rv, _ = resolve_batched_sparse(
+        torch.from_numpy(np.ascontiguousarray(indptr, dtype=np.int64)).to(dev),
+        torch.from_numpy(np.ascontiguousarray(indices, dtype=np.int32)).to(dev),
+        torch.from_numpy(np.ascontiguousarray(data)).to(dev), (1, nr, nc), col0.to(dev),
+        torch.zeros((1, nr), dtype=torch.float64, device=dev), v0.to(dev), with_cost=False, maximize=maximize)
+    return single_result(col, tall, ru, rv)  # (the duals come back in the matrix's own signs)
 
 
 def maximum_bipartite_matching(A, device: int | str = 0):
