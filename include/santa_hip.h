@@ -606,6 +606,72 @@ int lsap_warm_bf16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_
                    double *d_cost, double *d_u, double *d_v, int32_t *d_kept, unsigned flags, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * The k best assignments of every instance of a batch (Murty's partition in
+ * fixed row order), float64 and float32 costs solved in
+ * float64, 1 <= nr <= nc <= SH_MAX_N.
+ *
+ * A node of instance b is (col [nr], v [nc], p, F, cost): its optimal
+ * assignment, the column duals it ended with, the number of leading rows
+ * forced to col[0 .. p-1], the columns forbidden in row p as a bitmap of
+ * ceil(nc / 64) 64-bit words (bit j & 63 of word j >> 6), and the sum of its
+ * chosen costs.  The root is what lsap_solve_large_*(duals) returns, p = 0, F
+ * empty.  Child t of a node, p <= t < nr, is what lsap_warm_* computes from the
+ * node's (col, v) on the masked matrix M_t: row i < t is C[i][col[i]] at
+ * col[i] and +inf elsewhere; rows i >= t are +inf on col[0 .. t-1]; row t is
+ * also +inf on F_t = (F if t == p) + {col[t]}; the child's p is t and its F is
+ * F_t.  M_t is never written: the kernels read d_C through the masks.
+ *
+ * lsap_murty_children_*: expand one node per instance into its nr children.
+ *   d_pcol [B x nr], d_pv [B x nc], d_p [B], d_forb [B x ceil(nc / 64)]  in: the
+ *     node; d_p[b] < 0: instance b has no node.  Read as data, as lsap_warm_
+ *     reads its previous state: an entry of d_pcol outside [0, nc_b) names no
+ *     column and never forms an address -- a forced row with one has nothing
+ *     finite, so the child is infeasible, and row t's own column is then not
+ *     added to F_t.
+ *   d_col [B x nr x nr], d_cost [B x nr], d_u [B x nr x nr], d_v [B x nr x nc],
+ *   d_kept [B x nr] (nullable)  out: child t of instance b in slot b * nr + t,
+ *     each as lsap_warm_ writes an instance, with one difference: a child that
+ *     does not exist (no node, t < p, t >= nr_b, an empty or invalid shape: -1,
+ *     zero duals, kept 0) or is infeasible (-1, NaN duals in the live slots)
+ *     has cost +inf.
+ *
+ * lsap_kbest_*: rank r = 0 .. k-1 is, among the nodes not yet emitted, the one
+ * of least cost by value; on a tie the one created first (the root, then by
+ * round, then by t).  Its col goes to d_cols[b][r] and its cost to
+ * d_costs[b][r]; then (but for the last rank) it is expanded.  When no node is
+ * left the remaining ranks get -1 and +inf; d_count[b] is the number of ranks
+ * emitted (0 for an infeasible or empty instance).  The launches are the cold
+ * solve, then per rank one pop and one expansion: their number depends on k
+ * alone.  d_work holds the pool, lsap_kbest_work_bytes(nr, nc, B, k) bytes (0
+ * for arguments the entry rejects): col, v, F and cost of 1 + (k - 1) nr nodes
+ * per instance, in a layout private to the library.
+ *
+ * d_shape, the padding and the live shapes are lsap_warm_'s.  NaN and -inf
+ * costs are the caller's to reject.  flags: SH_FLAG_F64_MW / SH_FLAG_F64_SW
+ * choose the root's kernel on lsap_kbest_ (the same bits either way); no other
+ * flag is read.  The entries allocate nothing and never synchronise.
+ * SH_ERR_ARGS, checked on the host before any device call, for: nr < 1,
+ * nr > nc, nc > SH_MAX_N, B < 0, k < 1, B * nr or k * nr above 2^31 - 1; with
+ * B > 0 a null required pointer or work_bytes too small; d_work not 8-byte
+ * aligned.  B == 0 is a no-op after the checks.
+ * ------------------------------------------------------------------------ */
+int lsap_murty_children_f64(const double *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                            const int32_t *d_pcol, const double *d_pv, const int32_t *d_p, const uint64_t *d_forb,
+                            int32_t *d_col, double *d_cost, double *d_u, double *d_v, int32_t *d_kept,
+                            unsigned flags, void *stream);
+int lsap_murty_children_f32(const float *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                            const int32_t *d_pcol, const double *d_pv, const int32_t *d_p, const uint64_t *d_forb,
+                            int32_t *d_col, double *d_cost, double *d_u, double *d_v, int32_t *d_kept,
+                            unsigned flags, void *stream);
+size_t lsap_kbest_work_bytes(int nr, int nc, int B, int k);
+int lsap_kbest_f64(const double *d_C, int nr, int nc, int B, const int32_t *d_shape, int k, int32_t *d_cols,
+                   double *d_costs, int32_t *d_count, void *d_work, size_t work_bytes, unsigned flags,
+                   void *stream);
+int lsap_kbest_f32(const float *d_C, int nr, int nc, int B, const int32_t *d_shape, int k, int32_t *d_cols,
+                   double *d_costs, int32_t *d_count, void *d_work, size_t work_bytes, unsigned flags,
+                   void *stream);
+
+/* ---------------------------------------------------------------------------
  * The batched float solver on sparse (CSR) costs, a missing entry being a
  * forbidden pair: a sparse instance is solved exactly as the dense float
  * solver solves its densification, the nr x nc float64 matrix that holds each

@@ -1199,6 +1199,120 @@ int launch_warm(const S *C, int nr, int n, int B, const int32_t *shape, int32_t 
   return SH_OK;
 }
 
+// The lsap_murty_children_ entries and each expansion of lsap_kbest_: the two
+// launches of launch_warm over the B * nr children, murty_prep_kernel and then
+// the continuation by launch_warm's float table up to SH_MAX_N columns (the
+// same (NW, K, FB) and the same LDS lists; the prep's list has one byte a
+// column more).  The caller made the checks.  forb_out: where the pool keeps
+// each child's F_t, or null.
+static_assert(murty_prep_lds(SH_MAX_N, SH_MAX_N) <= LDS_NO_ATTR);
+
+template <typename S>
+int launch_murty(const S *C, int nr, int n, int B, const int32_t *shape, const int32_t *pcol, const double *pv,
+                 const int32_t *pp, const uint64_t *forb, int32_t *col, double *cost, double *du, double *dv,
+                 int32_t *kept, uint64_t *forb_out, hipStream_t s) {
+  const dim3 grid((unsigned)((size_t)B * nr));
+  hipLaunchKernelGGL((murty_prep_kernel<S>), grid, dim3(PREP_WG), murty_prep_lds(nr, n), s, C, nr, n, shape, pcol, pv,
+                     pp, forb, col, du, dv, kept, forb_out);
+  auto mw = [&](auto cfg) {
+    using C_ = decltype(cfg);
+    hipLaunchKernelGGL((murty_f64_mw_kernel<C_::NW, C_::K, S, C_::FB>), grid, dim3(C_::NW * WAVE),
+                       lsap_f64_mw_lds(nr, n, C_::NW, C_::FB), s, C, nr, n, shape, pcol, pp, forb, col, cost, du, dv);
+  };
+  if (n > 512) mw(BigCfg<4, 4, 10>{});
+  else if (n > 256) mw(BigCfg<4, 2, 10>{});
+  else if (n > WAVE) mw(BigCfg<4, 1, 10>{});
+  else
+    hipLaunchKernelGGL((murty_f64_kernel<1, S>), grid, dim3(WAVE), lsap_f64_lds(nr), s, C, nr, n, shape, pcol, pp,
+                       forb, col, cost, du, dv);
+  HIP_TRY(hipGetLastError());
+  return SH_OK;
+}
+
+int check_murty_sizes(int nr, int nc, int B) {
+  if (nr < 1 || nc > SH_MAX_N) return fail(SH_ERR_ARGS, "sizes must be in [1, 1024]");
+  if (nr > nc) return fail(SH_ERR_ARGS, "nr > nc: transpose tall input (as scipy does) and solve that");
+  if (B < 0) return fail(SH_ERR_ARGS, "B < 0");
+  if ((uint64_t)B * (uint64_t)nr > (uint64_t)INT32_MAX) return fail(SH_ERR_ARGS, "B * nr children exceed 2^31 - 1");
+  return SH_OK;
+}
+
+template <typename S>
+int murty_children(const S *C, int nr, int n, int B, const int32_t *shape, const int32_t *pcol, const double *pv,
+                   const int32_t *pp, const uint64_t *forb, int32_t *col, double *cost, double *du, double *dv,
+                   int32_t *kept, hipStream_t s) {
+  HIP_TRY_RC(check_murty_sizes(nr, n, B));
+  if (B > 0 && (!C || !pcol || !pv || !pp || !forb)) return fail(SH_ERR_ARGS, "null C, pcol, pv, p or forb");
+  if (B > 0 && (!col || !cost || !du || !dv)) return fail(SH_ERR_ARGS, "null col, cost, u or v");
+  if (B == 0) return SH_OK;
+  return launch_murty(C, nr, n, B, shape, pcol, pv, pp, forb, col, cost, du, dv, kept, (uint64_t *)nullptr, s);
+}
+
+// The pool of lsap_kbest_ (KbestPool) inside d_work: the 8-byte arrays, then
+// the int32 ones.  Returns the bytes, or 0 where they do not fit a size_t.
+size_t kbest_carve(unsigned char *base, int nr, int nc, int B, int k, KbestPool *P) {
+  const size_t W = (size_t)murty_words(nc), b = (size_t)B, r = (size_t)nr, c = (size_t)nc;
+  size_t rounds_nodes;  // (k - 1) * B * nr
+  if ((uint64_t)k * (uint64_t)nr > (uint64_t)INT32_MAX) return 0;  // (the pop counts slots in an int)
+  if (__builtin_mul_overflow((size_t)(k - 1), b * r, &rounds_nodes)) return 0;
+  const size_t per_node = 8 * (1 + c + W) + 4 * r;  // cost, v, F; col
+  size_t pool;
+  if (__builtin_mul_overflow(rounds_nodes, per_node, &pool)) return 0;
+  const size_t fixed = 8 * (b + b * c + b * r * r + b * c + b * W) + 4 * (b * r + b * r + b);
+  size_t total;
+  if (__builtin_add_overflow(pool, fixed, &total)) return 0;
+  if (P) {
+    size_t off = 0;
+    auto take = [&](auto *&ptr, size_t count) {
+      ptr = reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(base + off);
+      off += count * sizeof(*ptr);
+    };
+    take(P->root_cost, b);
+    take(P->root_v, b * c);
+    take(P->u, b * r * r);
+    take(P->cost, rounds_nodes);
+    take(P->v, rounds_nodes * c);
+    take(P->stage_v, b * c);
+    take(P->forb, rounds_nodes * W);
+    take(P->stage_forb, b * W);
+    take(P->root_col, b * r);
+    take(P->col, rounds_nodes * r);
+    take(P->stage_col, b * r);
+    take(P->stage_p, b);
+  }
+  return (total + 7) & ~(size_t)7;
+}
+
+// lsap_kbest_: the cold solve with duals into the root's slot, then for each
+// rank the pop and (but for the last) the expansion of what it popped into
+// round r's block: 1 + k + 2 (k - 1) launches, whatever the data.
+template <typename S>
+int kbest(const S *C, int nr, int n, int B, const int32_t *shape, int k, int32_t *cols, double *costs,
+          int32_t *count, void *work, size_t work_bytes, unsigned flags, hipStream_t s) {
+  HIP_TRY_RC(check_murty_sizes(nr, n, B));
+  if (k < 1) return fail(SH_ERR_ARGS, "k < 1");
+  if ((uint64_t)k * (uint64_t)nr > (uint64_t)INT32_MAX) return fail(SH_ERR_ARGS, "k * nr exceeds 2^31 - 1");
+  if (B > 0 && (!C || !cols || !costs || !count || !work)) return fail(SH_ERR_ARGS, "null C, cols, costs, count or work");
+  const size_t need = B > 0 ? kbest_carve(nullptr, nr, n, B, k, nullptr) : 0;
+  if (B > 0 && (need == 0 || work_bytes < need)) return fail(SH_ERR_ARGS, "work_bytes < lsap_kbest_work_bytes");
+  if ((uintptr_t)work % 8 != 0) return fail(SH_ERR_ARGS, "d_work must be 8-byte aligned");
+  HIP_TRY_RC(check_f64_flags(flags, n));
+  if (B == 0) return SH_OK;
+  KbestPool P;
+  kbest_carve((unsigned char *)work, nr, n, B, k, &P);
+  HIP_TRY_RC(solve_f64(C, nr, n, B, shape, P.root_col, P.root_cost, P.u, P.root_v, flags, s));
+  const size_t bn = (size_t)B * nr, W = (size_t)murty_words(n);
+  for (int r = 0; r < k; ++r) {
+    hipLaunchKernelGGL(kbest_pop_kernel, dim3(B), dim3(KBEST_POP_WG), 0, s, P, nr, n, B, r, k, cols, costs, count);
+    if (r == k - 1) break;
+    HIP_TRY_RC(launch_murty(C, nr, n, B, shape, P.stage_col, P.stage_v, P.stage_p, P.stage_forb,
+                            P.col + r * bn * nr, P.cost + r * bn, P.u, P.v + r * bn * n, (int32_t *)nullptr,
+                            P.forb + r * bn * W, s));
+  }
+  HIP_TRY(hipGetLastError());
+  return SH_OK;
+}
+
 // The certificate (lsap_cert_kernel, lsap_slack_kernel, lsap_cert_final_kernel):
 // S the stored cost type, T int64_t or double.  The pass over the corners
 // reads 16 bytes per load when every row starts 16-byte aligned; a batch too
@@ -1552,6 +1666,32 @@ SH_WARM_ENTRY(f32, float, float, double)
 SH_WARM_ENTRY(f16, uint16_t, _Float16, double)
 SH_WARM_ENTRY(bf16, uint16_t, sh_bf16, double)
 #undef SH_WARM_ENTRY
+
+// The k-best entries of a float cost type (murty_children, kbest).
+#define SH_KBEST_ENTRIES(SUF, CT)                                                                               \
+  int lsap_murty_children_##SUF(const CT *d_C, int nr, int nc, int B, const int32_t *d_shape,                   \
+                                const int32_t *d_pcol, const double *d_pv, const int32_t *d_p,                  \
+                                const uint64_t *d_forb, int32_t *d_col, double *d_cost, double *d_u,            \
+                                double *d_v, int32_t *d_kept, unsigned flags, void *stream) {                   \
+    (void)flags;                                                                                                \
+    return murty_children(d_C, nr, nc, B, d_shape, d_pcol, d_pv, d_p, d_forb, d_col, d_cost, d_u, d_v, d_kept,  \
+                          (hipStream_t)stream);                                                                 \
+  }                                                                                                             \
+  int lsap_kbest_##SUF(const CT *d_C, int nr, int nc, int B, const int32_t *d_shape, int k, int32_t *d_cols,    \
+                       double *d_costs, int32_t *d_count, void *d_work, size_t work_bytes, unsigned flags,      \
+                       void *stream) {                                                                          \
+    return kbest(d_C, nr, nc, B, d_shape, k, d_cols, d_costs, d_count, d_work, work_bytes, flags,               \
+                 (hipStream_t)stream);                                                                          \
+  }
+SH_KBEST_ENTRIES(f64, double)
+SH_KBEST_ENTRIES(f32, float)
+#undef SH_KBEST_ENTRIES
+
+size_t lsap_kbest_work_bytes(int nr, int nc, int B, int k) {
+  if (nr < 1 || nr > nc || nc > SH_MAX_N || B < 0 || k < 1 || (uint64_t)B * (uint64_t)nr > (uint64_t)INT32_MAX)
+    return 0;
+  return kbest_carve(nullptr, nr, nc, B, k, nullptr);
+}
 
 int lsap_solve_batched_rect_hash(uint64_t seed, int64_t modulus, int nr, int nc, int B,
                                  int32_t *d_col, int64_t *d_cost, unsigned flags, void *stream) {

@@ -7445,6 +7445,451 @@ __global__ __launch_bounds__(NW * WAVE) void warm_csr_mw_kernel(const int64_t *i
 }
 
 // ---------------------------------------------------------------------------
+// k-best assignments: Murty's partition in fixed row order (the
+// lsap_murty_children_ and lsap_kbest_ entries).
+//
+// A node of instance b is (pcol [nr], pv [n], p, F): its optimal assignment,
+// the column duals it ended with, the number of leading rows forced to
+// pcol[0 .. p-1], and the columns forbidden in row p (a bitmap of
+// murty_words(NC) 64-bit words).  Child t (p <= t < nr) is the warm start
+// (§16) from (pcol, pv) on the masked matrix M_t:
+//   row i < t   C[i][j] at j == pcol[i], +inf elsewhere
+//   row i >= t  +inf on the columns pcol[0 .. t-1]
+//   row t       also +inf on F_t = (F if t == p) + {pcol[t]}
+// M_t is never written: child c = b * NR + t reads instance b's C through the
+// masks.  Two launches, as launch_warm's, one workgroup per child:
+//   murty_prep_kernel   warm_prep_kernel's steps 1 to 7 on M_t, writing the
+//     child's slot of col / du / dv (and kept, and F_t where the pool wants it)
+//   murty_f64_kernel / murty_f64_mw_kernel   warm_f64_kernel's and
+//     warm_f64_mw_kernel's bodies behind MurtyLoader; the cost of a child that
+//     does not exist (no parent, t < p, t >= nr) or is infeasible is +inf.
+// pcol is read as data: an entry outside [0, n) names no column, so a forced
+// row with one has nothing finite (the child is infeasible) and row t's own
+// column is then not added to F_t.
+// ---------------------------------------------------------------------------
+__host__ __device__ constexpr int murty_words(int n) { return (n + 63) / 64; }
+
+// Whether child t of instance b exists, with b's live shape (block-uniform).
+__device__ __forceinline__ bool murty_child(const int32_t *shape, const int32_t *pp, int b, int t, int NR, int NC,
+                                            int &nr, int &n, int &p) {
+  p = __builtin_amdgcn_readfirstlane(pp[b]);
+  return lsap_shape(shape, b, NR, NC, nr, n) && p >= 0 && t >= p && t < nr;
+}
+
+// Column j < n is in F_t; ct is pcol[t], or -1 where that names no column.
+__device__ __forceinline__ bool murty_forbidden(const uint64_t *F_b, int p, int t, int ct, int j) {
+  return j == ct || (t == p && ((F_b[j >> 6] >> (j & 63)) & 1));
+}
+
+// GlobalLoaderF64 on M_t.  A thread keeps two K-bit masks of its own columns
+// (threadIdx.x + 64 NW k), made once at kernel entry from the parent's col:
+// `forced` (the column of a row < t) and `forb` (in F_t).  A step issues
+// GlobalLoaderF64's K loads and then selects +inf by the masks; a row i < t
+// (only reached when two forced rows share a column) keeps its own column,
+// read beside u[i] and not behind the costs.
+template <int NW, int K, typename S>
+struct MurtyLoader {
+  const S *base;
+  int n;   // live columns: j >= n is never read
+  int ld;  // row stride (elements)
+  const int32_t *pcol;  // the parent's col of this instance
+  int t;
+  uint32_t forced, forb;
+  __device__ __forceinline__ void masks(const uint64_t *F_b, int p) {
+    const int j0 = threadIdx.x;
+    forced = forb = 0;
+    for (int i = 0; i < t; ++i) {
+      const int c = pcol[i];
+#pragma unroll
+      for (int k = 0; k < K; ++k)
+        if (c == j0 + WAVE * NW * k) forced |= 1u << k;
+    }
+    int ct = pcol[t];
+    ct = (ct >= 0 && ct < n) ? ct : -1;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int j = j0 + WAVE * NW * k;
+      if (j < n && murty_forbidden(F_b, p, t, ct, j)) forb |= 1u << k;
+    }
+  }
+  __device__ __forceinline__ void load(int i, double (&c)[K]) const {
+    const S *row = base + (size_t)i * ld;
+    const int j0 = threadIdx.x;
+    if constexpr (std::is_same<S, double>::value) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        const int j = j0 + WAVE * NW * k;
+        c[k] = (j < n) ? row[j] : 0.0;
+      }
+    } else {  // (GlobalLoaderF64's note: all K loads, then the widening)
+      S raw[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) raw[k] = row[min(j0 + WAVE * NW * k, n - 1)];
+#pragma unroll
+      for (int k = 0; k < K; ++k) c[k] = (j0 + WAVE * NW * k < n) ? widen_f64(raw[k]) : 0.0;
+    }
+    uint32_t m = forced | (i == t ? forb : 0u);
+    if (i < t) {
+      const int f = pcol[i];
+      m = 0;
+#pragma unroll
+      for (int k = 0; k < K; ++k)
+        if (j0 + WAVE * NW * k != f) m |= 1u << k;
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+      if ((m >> k) & 1u) c[k] = __builtin_inf();
+  }
+};
+
+// msk_l[j]: bit 0 the column is forced by a row < t, bit 1 it is in F_t
+#define MURTY_PREP_LDS(X, nr, n) WARM_PREP_LDS(X, nr, n) X(msk_l, uint8_t, (size_t)n)
+__host__ __device__ constexpr size_t murty_prep_lds(int nr, int n) { return 0 MURTY_PREP_LDS(LDS_BYTES, nr, n); }
+
+// warm_prep_kernel on M_t (its steps and its comments; float costs only).  The
+// parent's (pcol, pv) of instance b are inputs, the state goes to child c's
+// slot.  A row i < t holds one finite entry, so step 4 reads that one.  The
+// lowest row that names a column holds its claim, so a column is forced
+// exactly when its claim is a row < t.
+template <typename S>
+__global__ __launch_bounds__(PREP_WG) void murty_prep_kernel(const S *C, int NR, int NC, const int32_t *shape,
+                                                             const int32_t *pcol, const double *pv,
+                                                             const int32_t *pp, const uint64_t *forb, int32_t *col,
+                                                             double *du, double *dv, int32_t *kept,
+                                                             uint64_t *forb_out) {
+  using T = double;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ int s_qt, s_bad, s_kept;
+  const int c = blockIdx.x, b = c / NR, t = c - b * NR;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int W = murty_words(NC);
+  int nr, n, p;
+  if (!murty_child(shape, pp, b, t, NR, NC, nr, n, p)) {
+    lsap_no_instance<PREP_WG>(col, (T *)nullptr, c, NR, NC, du, dv);
+    if (tid == 0 && kept) kept[c] = 0;
+    if (forb_out)
+      for (int x = tid; x < W; x += PREP_WG) forb_out[(size_t)c * W + x] = 0;
+    return;
+  }
+  size_t off = 0;
+  T *u_l;
+  int16_t *r4c_l, *c4r_l, *q_l;
+  uint8_t *msk_l;
+  MURTY_PREP_LDS(LDS_CARVE, nr, n)
+  int32_t *claim = (int32_t *)u_l;
+  const int32_t *pcol_b = pcol + (size_t)b * NR;
+  const double *pv_b = pv + (size_t)b * NC;
+  const uint64_t *F_b = forb + (size_t)b * W;
+  int32_t *col_c = col + (size_t)c * NR;
+  T *u_c = du + (size_t)c * NR, *v_c = dv + (size_t)c * NC;
+  const S *C_b = C + (size_t)b * NR * NC;
+  const bool wide = nr < n;
+  const T INF = VT<T>::inf();
+  int ct = pcol_b[t];
+  ct = (ct >= 0 && ct < n) ? ct : -1;
+  // M_t[i][j], j < n
+  auto at = [&](int i, int j) -> T {
+    const bool masked = (i < t) ? (j != pcol_b[i]) : (msk_l[j] & (i == t ? 3 : 1)) != 0;
+    return masked ? INF : cert_widen<T>(C_b[(size_t)i * NC + j]);
+  };
+  if (tid == 0) s_qt = s_bad = s_kept = 0;
+  for (int j = tid; j < n; j += PREP_WG) {  // 1
+    v_c[j] = warm_clean_v(pv_b[j]);
+    claim[j] = INT32_MAX;
+  }
+  __syncthreads();
+  for (int i = tid; i < nr; i += PREP_WG) {  // 2
+    const int j = pcol_b[i];
+    const bool ok = j >= 0 && j < n;
+    c4r_l[i] = ok ? (int16_t)j : (int16_t)-1;
+    if (ok) atomicMin(&claim[j], i);
+  }
+  __syncthreads();
+  for (int j = tid; j < n; j += PREP_WG) {  // 3
+    const int r = claim[j];
+    r4c_l[j] = (r == INT32_MAX) ? (int16_t)-1 : (int16_t)r;
+    if (wide && r == INT32_MAX) v_c[j] = 0;
+    msk_l[j] = (uint8_t)((r < t ? 1 : 0) | (murty_forbidden(F_b, p, t, ct, j) ? 2 : 0));
+  }
+  __syncthreads();  // (the claims are read: u_l may be written; v is final up to step 6)
+  for (int i = w; i < nr; i += PREP_WG / WAVE) {  // 4 and 5
+    const S *row = C_b + (size_t)i * NC;
+    T m = INF;
+    if (i < t) {
+      const int j = c4r_l[i];
+      if (lane == 0 && j >= 0) m = cert_sub(cert_widen<T>(row[j]), v_c[j]);
+    } else {
+      const int bits = (i == t) ? 3 : 1;
+#pragma unroll 4
+      for (int j = lane; j < n; j += WAVE) {
+        const T x = (msk_l[j] & bits) ? INF : cert_widen<T>(row[j]);
+        const T r = cert_sub(x, v_c[j]);
+        m = (r < m) ? r : m;
+      }
+    }
+    m = wave_min(m);
+    if (lane == 0) {
+      u_l[i] = m;
+      if (!(m < INF)) s_bad = 1;
+      const int j = c4r_l[i];
+      if (j >= 0) {
+        const bool mine = r4c_l[j] == i;  // (only row r4c_l[j] ever writes that slot)
+        const T vj = v_c[j];
+        if (!(mine && cert_sub(at(i, j), vj) == m)) {
+          c4r_l[i] = -1;
+          if (mine) {
+            r4c_l[j] = -1;
+            if (wide && vj < 0) q_l[atomicAdd(&s_qt, 1)] = (int16_t)j;
+          }
+        }
+      }
+    }
+  }
+  if (wide) {  // 6
+    for (int pop = 0; pop < n; ++pop) {
+      __syncthreads();  // the pushes and u of the pop before (or of step 5)
+      if (pop >= s_qt) break;  // (block-uniform: nobody pushes between this barrier and the next)
+      const int j = q_l[pop];
+      if (tid == 0) v_c[j] = 0;
+      for (int i = tid; i < nr; i += PREP_WG) {
+        const T x = at(i, j);
+        if (x < u_l[i]) {
+          u_l[i] = x;
+          const int jp = c4r_l[i];
+          if (jp >= 0) {
+            c4r_l[i] = -1;
+            r4c_l[jp] = -1;
+            if (v_c[jp] < 0) q_l[atomicAdd(&s_qt, 1)] = (int16_t)jp;
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const bool bad = s_bad;
+  int k = 0;
+  for (int i = tid; i < NR; i += PREP_WG) {
+    const int x = (i < nr && !bad) ? c4r_l[i] : -1;
+    col_c[i] = x;
+    k += x >= 0;
+    u_c[i] = (i < nr) ? (bad ? (T)__builtin_nan("") : u_l[i]) : (T)0;
+  }
+  for (int j = tid; j < NC; j += PREP_WG) {
+    if (j >= n) v_c[j] = 0;
+    else if (bad) v_c[j] = __builtin_nan("");
+  }
+  if (forb_out)
+    for (int x = tid; x < W; x += PREP_WG)
+      forb_out[(size_t)c * W + x] = (t == p ? F_b[x] : 0) | ((ct >= 0 && (ct >> 6) == x) ? 1ull << (ct & 63) : 0ull);
+  if (kept) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) k += __shfl_xor(k, o, WAVE);
+    if (lane == 0 && k) atomicAdd(&s_kept, k);
+    __syncthreads();
+    if (tid == 0) kept[c] = s_kept;
+  }
+}
+
+// A child the continuations have nothing to do for: it does not exist, or
+// murty_prep_kernel found it infeasible (warm_f64_done's test).  Its cost is
+// +inf.  Block-uniform.
+__device__ __forceinline__ bool murty_done(const int32_t *shape, const int32_t *pp, int b, int t, int c, int NR,
+                                           int NC, int &nr, int &n, int &p, const double *du, double *cost) {
+  bool done = !murty_child(shape, pp, b, t, NR, NC, nr, n, p);
+  if (!done) {
+    const double u0 = du[(size_t)c * NR];
+    done = u0 != u0;
+  }
+  if (done && threadIdx.x == 0) cost[c] = __builtin_inf();
+  return done;
+}
+
+// warm_f64_kernel on M_t: child c's state in col / du / dv, instance b's costs.
+template <int K, typename S>
+__global__ __launch_bounds__(WAVE) void murty_f64_kernel(const S *C, int NR, int NC, const int32_t *shape,
+                                                         const int32_t *pcol, const int32_t *pp,
+                                                         const uint64_t *forb, int32_t *col, double *cost,
+                                                         double *du, double *dv) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int c = blockIdx.x, b = c / NR, t = c - b * NR;
+  const int lane = threadIdx.x;
+  int nr, n, p;
+  if (murty_done(shape, pp, b, t, c, NR, NC, nr, n, p, du, cost)) return;
+  size_t off = 0;
+  double *u_l;
+  int16_t *c4r_l;
+  LSAP_F64_LDS(LDS_CARVE, nr)
+  for (int i = lane; i < nr; i += WAVE) {
+    u_l[i] = du[(size_t)c * NR + i];
+    c4r_l[i] = (int16_t)col[(size_t)c * NR + i];
+  }
+  __syncthreads();
+  int64_t steps = 0;
+  const size_t base = (size_t)b * NR * NC;
+  using ML = MurtyLoader<1, K, S>;
+  WithDuals<ML, double> ld{ML{C + base, n, NC, pcol + (size_t)b * NR, t, 0u, 0u}};
+  ld.masks(forb + (size_t)b * murty_words(NC), p);
+  ld.dv = dv + (size_t)c * NC;
+  const int st = sap_solve<K, double, true, true>(nr, n, ld, u_l, c4r_l, steps);
+  __syncthreads();
+  duals_store_f64<WAVE>(du, dv, u_l, st, c, NR, NC, nr, n);
+  double acc = 0;
+  for (int i = lane; i < NR; i += WAVE) {
+    const bool live = st == 0 && i < nr;
+    const int cidx = live ? c4r_l[i] : -1;
+    col[(size_t)c * NR + i] = cidx;
+    if (live) acc += widen_f64(C[base + (size_t)i * NC + cidx]);
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, WAVE);  // (warm_f64_kernel's order)
+  if (lane == 0) cost[c] = st == 0 ? acc : __builtin_inf();
+}
+
+// ... and warm_f64_mw_kernel on M_t.
+template <int NW, int K, typename S, int FB>
+__global__ __launch_bounds__(NW * WAVE) void murty_f64_mw_kernel(const S *C, int NR, int NC, const int32_t *shape,
+                                                                 const int32_t *pcol, const int32_t *pp,
+                                                                 const uint64_t *forb, int32_t *col, double *cost,
+                                                                 double *du, double *dv) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int WG = NW * WAVE;
+  const int c = blockIdx.x, b = c / NR, t = c - b * NR;
+  const int tid = threadIdx.x;
+  int nr, n, p;
+  if (murty_done(shape, pp, b, t, c, NR, NC, nr, n, p, du, cost)) return;
+  size_t off = 0;
+  SolveLdsF64 Sl;
+  LSAP_F64_MW_LDS(LDS_CARVE, nr, n, NW, FB)
+  for (int i = tid; i < n; i += WG) {
+    if (i < nr) {
+      Sl.u[i] = du[(size_t)c * NR + i];
+      Sl.c4r[i] = (int16_t)col[(size_t)c * NR + i];
+    }
+    Sl.r4c[i] = -1;
+    Sl.path[i] = -1;
+  }
+  __syncthreads();
+  for (int i = tid; i < nr; i += WG) {
+    const int j = Sl.c4r[i];
+    if (j >= 0) Sl.r4c[j] = (int16_t)i;
+  }
+  __syncthreads();
+  const size_t base = (size_t)b * NR * NC;
+  using ML = MurtyLoader<NW, K, S>;
+  WithDuals<ML, double> ld{ML{C + base, n, NC, pcol + (size_t)b * NR, t, 0u, 0u}};
+  ld.masks(forb + (size_t)b * murty_words(NC), p);
+  ld.dv = dv + (size_t)c * NC;
+  const int st = sap_solve_mw_f64<NW, K, true, FB, true>(nr, n, ld, Sl);
+  __syncthreads();
+  duals_store_f64<WG>(du, dv, Sl.u, st, c, NR, NC, nr, n);
+  for (int i = tid; i < NR; i += WG) col[(size_t)c * NR + i] = (st == 0 && i < nr) ? Sl.c4r[i] : -1;
+  if (tid < WAVE) {
+    double acc = 0;
+    for (int i = tid; i < NR; i += WAVE)
+      if (st == 0 && i < nr) acc += widen_f64(C[base + (size_t)i * NC + Sl.c4r[i]]);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, WAVE);
+    if (tid == 0) cost[c] = st == 0 ? acc : __builtin_inf();
+  }
+}
+
+// The pool of a k-best call (lsap_kbest_, inside d_work; private to the
+// library).  Slot 0 of an instance is its root; the children of the node
+// popped at rank r are slots 1 + r NR + t, stored by round: round r's block of
+// each array is laid out [B x NR x ...] as lsap_murty_children_ writes it, so
+// an expansion is that entry's two launches on the block.  A node's p is its
+// t (the root's 0); an emitted or absent node has cost +inf.
+struct KbestPool {
+  double *root_cost;    // [B]
+  double *root_v;       // [B x NC]
+  double *u;            // [B x NR x NR]  the row duals of the latest launch (nobody reads them)
+  double *cost;         // [k-1][B x NR]
+  double *v;            // [k-1][B x NR x NC]
+  double *stage_v;      // [B x NC]        the parent of the next expansion: v,
+  uint64_t *forb;       // [k-1][B x NR x W]
+  uint64_t *stage_forb; // [B x W]          F,
+  int32_t *root_col;    // [B x NR]
+  int32_t *col;         // [k-1][B x NR x NR]
+  int32_t *stage_col;   // [B x NR]         col
+  int32_t *stage_p;     // [B]              and p (-1: the instance is exhausted)
+};
+
+// Rank r of instance b: the live slot of least cost by value, the lowest slot
+// on a tie, among the 1 + r NR slots made so far.  Emits its col and cost,
+// marks it, and stages it as the parent of round r.  A root without an
+// assignment (infeasible, or no shape) is no node.
+constexpr int KBEST_POP_WG = 256;
+__global__ __launch_bounds__(KBEST_POP_WG) void kbest_pop_kernel(KbestPool P, int NR, int NC, int B, int r, int k,
+                                                                 int32_t *cols, double *costs, int32_t *count) {
+  __shared__ double s_c[KBEST_POP_WG / WAVE];
+  __shared__ int s_s[KBEST_POP_WG / WAVE];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int W = murty_words(NC);
+  const double INF = __builtin_inf();
+  const int nslots = 1 + r * NR;
+  double best = INF;
+  int bs = INT32_MAX;
+  for (int s = tid; s < nslots; s += KBEST_POP_WG) {
+    double x;
+    if (s == 0) {
+      x = (P.root_col[(size_t)b * NR] < 0) ? INF : P.root_cost[b];
+    } else {
+      const int rd = (s - 1) / NR, t = (s - 1) - rd * NR;
+      x = P.cost[((size_t)rd * B + b) * NR + t];
+    }
+    if (x < best) {  // (s ascends: the lowest slot keeps a tie)
+      best = x;
+      bs = s;
+    }
+  }
+  auto fold = [&](double ob, int os) {
+    if (ob < best || (ob == best && os < bs)) {
+      best = ob;
+      bs = os;
+    }
+  };
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const double ob = __shfl_xor(best, o, WAVE);
+    const int os = __shfl_xor(bs, o, WAVE);
+    fold(ob, os);
+  }
+  if ((tid & 63) == 0) {
+    s_c[tid >> 6] = best;
+    s_s[tid >> 6] = bs;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < KBEST_POP_WG / WAVE; ++q) fold(s_c[q], s_s[q]);
+  int32_t *out = cols + ((size_t)b * k + r) * NR;
+  if (!(best < INF)) {  // exhausted (block-uniform)
+    for (int i = tid; i < NR; i += KBEST_POP_WG) out[i] = -1;
+    if (tid == 0) {
+      costs[(size_t)b * k + r] = INF;
+      P.stage_p[b] = -1;
+      if (r == 0) count[b] = 0;
+    }
+    return;
+  }
+  const size_t node = bs == 0 ? 0 : ((size_t)((bs - 1) / NR) * B + b) * NR + (bs - 1) % NR;
+  const int32_t *col_n = bs == 0 ? P.root_col + (size_t)b * NR : P.col + node * NR;
+  const double *v_n = bs == 0 ? P.root_v + (size_t)b * NC : P.v + node * NC;
+  for (int i = tid; i < NR; i += KBEST_POP_WG) {
+    const int x = col_n[i];
+    out[i] = x;
+    P.stage_col[(size_t)b * NR + i] = x;
+  }
+  for (int j = tid; j < NC; j += KBEST_POP_WG) P.stage_v[(size_t)b * NC + j] = v_n[j];
+  for (int x = tid; x < W; x += KBEST_POP_WG) P.stage_forb[(size_t)b * W + x] = bs == 0 ? 0 : P.forb[node * W + x];
+  if (tid == 0) {
+    costs[(size_t)b * k + r] = best;
+    count[b] = r + 1;
+    P.stage_p[b] = bs == 0 ? 0 : (bs - 1) % NR;
+    *(bs == 0 ? P.root_cost + b : P.cost + node) = INF;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Batched linear bottleneck assignment (LBAP): the assignment whose LARGEST
 // chosen cost is as small as possible (Derigs-Zimmermann: the shortest
 // augmenting path loop with max in place of +).  One search per

@@ -30,6 +30,9 @@ lsap_check_duals_csr_, lsap_match_csr_ and lsap_check_hall_csr_ entries).
 resolve_batched_sparse and linear_sum_assignment_sparse_resolve are the warm
 start on the CSR (the lsap_warm_csr_ entries): resolve_batched on the
 densification, from a previous (col, v), without the dense matrix.
+kbest_batched and kbest_assignments return the k best assignments (Murty's
+partition on that warm start, pool and ranking on the device: the lsap_kbest_
+entries); murty_children_batched is one expansion (lsap_murty_children_).
 """
 from __future__ import annotations
 
@@ -39,8 +42,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._batch import (DTYPE_SUFFIX, _INT32_MAX, _INT32_MIN, _p, alloc_outputs, check_solution, device_of, empty_result,
-                     invert_col, minimised, narrow_col, plan, single_empty, single_result, tall_view, wide_view)
+from ._batch import (_COL_DTYPES, DTYPE_SUFFIX, _INT32_MAX, _INT32_MIN, _p, alloc_outputs, check_solution, device_of,
+                     empty_result, invert_col, minimised, narrow_col, plan, single_empty, single_result, tall_view,
+                     wide_view)
 from ._batch import check_shapes, invert_tall, tall_result  # noqa: F401  (re-exported: they lived here)
 from .context import current_stream_handle, require_gpu
 
@@ -408,6 +412,157 @@ def linear_sum_assignment_resolve(cost_matrix, col_ind, u, v, maximize: bool = F
     col, _, ru, rv, _ = resolve_batched(Ct.unsqueeze(0).to(dev), col0.to(dev), torch.zeros((1, m), dtype=v0.dtype, device=dev),
                                         v0.to(dev), with_cost=False)
     return single_result(col, tall, ru, rv, negate=maximize)
+
+
+# ---------------------------------------------------------------------------
+# The k best assignments (Murty's partition in fixed row order, DESIGN.md §20;
+# the lsap_murty_children_ and lsap_kbest_ entries).  Float costs only: a child
+# is its parent's matrix with +inf in places, and the integer solvers have no
+# forbidden value.
+# ---------------------------------------------------------------------------
+KBEST_DTYPES = (torch.float64, torch.float32)
+
+
+def _kbest_dtype(C):
+    if C.dtype not in KBEST_DTYPES:
+        raise TypeError(f"k-best assignments take float64 or float32 costs, got {C.dtype}: a subproblem forbids "
+                        "pairs with +inf, and the integer solvers have no forbidden value (convert with .double())")
+
+
+def forbidden_words(nc: int) -> int:
+    """The 64-bit words of a node's forbidden-column bitmap over nc columns."""
+    return (nc + 63) // 64
+
+
+def murty_children_batched(C: torch.Tensor, col: torch.Tensor, v: torch.Tensor, p: torch.Tensor,
+                           forb: torch.Tensor, shapes=None):
+    """Expand one Murty node per instance into its NR children (the
+    lsap_murty_children_ entries) -> (col int32 [B, NR, NR], cost float64
+    [B, NR], u [B, NR, NR], v [B, NR, NC], kept int32 [B, NR]).
+
+    C [B, NR, NC], NR <= NC <= SH_MAX_N, float64 or float32; the node of
+    instance b is col[b] (any integer dtype), v[b] (float64 [NC]), p[b] (integer;
+    negative: no node) and forb[b] (int64 [ceil(NC / 64)]: bit j & 63 of word
+    j >> 6 forbids column j in row p).  Child t, p <= t < nr_b, is what
+    resolve_batched computes from (col, v) on the matrix with rows < t fixed to
+    their columns, those columns closed to the rows below, and forb (if
+    t == p) and col[t] closed to row t; its slot is [b, t].  A child that does
+    not exist or is infeasible has col -1 and cost +inf.  The node is read as
+    data and not modified."""
+    _kbest_dtype(C)
+    p_ = plan(C.shape, C.dtype, _lib.SH_MAX_N, shapes)
+    if p_.tall:
+        raise ValueError(f"a Murty expansion takes a wide or square batch, got [{p_.NR}, {p_.NC}]")
+    B, NR, NC = p_.B, p_.NR, p_.NC
+    W = forbidden_words(NC)
+    if tuple(col.shape) != (B, NR) or tuple(v.shape) != (B, NC) or tuple(p.shape) != (B,) \
+            or tuple(forb.shape) != (B, W):
+        raise ValueError(f"expected col [{B}, {NR}], v [{B}, {NC}], p [{B}] and forb [{B}, {W}]")
+    if v.dtype != torch.float64:
+        raise TypeError(f"the duals of {C.dtype} costs are torch.float64")
+    if forb.dtype != torch.int64:
+        raise TypeError("forb holds its 64-bit words as torch.int64")
+    for name, x in (("col", col), ("p", p)):
+        if x.dtype not in _COL_DTYPES:
+            raise TypeError(f"{name} must be an integer tensor, got {x.dtype}")
+    dev = C.device
+    if p_.empty:
+        return (torch.full((B, NR, NR), -1, dtype=torch.int32, device=dev),
+                torch.full((B, NR), float("inf"), dtype=torch.float64, device=dev),
+                torch.zeros((B, NR, NR), dtype=torch.float64, device=dev),
+                torch.zeros((B, NR, NC), dtype=torch.float64, device=dev),
+                torch.zeros((B, NR), dtype=torch.int32, device=dev))
+    require_gpu()
+    C = C.contiguous()
+    col0, v0, p0, f0 = narrow_col(col).contiguous(), v.contiguous(), narrow_col(p).contiguous(), forb.contiguous()
+    ccol = torch.empty((B, NR, NR), dtype=torch.int32, device=dev)
+    cost = torch.empty((B, NR), dtype=torch.float64, device=dev)
+    cu = torch.empty((B, NR, NR), dtype=torch.float64, device=dev)
+    cv = torch.empty((B, NR, NC), dtype=torch.float64, device=dev)
+    kept = torch.empty((B, NR), dtype=torch.int32, device=dev)
+    shape_dev = p_.shapes_on(dev) if p_.shapes is not None else None
+    rc = getattr(_lib.lib(), "lsap_murty_children_" + DTYPE_SUFFIX[C.dtype])(
+        _p(C), NR, NC, B, _p(shape_dev), _p(col0), _p(v0), _p(p0), _p(f0), _p(ccol), _p(cost), _p(cu), _p(cv),
+        _p(kept), _lib.SH_COMPAT_TIEBREAK, current_stream_handle(dev))
+    _lib.check(rc, "lsap_murty_children")
+    return ccol, cost, cu, cv, kept
+
+
+def kbest_batched(C: torch.Tensor, k: int, shapes=None, maximize: bool = False):
+    """The k best assignments of every instance (the lsap_kbest_ entries) ->
+    (cols int32 [B, k, NR], costs float64 [B, k], count int32 [B]).
+
+    C [B, NR, NC] float64 or float32 (TypeError for any other dtype: the
+    integer solvers have no forbidden value), up to SH_MAX_N rows or columns;
+    shapes, maximize and tall batches as in resolve_batched.  Rank 0 is
+    solve_batched_large's assignment, bit for bit; costs[b] is non-decreasing
+    (non-increasing under maximize), the assignments of an instance are
+    distinct, and count[b] <= k of them exist: the ranks beyond have col -1 and
+    cost +inf (-inf under maximize).  cols[b, r, i] is the column of row i, -1
+    for the rows a tall instance leaves out.  One call launches 3 k - 1 kernels
+    whatever the data, allocates its pool once and never synchronises."""
+    _kbest_dtype(C)
+    if int(k) != k or k < 1:
+        raise ValueError(f"k must be an integer >= 1, got {k!r}")
+    k = int(k)
+    p = plan(C.shape, C.dtype, _lib.SH_MAX_N, shapes)
+    dev = C.device
+    if p.empty:
+        return (torch.full((p.B, k, p.NR), -1, dtype=torch.int32, device=dev),
+                torch.full((p.B, k), float("-inf") if maximize else float("inf"), dtype=torch.float64, device=dev),
+                torch.zeros(p.B, dtype=torch.int32, device=dev))
+    require_gpu()
+    if maximize:
+        C, = minimised(C)
+    if p.tall:
+        C, _, _ = wide_view(C)
+    C = C.contiguous()
+    L = _lib.lib()
+    nbytes = int(L.lsap_kbest_work_bytes(p.nr, p.nc, p.B, k))
+    if nbytes == 0:
+        raise ValueError(f"k = {k} is too large for a [{p.B}, {p.nr}, {p.nc}] batch")
+    work = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+    cols = torch.empty((p.B, k, p.nr), dtype=torch.int32, device=dev)
+    costs = torch.empty((p.B, k), dtype=torch.float64, device=dev)
+    count = torch.empty(p.B, dtype=torch.int32, device=dev)
+    shape_dev = p.shapes_on(dev) if p.shapes is not None else None
+    rc = getattr(L, "lsap_kbest_" + DTYPE_SUFFIX[C.dtype])(
+        _p(C), p.nr, p.nc, p.B, _p(shape_dev), k, _p(cols), _p(costs), _p(count), _p(work), nbytes,
+        _lib.SH_COMPAT_TIEBREAK, current_stream_handle(dev))
+    _lib.check(rc, "lsap_kbest")
+    if p.tall:
+        cols = invert_tall(cols.view(p.B * k, p.nr), p.NR).view(p.B, k, p.NR)
+    if maximize:
+        costs = -costs
+    return cols, costs, count
+
+
+def kbest_assignments(cost_matrix, k: int, maximize: bool = False, device: int | str = 0):
+    """The k best assignments of one matrix -> (col_inds int64 [m, nr], costs
+    float64 [m]), m <= k the number that exist, best first.  col_inds[r, i] is
+    the column of row i in the rank-r assignment, -1 for a row a tall matrix
+    leaves out.  The matrix is solved in float64 (float32 input at its own
+    width); +inf forbids a pair (under maximize: -inf), NaN and -inf (under
+    maximize: +inf) raise ValueError as in linear_sum_assignment."""
+    C = np.asarray(cost_matrix)
+    if C.ndim != 2:
+        raise ValueError("expected a matrix (2-D array), got a %r array" % (C.shape,))
+    if int(k) != k or k < 1:
+        raise ValueError(f"k must be an integer >= 1, got {k!r}")
+    nr, nc = C.shape
+    if nr == 0 or nc == 0:
+        return np.zeros((0, nr), dtype=np.int64), np.zeros(0, dtype=np.float64)
+    if max(nr, nc) > _lib.SH_MAX_N:
+        raise ValueError(f"max(nr, nc) = {max(nr, nc)} > {_lib.SH_MAX_N}")
+    if C.dtype != np.float32:
+        C = C.astype(np.float64)
+    bad = -np.inf if not maximize else np.inf
+    if np.isnan(C).any() or (C == bad).any():
+        raise ValueError("matrix contains invalid numeric entries")
+    Ct = torch.from_numpy(np.ascontiguousarray(C)).to(device_of(device))
+    cols, costs, count = kbest_batched(Ct.unsqueeze(0), k, maximize=maximize)
+    m = int(count[0])
+    return cols[0, :m].cpu().numpy().astype(np.int64), costs[0, :m].cpu().numpy()
 
 
 # ---------------------------------------------------------------------------
