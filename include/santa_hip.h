@@ -775,6 +775,65 @@ int lsap_warm_csr_f32(const int64_t *d_indptr, const int32_t *d_indices, const f
                       int32_t *d_kept, void *d_work, size_t work_bytes, unsigned flags, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * The k best assignments on sparse (CSR) costs:
+ * lsap_murty_children_ and lsap_kbest_ on the densification (the stored values,
+ * +inf elsewhere; a stored +inf counts as a missing entry), without densifying,
+ * float64 and float32 values, 1 <= nr <= nc <= SH_MAX_N.  The batch is
+ * lsap_solve_csr_'s: one CSR of B * nr rows, canonical rows, d_shape for ragged
+ * corners, and its memory-safety rule (an index outside [0, nc_b) never forms
+ * an address; reads of d_indices and d_data for row r stay inside
+ * [d_indptr[r], d_indptr[r + 1])).  The node, child t and the masked matrix M_t
+ * are lsap_murty_children_'s; M_t is never written: the kernels read the CSR
+ * through its presence words and the masks.
+ *
+ * lsap_murty_children_csr_*: what lsap_murty_children_* returns for the
+ *   densification with the same d_shape and the same node: d_col and d_kept the
+ *   same integers, d_cost the same bits, d_u and d_v equal by value (a zero may
+ *   carry the other sign, as on lsap_warm_csr_).  Child t is lsap_warm_csr_ on
+ *   the CSR of M_t.  A child that does not exist or is infeasible has -1 and
+ *   cost +inf.  The node is data, as there: a forced row whose d_pcol entry is
+ *   not stored makes the child infeasible.  d_work: lsap_csr_work_bytes(nr, nc,
+ *   B) bytes, 8-byte aligned.  Three launches: the pass over the CSR, the first
+ *   pass on M_t, the continuation chosen by nc alone.  flags is not read.
+ *
+ * lsap_kbest_csr_*: d_cols, d_costs and d_count of lsap_kbest_* on the
+ *   densification: the same integers, the same bits in d_costs, the same rank
+ *   order, tie rule (created first) and -1 / +inf tail.  Rank 0 is
+ *   lsap_solve_csr_'s solve with duals.  d_work: lsap_kbest_csr_work_bytes(nr,
+ *   nc, B, k) bytes -- lsap_kbest_work_bytes plus lsap_csr_work_bytes, rounded
+ *   up to 8; 0 for arguments the entry rejects -- 8-byte aligned.  The pass
+ *   over the CSR runs once and serves the root and every expansion; then the
+ *   root, then per rank one pop and one expansion: 3 k launches whatever the
+ *   data.  flags: SH_FLAG_F64_MW / SH_FLAG_F64_SW choose the root's kernel (the
+ *   same bits either way); no other flag is read.
+ *
+ * The entries allocate nothing and never synchronise.  SH_ERR_ARGS, checked on
+ * the host before any device call, for: nr < 1, nr > nc, nc > SH_MAX_N, B < 0,
+ * B * nr above 2^31 - 1; on lsap_kbest_csr_ also k < 1, k * nr above 2^31 - 1
+ * and SH_FLAG_F64_MW together with SH_FLAG_F64_SW; with B > 0 a null required
+ * pointer (d_indptr, the node's arrays, the outputs other than d_kept, d_work)
+ * or work_bytes too small; d_work not 8-byte aligned.  B == 0 is a no-op after
+ * the checks; d_indices and d_data may be null when there are no entries.
+ * ------------------------------------------------------------------------ */
+int lsap_murty_children_csr_f64(const int64_t *d_indptr, const int32_t *d_indices, const double *d_data, int nr,
+                                int nc, int B, const int32_t *d_shape, const int32_t *d_pcol, const double *d_pv,
+                                const int32_t *d_p, const uint64_t *d_forb, int32_t *d_col, double *d_cost,
+                                double *d_u, double *d_v, int32_t *d_kept, void *d_work, size_t work_bytes,
+                                unsigned flags, void *stream);
+int lsap_murty_children_csr_f32(const int64_t *d_indptr, const int32_t *d_indices, const float *d_data, int nr,
+                                int nc, int B, const int32_t *d_shape, const int32_t *d_pcol, const double *d_pv,
+                                const int32_t *d_p, const uint64_t *d_forb, int32_t *d_col, double *d_cost,
+                                double *d_u, double *d_v, int32_t *d_kept, void *d_work, size_t work_bytes,
+                                unsigned flags, void *stream);
+size_t lsap_kbest_csr_work_bytes(int nr, int nc, int B, int k);
+int lsap_kbest_csr_f64(const int64_t *d_indptr, const int32_t *d_indices, const double *d_data, int nr, int nc,
+                       int B, const int32_t *d_shape, int k, int32_t *d_cols, double *d_costs, int32_t *d_count,
+                       void *d_work, size_t work_bytes, unsigned flags, void *stream);
+int lsap_kbest_csr_f32(const int64_t *d_indptr, const int32_t *d_indices, const float *d_data, int nr, int nc,
+                       int B, const int32_t *d_shape, int k, int32_t *d_cols, double *d_costs, int32_t *d_count,
+                       void *d_work, size_t work_bytes, unsigned flags, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Certificates on the CSR itself: optimality of a sparse solve, and a proof
  * that a sparsity pattern has, or has not, a perfect matching of its rows.
  * Nothing is densified.  Batch layout, d_shape, sizes, canonical rows and the

@@ -1431,6 +1431,114 @@ int launch_warm_csr(const int64_t *indptr, const int32_t *indices, const S *data
 }
 
 // ---------------------------------------------------------------------------
+// k-best on the CSR (DESIGN.md §21): the lsap_murty_children_csr_ and
+// lsap_kbest_csr_ entries.  launch_mcsr is launch_murty behind the masking CSR
+// loader, after lsap_csr_prep_kernel: mcsr_prep_kernel and then the
+// continuation by the same table on the column count alone.  The caller made
+// the checks and ran the prep.
+// ---------------------------------------------------------------------------
+static_assert(mcsr_prep_lds(SH_MAX_N, SH_MAX_N) <= LDS_NO_ATTR);
+
+template <typename S>
+int launch_mcsr(const int64_t *indptr, const S *data, const uint64_t *mask, const uint16_t *pre, int nr, int n, int B,
+                const int32_t *shape, const int32_t *pcol, const double *pv, const int32_t *pp, const uint64_t *forb,
+                int32_t *col, double *cost, double *du, double *dv, int32_t *kept, uint64_t *forb_out,
+                hipStream_t s) {
+  const dim3 grid((unsigned)((size_t)B * nr));
+  hipLaunchKernelGGL((mcsr_prep_kernel<S>), grid, dim3(PREP_WG), mcsr_prep_lds(nr, n), s, indptr, data, mask, pre, nr,
+                     n, shape, pcol, pv, pp, forb, col, du, dv, kept, forb_out);
+  auto mw = [&](auto cfg) {
+    using C_ = decltype(cfg);
+    hipLaunchKernelGGL((mcsr_f64_mw_kernel<C_::NW, C_::K, S, C_::FB>), grid, dim3(C_::NW * WAVE),
+                       lsap_f64_mw_lds(nr, n, C_::NW, C_::FB), s, indptr, data, mask, pre, nr, n, shape, pcol, pp, forb,
+                       col, cost, du, dv);
+  };
+  if (n > 512) mw(BigCfg<4, 4, 10>{});
+  else if (n > 256) mw(BigCfg<4, 2, 10>{});
+  else if (n > WAVE) mw(BigCfg<4, 1, 10>{});
+  else
+    hipLaunchKernelGGL((mcsr_f64_kernel<1, S>), grid, dim3(WAVE), lsap_f64_lds(nr), s, indptr, data, mask, pre, nr, n,
+                       shape, pcol, pp, forb, col, cost, du, dv);
+  HIP_TRY(hipGetLastError());
+  return SH_OK;
+}
+
+// The bitmap pass of a batch whose sizes check_murty_sizes accepted (B * nr
+// rows fit an int, so the grid does).
+void launch_csr_prep(const int64_t *indptr, const int32_t *indices, int nr, int n, int B, const int32_t *shape,
+                     uint64_t *mask, uint16_t *pre, hipStream_t s) {
+  const int64_t rows = (int64_t)B * nr;
+  constexpr int PREP_ROWS = CSR_PREP_WG / WAVE;
+  hipLaunchKernelGGL(lsap_csr_prep_kernel, dim3((unsigned)((rows + PREP_ROWS - 1) / PREP_ROWS)), dim3(CSR_PREP_WG),
+                     0, s, indptr, indices, nr, n, rows, shape, mask, pre);
+}
+
+template <typename S>
+int murty_children_csr(const int64_t *indptr, const int32_t *indices, const S *data, int nr, int n, int B,
+                       const int32_t *shape, const int32_t *pcol, const double *pv, const int32_t *pp,
+                       const uint64_t *forb, int32_t *col, double *cost, double *du, double *dv, int32_t *kept,
+                       void *work, size_t work_bytes, hipStream_t s) {
+  HIP_TRY_RC(check_murty_sizes(nr, n, B));
+  if (B > 0 && (!indptr || !pcol || !pv || !pp || !forb)) return fail(SH_ERR_ARGS, "null indptr, pcol, pv, p or forb");
+  if (B > 0 && (!col || !cost || !du || !dv)) return fail(SH_ERR_ARGS, "null col, cost, u or v");
+  if (B > 0 && (!work || work_bytes < lsap_csr_work_bytes(nr, n, B)))
+    return fail(SH_ERR_ARGS, "work buffer smaller than lsap_csr_work_bytes");
+  if ((uintptr_t)work % 8) return fail(SH_ERR_ARGS, "work buffer not 8-byte aligned");
+  if (B == 0) return SH_OK;
+  uint64_t *mask = (uint64_t *)work;
+  uint16_t *pre = (uint16_t *)(mask + csr_words(nr, n, B));
+  launch_csr_prep(indptr, indices, nr, n, B, shape, mask, pre, s);
+  return launch_mcsr(indptr, data, mask, pre, nr, n, B, shape, pcol, pv, pp, forb, col, cost, du, dv, kept,
+                     (uint64_t *)nullptr, s);
+}
+
+// d_work of lsap_kbest_csr_: the dense pool (kbest_carve), then the words of
+// lsap_csr_prep_kernel.  Returns 0 where the pool does not fit a size_t.
+size_t kbest_csr_bytes(int nr, int nc, int B, int k, size_t *pool_bytes) {
+  const size_t pool = kbest_carve(nullptr, nr, nc, B, k, nullptr);  // (a multiple of 8)
+  size_t total;
+  if (B < 1 || pool == 0 || __builtin_add_overflow(pool, lsap_csr_work_bytes(nr, nc, B), &total)) return 0;
+  if (pool_bytes) *pool_bytes = pool;
+  return (total + 7) & ~(size_t)7;
+}
+
+// lsap_kbest_csr_: the bitmap pass and the cold CSR solve with duals into the
+// root's slot (launch_lsap_csr), then kbest's loop with launch_mcsr on the same
+// words: 2 + k + 2 (k - 1) = 3 k launches, whatever the data.
+template <typename S>
+int kbest_csr(const int64_t *indptr, const int32_t *indices, const S *data, int nr, int n, int B,
+              const int32_t *shape, int k, int32_t *cols, double *costs, int32_t *count, void *work,
+              size_t work_bytes, unsigned flags, hipStream_t s) {
+  HIP_TRY_RC(check_murty_sizes(nr, n, B));
+  if (k < 1) return fail(SH_ERR_ARGS, "k < 1");
+  if ((uint64_t)k * (uint64_t)nr > (uint64_t)INT32_MAX) return fail(SH_ERR_ARGS, "k * nr exceeds 2^31 - 1");
+  if (B > 0 && (!indptr || !cols || !costs || !count || !work))
+    return fail(SH_ERR_ARGS, "null indptr, cols, costs, count or work");
+  size_t pool = 0;
+  const size_t need = B > 0 ? kbest_csr_bytes(nr, n, B, k, &pool) : 0;
+  if (B > 0 && (need == 0 || work_bytes < need)) return fail(SH_ERR_ARGS, "work_bytes < lsap_kbest_csr_work_bytes");
+  if ((uintptr_t)work % 8 != 0) return fail(SH_ERR_ARGS, "d_work must be 8-byte aligned");
+  HIP_TRY_RC(check_f64_flags(flags, n));
+  if (B == 0) return SH_OK;
+  KbestPool P;
+  kbest_carve((unsigned char *)work, nr, n, B, k, &P);
+  uint64_t *mask = (uint64_t *)((unsigned char *)work + pool);
+  uint16_t *pre = (uint16_t *)(mask + csr_words(nr, n, B));
+  HIP_TRY_RC(launch_lsap_csr(indptr, indices, data, nr, n, B, shape, P.root_col, P.root_cost, P.u, P.root_v, mask,
+                             need - pool, flags & (SH_FLAG_F64_MW | SH_FLAG_F64_SW), s));
+  const size_t bn = (size_t)B * nr, W = (size_t)murty_words(n);
+  for (int r = 0; r < k; ++r) {
+    hipLaunchKernelGGL(kbest_pop_kernel, dim3(B), dim3(KBEST_POP_WG), 0, s, P, nr, n, B, r, k, cols, costs, count);
+    if (r == k - 1) break;
+    HIP_TRY_RC(launch_mcsr(indptr, data, mask, pre, nr, n, B, shape, P.stage_col, P.stage_v, P.stage_p, P.stage_forb,
+                           P.col + r * bn * nr, P.cost + r * bn, P.u, P.v + r * bn * n, (int32_t *)nullptr,
+                           P.forb + r * bn * W, s));
+  }
+  HIP_TRY(hipGetLastError());
+  return SH_OK;
+}
+
+// ---------------------------------------------------------------------------
 // The certificates on the CSR (DESIGN.md §18): lsap_check_duals_csr_
 // (csr_cert_kernel, csr_slack_kernel, lsap_cert_final_kernel), lsap_match_csr_
 // (csr_edges_kernel into d_work, then csr_match_kernel) and
@@ -1733,6 +1841,33 @@ int lsap_solve_csr_f32(const int64_t *d_indptr, const int32_t *d_indices, const 
 SH_WARM_CSR_ENTRY(f64, double)
 SH_WARM_CSR_ENTRY(f32, float)
 #undef SH_WARM_CSR_ENTRY
+
+// The k-best entries of a CSR value type (murty_children_csr, kbest_csr).
+#define SH_KBEST_CSR_ENTRIES(SUF, CT)                                                                             \
+  int lsap_murty_children_csr_##SUF(const int64_t *d_indptr, const int32_t *d_indices, const CT *d_data, int nr,  \
+                                    int nc, int B, const int32_t *d_shape, const int32_t *d_pcol,                 \
+                                    const double *d_pv, const int32_t *d_p, const uint64_t *d_forb,               \
+                                    int32_t *d_col, double *d_cost, double *d_u, double *d_v, int32_t *d_kept,    \
+                                    void *d_work, size_t work_bytes, unsigned flags, void *stream) {              \
+    (void)flags;                                                                                                  \
+    return murty_children_csr(d_indptr, d_indices, d_data, nr, nc, B, d_shape, d_pcol, d_pv, d_p, d_forb, d_col,  \
+                              d_cost, d_u, d_v, d_kept, d_work, work_bytes, (hipStream_t)stream);                 \
+  }                                                                                                               \
+  int lsap_kbest_csr_##SUF(const int64_t *d_indptr, const int32_t *d_indices, const CT *d_data, int nr, int nc,   \
+                           int B, const int32_t *d_shape, int k, int32_t *d_cols, double *d_costs,                \
+                           int32_t *d_count, void *d_work, size_t work_bytes, unsigned flags, void *stream) {     \
+    return kbest_csr(d_indptr, d_indices, d_data, nr, nc, B, d_shape, k, d_cols, d_costs, d_count, d_work,        \
+                     work_bytes, flags, (hipStream_t)stream);                                                     \
+  }
+SH_KBEST_CSR_ENTRIES(f64, double)
+SH_KBEST_CSR_ENTRIES(f32, float)
+#undef SH_KBEST_CSR_ENTRIES
+
+size_t lsap_kbest_csr_work_bytes(int nr, int nc, int B, int k) {
+  if (nr < 1 || nr > nc || nc > SH_MAX_N || B < 0 || k < 1 || (uint64_t)B * (uint64_t)nr > (uint64_t)INT32_MAX)
+    return 0;
+  return kbest_csr_bytes(nr, nc, B, k, nullptr);
+}
 
 // The certificates of a CSR value type (launch_csr_cert, launch_csr_match,
 // launch_csr_hall_check).  The matching takes no launch-forcing flag: it has

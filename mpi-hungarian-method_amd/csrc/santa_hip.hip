@@ -7890,6 +7890,353 @@ __global__ __launch_bounds__(KBEST_POP_WG) void kbest_pop_kernel(KbestPool P, in
 }
 
 // ---------------------------------------------------------------------------
+// k-best assignments on CSR costs (the lsap_murty_children_csr_ and
+// lsap_kbest_csr_ entries): the expansion above on the
+// densification (the stored values, +inf elsewhere), after
+// lsap_csr_prep_kernel.  The node, the pool and kbest_pop_kernel are the dense
+// ones; M_t is still never written: child c = b * NR + t reads instance b's
+// CSR through its presence words and the masks.
+//   mcsr_prep_kernel   warm_csr_prep_kernel's steps 1 to 7 on M_t
+//   mcsr_f64_kernel / mcsr_f64_mw_kernel   warm_csr_kernel's and
+//     warm_csr_mw_kernel's bodies behind MaskedCsrLoader, with murty_f64_kernel's
+//     rule for a child that does not exist or is infeasible (cost +inf).
+// Memory safety is CsrLoader's: a value's address comes from the unmasked
+// presence word and its prefix alone, the masks only select +inf afterwards,
+// and pcol is compared, never used as an index, outside the prologue's checked
+// claims.
+// ---------------------------------------------------------------------------
+
+// CsrLoader on M_t: MurtyLoader's two K-bit masks of the thread's own columns
+// (threadIdx.x + 64 NW k), made once at kernel entry.  A step issues
+// CsrLoader::load's two groups of loads unchanged -- rank and address from the
+// unmasked word, so no new dependent load -- and then takes +inf where the bit
+// is absent or the column is closed to row i.
+template <int NW, int K, typename S>
+struct MaskedCsrLoader : CsrLoader<NW, K, S> {
+  const int32_t *pcol;  // the parent's col of this instance
+  int t;
+  uint32_t forced, forb;
+  __device__ __forceinline__ void masks(const uint64_t *F_b, int p, int n) {
+    const int j0 = threadIdx.x;
+    forced = forb = 0;
+    for (int i = 0; i < t; ++i) {
+      const int c = pcol[i];
+#pragma unroll
+      for (int k = 0; k < K; ++k)
+        if (c == j0 + WAVE * NW * k) forced |= 1u << k;
+    }
+    int ct = pcol[t];
+    ct = (ct >= 0 && ct < n) ? ct : -1;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int j = j0 + WAVE * NW * k;
+      if (j < n && murty_forbidden(F_b, p, t, ct, j)) forb |= 1u << k;
+    }
+  }
+  __device__ __forceinline__ void load(int i, double (&c)[K]) const {
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const S *row = this->data + this->indptr[i];
+    const size_t r = (size_t)i * this->nw;
+    uint64_t m[K];
+    int p[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int q = min(w + NW * k, this->nw - 1);
+      m[k] = this->mask[r + q];
+      p[k] = this->pre[r + q];
+    }
+    const S *nothing = (const S *)(this->mask + r);
+    S raw[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      if (w + NW * k >= this->nw) m[k] = 0;
+      const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m[k] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m[k], 0u));
+      raw[k] = *(((m[k] >> lane) & 1) ? row + (p[k] + rank) : nothing);
+    }
+    uint32_t x = forced | (i == t ? forb : 0u);
+    if (i < t) {  // (only reached when two forced rows share a column)
+      const int f = pcol[i];
+      x = 0;
+#pragma unroll
+      for (int k = 0; k < K; ++k)
+        if ((int)threadIdx.x + WAVE * NW * k != f) x |= 1u << k;
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+      c[k] = (((m[k] >> lane) & 1) && !((x >> k) & 1u)) ? widen_f64(raw[k]) : VT<double>::inf();
+  }
+};
+
+// closed_l[q]: the columns of word q forced by a row < t; closedt_l[q]: those
+// and F_t.  The pattern of M_t is presence & ~closed_l in a row > t, presence &
+// ~closedt_l in row t, and the one entry (i, pcol[i]) in a row < t.
+#define MCSR_PREP_LDS(X, nr, n, nw) \
+  WARM_PREP_LDS(X, nr, n) X(closed_l, uint64_t, (size_t)nw * 8) X(closedt_l, uint64_t, (size_t)nw * 8)
+__host__ __device__ constexpr size_t mcsr_prep_lds(int nr, int n) {
+  return 0 MCSR_PREP_LDS(LDS_BYTES, nr, n, murty_words(n));
+}
+
+// warm_csr_prep_kernel on M_t (its steps and murty_prep_kernel's rules).  The
+// parent's (pcol, pv) of instance b are inputs, the state goes to child c's
+// slot.  Step 4 walks the words of presence & ~closed that hold an entry; a
+// row i < t reads its one entry through CsrLoader::at.
+template <typename S>
+__global__ __launch_bounds__(PREP_WG) void mcsr_prep_kernel(const int64_t *indptr, const S *data,
+                                                            const uint64_t *mask, const uint16_t *pre, int NR,
+                                                            int NC, const int32_t *shape, const int32_t *pcol,
+                                                            const double *pv, const int32_t *pp,
+                                                            const uint64_t *forb, int32_t *col, double *du,
+                                                            double *dv, int32_t *kept, uint64_t *forb_out) {
+  using T = double;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ int s_qt, s_bad, s_kept;
+  const int c = blockIdx.x, b = c / NR, t = c - b * NR;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int nw = murty_words(NC);
+  int nr, n, p;
+  if (!murty_child(shape, pp, b, t, NR, NC, nr, n, p)) {
+    lsap_no_instance<PREP_WG>(col, (T *)nullptr, c, NR, NC, du, dv);
+    if (tid == 0 && kept) kept[c] = 0;
+    if (forb_out)
+      for (int x = tid; x < nw; x += PREP_WG) forb_out[(size_t)c * nw + x] = 0;
+    return;
+  }
+  size_t off = 0;
+  T *u_l;
+  int16_t *r4c_l, *c4r_l, *q_l;
+  uint64_t *closed_l, *closedt_l;
+  MCSR_PREP_LDS(LDS_CARVE, nr, n, nw)
+  int32_t *claim = (int32_t *)u_l;
+  const int32_t *pcol_b = pcol + (size_t)b * NR;
+  const double *pv_b = pv + (size_t)b * NC;
+  const uint64_t *F_b = forb + (size_t)b * nw;
+  int32_t *col_c = col + (size_t)c * NR;
+  T *u_c = du + (size_t)c * NR, *v_c = dv + (size_t)c * NC;
+  const CsrLoader<1, 1, S> ld{indptr + (size_t)b * NR, data, mask + (size_t)b * NR * nw, pre + (size_t)b * NR * nw,
+                              nw};
+  const bool wide = nr < n;
+  const T INF = VT<T>::inf();
+  int ct = pcol_b[t];
+  ct = (ct >= 0 && ct < n) ? ct : -1;
+  // F_t's word x
+  auto ft = [&](int x) -> uint64_t {
+    return (t == p ? F_b[x] : 0) | ((ct >= 0 && (ct >> 6) == x) ? 1ull << (ct & 63) : 0ull);
+  };
+  // M_t[i][j], j < n
+  auto at = [&](int i, int j) -> T {
+    const bool masked = (i < t) ? (j != pcol_b[i]) : (((i == t ? closedt_l : closed_l)[j >> 6] >> (j & 63)) & 1) != 0;
+    return masked ? INF : ld.at(i, j);
+  };
+  if (tid == 0) s_qt = s_bad = s_kept = 0;
+  for (int j = tid; j < n; j += PREP_WG) {  // 1
+    v_c[j] = warm_clean_v(pv_b[j]);
+    claim[j] = INT32_MAX;
+  }
+  __syncthreads();
+  for (int i = tid; i < nr; i += PREP_WG) {  // 2
+    const int j = pcol_b[i];
+    const bool ok = j >= 0 && j < n;
+    c4r_l[i] = ok ? (int16_t)j : (int16_t)-1;
+    if (ok) atomicMin(&claim[j], i);
+  }
+  __syncthreads();
+  for (int j = tid; j < 64 * nw; j += PREP_WG) {  // 3 (a wave holds one word's columns)
+    const int r = (j < n) ? claim[j] : INT32_MAX;
+    if (j < n) {
+      r4c_l[j] = (r == INT32_MAX) ? (int16_t)-1 : (int16_t)r;
+      if (wide && r == INT32_MAX) v_c[j] = 0;
+    }
+    const uint64_t f = __ballot(r < t);
+    if (lane == 0) {
+      closed_l[j >> 6] = f;
+      closedt_l[j >> 6] = f | ft(j >> 6);
+    }
+  }
+  __syncthreads();  // (the claims are read: u_l may be written; v is final up to step 6)
+  for (int i = w; i < nr; i += PREP_WG / WAVE) {  // 4 and 5
+    T m = INF;
+    if (i < t) {
+      const int j = c4r_l[i];
+      if (lane == 0 && j >= 0) m = cert_sub(ld.at(i, j), v_c[j]);
+    } else {
+      const size_t r = (size_t)i * nw;
+      const S *row = ld.data + ld.indptr[i];
+      const int ql = min(lane, nw - 1);  // (a lane past the row's last word holds an empty one)
+      const uint64_t mw = (lane < nw) ? ld.mask[r + ql] : 0;
+      const int pw = ld.pre[r + ql];
+      const uint64_t ow = mw & ~(i == t ? closedt_l : closed_l)[ql];  // the open entries
+      uint64_t words = __ballot(ow != 0);  // the words that hold one
+      while (words) {
+        const int q = __builtin_ctzll(words);
+        words &= words - 1;
+        const uint64_t mq = readlane_u64(mw, q);
+        const uint64_t oq = readlane_u64(ow, q);
+        const int pq = __builtin_amdgcn_readlane(pw, q);
+        if ((oq >> lane) & 1) {  // (rank and address from the unmasked word)
+          const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mq >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mq, 0u));
+          const T x = cert_sub(widen_f64(row[pq + rank]), v_c[64 * q + lane]);
+          m = (x < m) ? x : m;
+        }
+      }
+    }
+    m = wave_min(m);
+    if (lane == 0) {
+      u_l[i] = m;
+      if (!(m < INF)) s_bad = 1;
+      const int j = c4r_l[i];
+      if (j >= 0) {
+        const bool mine = r4c_l[j] == i;  // (only row r4c_l[j] ever writes that slot)
+        const T vj = v_c[j];
+        if (!(mine && cert_sub(at(i, j), vj) == m)) {
+          c4r_l[i] = -1;
+          if (mine) {
+            r4c_l[j] = -1;
+            if (wide && vj < 0) q_l[atomicAdd(&s_qt, 1)] = (int16_t)j;
+          }
+        }
+      }
+    }
+  }
+  if (wide) {  // 6
+    for (int pop = 0; pop < n; ++pop) {
+      __syncthreads();  // the pushes and u of the pop before (or of step 5)
+      if (pop >= s_qt) break;  // (block-uniform: nobody pushes between this barrier and the next)
+      const int j = q_l[pop];
+      if (tid == 0) v_c[j] = 0;
+      for (int i = tid; i < nr; i += PREP_WG) {
+        const T x = at(i, j);
+        if (x < u_l[i]) {
+          u_l[i] = x;
+          const int jp = c4r_l[i];
+          if (jp >= 0) {
+            c4r_l[i] = -1;
+            r4c_l[jp] = -1;
+            if (v_c[jp] < 0) q_l[atomicAdd(&s_qt, 1)] = (int16_t)jp;
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const bool bad = s_bad;
+  int k = 0;
+  for (int i = tid; i < NR; i += PREP_WG) {
+    const int x = (i < nr && !bad) ? c4r_l[i] : -1;
+    col_c[i] = x;
+    k += x >= 0;
+    u_c[i] = (i < nr) ? (bad ? (T)__builtin_nan("") : u_l[i]) : (T)0;
+  }
+  for (int j = tid; j < NC; j += PREP_WG) {
+    if (j >= n) v_c[j] = 0;
+    else if (bad) v_c[j] = __builtin_nan("");
+  }
+  if (forb_out)
+    for (int x = tid; x < nw; x += PREP_WG) forb_out[(size_t)c * nw + x] = ft(x);
+  if (kept) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) k += __shfl_xor(k, o, WAVE);
+    if (lane == 0 && k) atomicAdd(&s_kept, k);
+    __syncthreads();
+    if (tid == 0) kept[c] = s_kept;
+  }
+}
+
+// warm_csr_kernel on M_t: child c's state in col / du / dv, instance b's CSR.
+template <int K, typename S>
+__global__ __launch_bounds__(WAVE) void mcsr_f64_kernel(const int64_t *indptr, const S *data, const uint64_t *mask,
+                                                        const uint16_t *pre, int NR, int NC, const int32_t *shape,
+                                                        const int32_t *pcol, const int32_t *pp,
+                                                        const uint64_t *forb, int32_t *col, double *cost,
+                                                        double *du, double *dv) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int c = blockIdx.x, b = c / NR, t = c - b * NR;
+  const int lane = threadIdx.x;
+  int nr, n, p;
+  if (murty_done(shape, pp, b, t, c, NR, NC, nr, n, p, du, cost)) return;
+  size_t off = 0;
+  double *u_l;
+  int16_t *c4r_l;
+  LSAP_F64_LDS(LDS_CARVE, nr)
+  for (int i = lane; i < nr; i += WAVE) {
+    u_l[i] = du[(size_t)c * NR + i];
+    c4r_l[i] = (int16_t)col[(size_t)c * NR + i];
+  }
+  __syncthreads();
+  int64_t steps = 0;
+  const int nw = murty_words(NC);
+  using ML = MaskedCsrLoader<1, K, S>;
+  WithDuals<ML, double> ld{ML{{indptr + (size_t)b * NR, data, mask + (size_t)b * NR * nw, pre + (size_t)b * NR * nw, nw},
+                              pcol + (size_t)b * NR, t, 0u, 0u}};
+  ld.masks(forb + (size_t)b * nw, p, n);
+  ld.dv = dv + (size_t)c * NC;
+  const int st = sap_solve<K, double, true, true>(nr, n, ld, u_l, c4r_l, steps);
+  __syncthreads();
+  duals_store_f64<WAVE>(du, dv, u_l, st, c, NR, NC, nr, n);
+  double acc = 0;
+  for (int i = lane; i < NR; i += WAVE) {
+    const bool live = st == 0 && i < nr;
+    const int cidx = live ? c4r_l[i] : -1;
+    col[(size_t)c * NR + i] = cidx;
+    if (live) acc += ld.at(i, cidx);  // (a chosen column is never masked: the CSR's own value)
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, WAVE);  // (warm_f64_kernel's order)
+  if (lane == 0) cost[c] = st == 0 ? acc : __builtin_inf();
+}
+
+// ... and warm_csr_mw_kernel on M_t.
+template <int NW, int K, typename S, int FB>
+__global__ __launch_bounds__(NW * WAVE) void mcsr_f64_mw_kernel(const int64_t *indptr, const S *data,
+                                                                const uint64_t *mask, const uint16_t *pre, int NR,
+                                                                int NC, const int32_t *shape, const int32_t *pcol,
+                                                                const int32_t *pp, const uint64_t *forb,
+                                                                int32_t *col, double *cost, double *du,
+                                                                double *dv) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int WG = NW * WAVE;
+  const int c = blockIdx.x, b = c / NR, t = c - b * NR;
+  const int tid = threadIdx.x;
+  int nr, n, p;
+  if (murty_done(shape, pp, b, t, c, NR, NC, nr, n, p, du, cost)) return;
+  size_t off = 0;
+  SolveLdsF64 Sl;
+  LSAP_F64_MW_LDS(LDS_CARVE, nr, n, NW, FB)
+  for (int i = tid; i < n; i += WG) {
+    if (i < nr) {
+      Sl.u[i] = du[(size_t)c * NR + i];
+      Sl.c4r[i] = (int16_t)col[(size_t)c * NR + i];
+    }
+    Sl.r4c[i] = -1;
+    Sl.path[i] = -1;
+  }
+  __syncthreads();
+  for (int i = tid; i < nr; i += WG) {
+    const int j = Sl.c4r[i];
+    if (j >= 0) Sl.r4c[j] = (int16_t)i;
+  }
+  __syncthreads();
+  const int nw = murty_words(NC);
+  using ML = MaskedCsrLoader<NW, K, S>;
+  WithDuals<ML, double> ld{ML{{indptr + (size_t)b * NR, data, mask + (size_t)b * NR * nw, pre + (size_t)b * NR * nw, nw},
+                              pcol + (size_t)b * NR, t, 0u, 0u}};
+  ld.masks(forb + (size_t)b * nw, p, n);
+  ld.dv = dv + (size_t)c * NC;
+  const int st = sap_solve_mw_f64<NW, K, true, FB, true>(nr, n, ld, Sl);
+  __syncthreads();
+  duals_store_f64<WG>(du, dv, Sl.u, st, c, NR, NC, nr, n);
+  for (int i = tid; i < NR; i += WG) col[(size_t)c * NR + i] = (st == 0 && i < nr) ? Sl.c4r[i] : -1;
+  if (tid < WAVE) {
+    double acc = 0;
+    for (int i = tid; i < NR; i += WAVE)
+      if (st == 0 && i < nr) acc += ld.at(i, Sl.c4r[i]);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, WAVE);
+    if (tid == 0) cost[c] = st == 0 ? acc : __builtin_inf();
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Batched linear bottleneck assignment (LBAP): the assignment whose LARGEST
 // chosen cost is as small as possible (Derigs-Zimmermann: the shortest
 // augmenting path loop with max in place of +).  One search per

@@ -26,6 +26,7 @@ from .lsap import (check_duals, check_duals_large, check_duals_sparse, check_mat
                    linear_sum_assignment_resolve, linear_sum_assignment_sparse,
                    linear_sum_assignment_sparse_resolve, resolve_batched, resolve_batched_sparse,
                    kbest_assignments, kbest_batched, murty_children_batched,
+                   kbest_assignments_sparse, kbest_batched_sparse, murty_children_batched_sparse,
                    solve_batched, solve_batched_large, solve_batched_sparse, solve_hash, validate_csr)
 from .lbap import check_bottleneck, linear_bottleneck_assignment, solve_bottleneck_batched  # noqa: F401
 
@@ -40,6 +41,7 @@ __all__ = [
     "linear_sum_assignment_sparse", "solve_batched_sparse", "densify", "csr_transpose", "validate_csr",
     "resolve_batched_sparse", "linear_sum_assignment_sparse_resolve",
     "kbest_assignments", "kbest_batched", "murty_children_batched",
+    "kbest_assignments_sparse", "kbest_batched_sparse", "murty_children_batched_sparse",
     "check_duals_sparse", "maximum_matching_sparse", "check_matching_sparse", "maximum_bipartite_matching",
     "linear_bottleneck_assignment", "solve_bottleneck_batched", "check_bottleneck",
     "SH_CERT_COL", "SH_CERT_SLACK", "SH_CERT_TIGHT", "SH_CERT_SIGN", "SH_CERT_GAP", "SH_CERT_NONE",

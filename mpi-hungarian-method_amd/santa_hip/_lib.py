@@ -177,7 +177,16 @@ for _suf in ("f64", "f32"):
     SIGNATURES["lsap_murty_children_" + _suf] = (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U, _P])
     # the k best: C, nr, nc, B, shape, k, cols, costs, count, work, work_bytes, flags, stream
     SIGNATURES["lsap_kbest_" + _suf] = (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P, _P, ctypes.c_size_t, _U, _P])
+    # Murty's expansion on the CSR: indptr, indices, data, nr, nc, B, shape, pcol, pv, p, forb, col, cost, u, v, kept,
+    # work, work_bytes, flags, stream
+    SIGNATURES["lsap_murty_children_csr_" + _suf] = (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                                          _P, _P, ctypes.c_size_t, _U, _P])
+    # the k best on the CSR: indptr, indices, data, nr, nc, B, shape, k, cols, costs, count, work, work_bytes, flags,
+    # stream
+    SIGNATURES["lsap_kbest_csr_" + _suf] = (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, ctypes.c_size_t, _U,
+                                                 _P])
 SIGNATURES["lsap_kbest_work_bytes"] = (ctypes.c_size_t, [_I, _I, _I, _I])
+SIGNATURES["lsap_kbest_csr_work_bytes"] = (ctypes.c_size_t, [_I, _I, _I, _I])
 
 
 class RoundExt(ctypes.Structure):

@@ -33,6 +33,9 @@ densification, from a previous (col, v), without the dense matrix.
 kbest_batched and kbest_assignments return the k best assignments (Murty's
 partition on that warm start, pool and ranking on the device: the lsap_kbest_
 entries); murty_children_batched is one expansion (lsap_murty_children_).
+kbest_batched_sparse, kbest_assignments_sparse and murty_children_batched_sparse
+are the same on the CSR (the lsap_kbest_csr_ and lsap_murty_children_csr_
+entries): kbest_batched on the densification, without the dense matrix.
 """
 from __future__ import annotations
 
@@ -659,11 +662,11 @@ def _csr_parts(crow, col_indices, values, shape):
     return crow, col_indices, values, tuple(int(s) for s in shape)
 
 
-def _sparse_batch(crow, col_indices, values, shape, shapes, validate, pattern=False):
+def _sparse_batch(crow, col_indices, values, shape, shapes, validate, pattern=False, limit=_lib.SH_MAX_N_LARGE):
     """The argument checks of a sparse batched call, in solve_batched_sparse's
     order -> (crow, col_indices, values, (B, NR, NC), its Batch); values
     float64 or float32.  pattern: values may be None (every stored entry counts),
-    and stays None."""
+    and stays None.  limit: the entry's largest NC."""
     crow, col_indices, values, shape = _csr_parts(crow, col_indices, values, shape)
     B, NR, NC = shape
     if B < 0 or NR < 0 or NC < 0:
@@ -682,7 +685,7 @@ def _sparse_batch(crow, col_indices, values, shape, shapes, validate, pattern=Fa
         raise TypeError(f"unsupported dtype {values.dtype}")
     if values.dtype not in (torch.float64, torch.float32):
         values = values.to(torch.float64)
-    p = plan(shape, values.dtype, _lib.SH_MAX_N_LARGE, shapes)
+    p = plan(shape, values.dtype, limit, shapes)
     if validate:
         validate_csr(crow, col_indices, values, shape, p.shapes)
     elif crow.numel() != B * NR + 1 or col_indices.numel() != values.numel():
@@ -999,6 +1002,151 @@ def linear_sum_assignment_sparse_resolve(A, col_ind, u, v, maximize: bool = Fals
         torch.from_numpy(np.ascontiguousarray(data)).to(dev), (1, nr, nc), col0.to(dev),
         torch.zeros((1, nr), dtype=torch.float64, device=dev), v0.to(dev), with_cost=False, maximize=maximize)
     return single_result(col, tall, ru, rv)  # (the duals come back in the matrix's own signs)
+
+
+# ---------------------------------------------------------------------------
+# The k best assignments on the CSR (the lsap_murty_children_csr_
+# and lsap_kbest_csr_ entries): kbest_batched on the densification, without the
+# dense matrix.
+# ---------------------------------------------------------------------------
+def murty_children_batched_sparse(crow, col_indices, values, shape, col, v, p, forb, shapes=None,
+                                  validate: bool = True):
+    """murty_children_batched on sparse costs (the lsap_murty_children_csr_
+    entries) -> (col int32 [B, NR, NR], cost float64 [B, NR], u [B, NR, NR],
+    v [B, NR, NC], kept int32 [B, NR]): what murty_children_batched returns for
+    the densification (densify) with the same shapes and the same node -- the
+    same col and kept, the same bits in cost, u and v equal by value (a zero may
+    carry the other sign) -- without building it.
+
+    The batch, `shapes` and `validate` are solve_batched_sparse's, with NR <= NC
+    <= SH_MAX_N; the node (col, v, p, forb) is murty_children_batched's: read as
+    data and not modified.  A forced row whose column is not stored makes the
+    child infeasible: col -1 and cost +inf, as for a child that does not
+    exist."""
+    crow, col_indices, values, shape, p_ = _sparse_batch(crow, col_indices, values, shape, shapes, validate,
+                                                         limit=_lib.SH_MAX_N)
+    B, NR, NC = shape
+    W = forbidden_words(NC)
+    if tuple(col.shape) != (B, NR) or tuple(v.shape) != (B, NC) or tuple(p.shape) != (B,) \
+            or tuple(forb.shape) != (B, W):
+        raise ValueError(f"expected col [{B}, {NR}], v [{B}, {NC}], p [{B}] and forb [{B}, {W}]")
+    if v.dtype != torch.float64:
+        raise TypeError(f"the duals of {values.dtype} costs are torch.float64")
+    if forb.dtype != torch.int64:
+        raise TypeError("forb holds its 64-bit words as torch.int64")
+    for name, x in (("col", col), ("p", p)):
+        if x.dtype not in _COL_DTYPES:
+            raise TypeError(f"{name} must be an integer tensor, got {x.dtype}")
+    dev = values.device
+    if p_.empty:
+        return (torch.full((B, NR, NR), -1, dtype=torch.int32, device=dev),
+                torch.full((B, NR), float("inf"), dtype=torch.float64, device=dev),
+                torch.zeros((B, NR, NR), dtype=torch.float64, device=dev),
+                torch.zeros((B, NR, NC), dtype=torch.float64, device=dev),
+                torch.zeros((B, NR), dtype=torch.int32, device=dev))
+    require_gpu()
+    crow, col_indices, values, shape_dev = _sparse_operands(p_, crow, col_indices, values, False)
+    col0, v0, p0, f0 = narrow_col(col).contiguous(), v.contiguous(), narrow_col(p).contiguous(), forb.contiguous()
+    ccol = torch.empty((B, NR, NR), dtype=torch.int32, device=dev)
+    cost = torch.empty((B, NR), dtype=torch.float64, device=dev)
+    cu = torch.empty((B, NR, NR), dtype=torch.float64, device=dev)
+    cv = torch.empty((B, NR, NC), dtype=torch.float64, device=dev)
+    kept = torch.empty((B, NR), dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    nbytes = int(L.lsap_csr_work_bytes(NR, NC, B))
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    nnz = values.numel()
+    rc = getattr(L, "lsap_murty_children_csr_" + DTYPE_SUFFIX[values.dtype])(
+        _p(crow), _p(col_indices) if nnz else None, _p(values) if nnz else None, NR, NC, B, _p(shape_dev), _p(col0),
+        _p(v0), _p(p0), _p(f0), _p(ccol), _p(cost), _p(cu), _p(cv), _p(kept), _p(work), nbytes,
+        _lib.SH_COMPAT_TIEBREAK, current_stream_handle(dev))
+    _lib.check(rc, "lsap_murty_children_csr")
+    return ccol, cost, cu, cv, kept
+
+
+def kbest_batched_sparse(crow, col_indices=None, values=None, shape=None, k: int = 1, shapes=None,
+                         maximize: bool = False, validate: bool = True):
+    """kbest_batched on sparse costs, a missing entry being a forbidden pair
+    (the lsap_kbest_csr_ entries) -> (cols int32 [B, k, NR], costs float64
+    [B, k], count int32 [B]): cols, costs and count of kbest_batched on the
+    densification (densify), the same integers and the same bits, in the same
+    rank order, without building it.  Rank 0 is solve_batched_sparse's
+    assignment.
+
+    The batch, `shapes`, maximize and `validate` are solve_batched_sparse's (the
+    triple with shape = (B, NR, NC), or one 2-D torch.sparse_csr tensor in place
+    of crow), with 1 <= NR <= NC <= SH_MAX_N: ValueError for a tall batch, for a
+    k that is no integer >= 1 and for a pool that does not fit.  One call
+    launches 3 k kernels whatever the data, allocates its pool once and never
+    synchronises."""
+    crow, col_indices, values, shape, p = _sparse_batch(crow, col_indices, values, shape, shapes, validate,
+                                                        limit=_lib.SH_MAX_N)
+    if int(k) != k or k < 1:
+        raise ValueError(f"k must be an integer >= 1, got {k!r}")
+    k = int(k)
+    B, NR, NC = shape
+    dev = values.device
+    if p.empty:
+        return (torch.full((B, k, NR), -1, dtype=torch.int32, device=dev),
+                torch.full((B, k), float("-inf") if maximize else float("inf"), dtype=torch.float64, device=dev),
+                torch.zeros(B, dtype=torch.int32, device=dev))
+    require_gpu()
+    crow, col_indices, values, shape_dev = _sparse_operands(p, crow, col_indices, values, maximize)
+    L = _lib.lib()
+    nbytes = int(L.lsap_kbest_csr_work_bytes(NR, NC, B, k))
+    if nbytes == 0:
+        raise ValueError(f"k = {k} is too large for a [{B}, {NR}, {NC}] batch")
+    work = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+    cols = torch.empty((B, k, NR), dtype=torch.int32, device=dev)
+    costs = torch.empty((B, k), dtype=torch.float64, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    nnz = values.numel()
+    rc = getattr(L, "lsap_kbest_csr_" + DTYPE_SUFFIX[values.dtype])(
+        _p(crow), _p(col_indices) if nnz else None, _p(values) if nnz else None, NR, NC, B, _p(shape_dev), k,
+        _p(cols), _p(costs), _p(count), _p(work), nbytes, _lib.SH_COMPAT_TIEBREAK, current_stream_handle(dev))
+    _lib.check(rc, "lsap_kbest_csr")
+    if maximize:
+        costs = -costs
+    return cols, costs, count
+
+
+def kbest_assignments_sparse(A, k: int, maximize: bool = False, device: int | str = 0):
+    """kbest_assignments for one sparse matrix whose missing entries are
+    forbidden pairs -> (col_inds int64 [m, nr], costs float64 [m]), m <= k the
+    number of assignments that exist, best first: those of kbest_assignments on
+    densify(A).  A is linear_sum_assignment_sparse's, up to SH_MAX_N on the
+    longer side; a tall matrix is solved as its transpose (csr_transpose) and
+    col_inds has -1 for the rows left out.  A stored +inf (under maximize:
+    -inf) is a missing entry; NaN and -inf (under maximize: +inf) raise
+    ValueError."""
+    indptr, indices, data, (nr, nc) = _csr_of(A)
+    if int(k) != k or k < 1:
+        raise ValueError(f"k must be an integer >= 1, got {k!r}")
+    if nr == 0 or nc == 0:
+        return np.zeros((0, nr), dtype=np.int64), np.zeros(0, dtype=np.float64)
+    if max(nr, nc) > _lib.SH_MAX_N:
+        raise ValueError(f"max(nr, nc) = {max(nr, nc)} > {_lib.SH_MAX_N}")
+    if data.dtype not in (np.float64, np.float32):
+        data = data.astype(np.float64)
+    if np.isnan(data).any() or (data == (np.inf if maximize else -np.inf)).any():
+        raise ValueError("matrix contains invalid numeric entries")
+    NR = nr
+    tall = nr > nc
+    if tall:
+        indptr, indices, data, (nr, nc) = csr_transpose(indptr, indices, data, (nr, nc))
+    dev = device_of(device)
+    if maximize:  # (negated here, so that the validation meets the forbidden value as +inf)
+        data = -data
+    cols, costs, count = kbest_batched_sparse(
+        torch.from_numpy(np.ascontiguousarray(indptr, dtype=np.int64)).to(dev),
+        torch.from_numpy(np.ascontiguousarray(indices, dtype=np.int32)).to(dev),
+        torch.from_numpy(np.ascontiguousarray(data)).to(dev), shape=(1, nr, nc), k=int(k))
+    if maximize:
+        costs = -costs
+    if tall:
+        cols = invert_tall(cols.view(int(k), nr), NR).view(1, int(k), NR)
+    m = int(count[0])
+    return cols[0, :m].cpu().numpy().astype(np.int64), costs[0, :m].cpu().numpy()
 
 
 def maximum_bipartite_matching(A, device: int | str = 0):
