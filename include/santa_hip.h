@@ -606,6 +606,70 @@ int lsap_warm_bf16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_
                    double *d_cost, double *d_u, double *d_v, int32_t *d_kept, unsigned flags, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Warm start with free rows: lsap_warm_* for wide instances,
+ * nr < nc.  Instance b is solved as the PADDED problem: the square nc_b x nc_b
+ * matrix whose rows nr_b .. nc_b - 1 cost 0 in every column.  It has the same
+ * optimal assignments of the real rows and the same optimum; those rows are
+ * never stored or read.  A square state needs no raising of column duals, so a
+ * previous pair that is no longer tight costs one Dijkstra and breaks no other
+ * pair (lsap_warm_* on a wide instance raises the dual of every free and
+ * broken column to 0, which can run through the whole instance).
+ *
+ * Arguments as lsap_warm_*, except
+ *   d_kept  [B x 2]  out, nullable: the previous pairs of real rows that were
+ *                    kept, and the pairs of virtual rows the start state holds;
+ *                    (nr_b - kept[2b]) + (nc_b - nr_b - kept[2b + 1])
+ *                    Dijkstras run
+ *   d_theta [B]      out, nullable, of the duals' type: the largest column dual
+ *                    of the padded problem's final state.  The virtual rows'
+ *                    duals are all -theta and the columns no real row holds end
+ *                    with v == theta (exactly so in integers).
+ *
+ * The start state: lsap_warm_*'s first launch without the raising (its square
+ * path, whatever nr); then, with theta = max_j v[j], the columns that are free
+ * and have v == theta go, ascending, to the virtual rows nr_b, nr_b + 1, ...
+ * while both last, and every virtual row gets u = -theta.  This is the state
+ * lsap_warm_* makes of the written-out padded matrix when d_col is extended by
+ * those columns.
+ *
+ * Duals.  Integer costs (i64, i32), nr_b < nc_b: d_u and d_v receive the
+ * normalised duals u + theta and v - theta.  The shift is exact, the result
+ * has the signs and equalities lsap_check_duals_large_* tests on the unpadded
+ * matrix (v <= 0, v == 0 on every free column), and it can be fed back to this
+ * entry or to lsap_warm_* as it is.  Float costs: d_u and d_v receive the
+ * padded problem's duals as the solver left them, bit for bit (a shift would
+ * round); v <= 0 still holds, a free column has v == theta up to rounding and
+ * not 0, so they are the input of this entry's next call, not of lsap_warm_*.
+ * nr_b == nc_b: the instance is lsap_warm_*'s, duals included, and theta is
+ * still reported.
+ *
+ * Padding, empty and invalid shapes and infeasible float instances as
+ * lsap_warm_* (theta 0, and NaN where the duals are NaN).  flags as
+ * lsap_warm_*; SH_FLAG_BUILD_ONLY leaves the start state: the kept real pairs,
+ * u of the real rows, v, both counts and the start state's theta, no shift
+ * applied.  The same SH_ERR_ARGS cases, checked on the host before any device
+ * call; nothing is allocated and nothing synchronises.
+ * ------------------------------------------------------------------------ */
+int lsap_warm_fr_i64(const int64_t *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,
+                     int64_t *d_cost, int64_t *d_u, int64_t *d_v, int32_t *d_kept, int64_t *d_theta,
+                     unsigned flags, void *stream);
+int lsap_warm_fr_i32(const int32_t *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,
+                     int64_t *d_cost, int64_t *d_u, int64_t *d_v, int32_t *d_kept, int64_t *d_theta,
+                     unsigned flags, void *stream);
+int lsap_warm_fr_f64(const double *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,
+                     double *d_cost, double *d_u, double *d_v, int32_t *d_kept, double *d_theta,
+                     unsigned flags, void *stream);
+int lsap_warm_fr_f32(const float *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,
+                     double *d_cost, double *d_u, double *d_v, int32_t *d_kept, double *d_theta,
+                     unsigned flags, void *stream);
+int lsap_warm_fr_f16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,
+                     double *d_cost, double *d_u, double *d_v, int32_t *d_kept, double *d_theta,
+                     unsigned flags, void *stream);
+int lsap_warm_fr_bf16(const uint16_t *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,
+                      double *d_cost, double *d_u, double *d_v, int32_t *d_kept, double *d_theta,
+                      unsigned flags, void *stream);
+
+/* ---------------------------------------------------------------------------
  * The k best assignments of every instance of a batch (Murty's partition in
  * fixed row order), float64 and float32 costs solved in
  * float64, 1 <= nr <= nc <= SH_MAX_N.
@@ -670,6 +734,40 @@ int lsap_kbest_f64(const double *d_C, int nr, int nc, int B, const int32_t *d_sh
 int lsap_kbest_f32(const float *d_C, int nr, int nc, int B, const int32_t *d_shape, int k, int32_t *d_cols,
                    double *d_costs, int32_t *d_count, void *d_work, size_t work_bytes, unsigned flags,
                    void *stream);
+
+/* ---------------------------------------------------------------------------
+ * The k best assignments with free rows: the entries above
+ * with every child computed by lsap_warm_fr_* in place of lsap_warm_*.  Child
+ * t is the warm start of the PADDED M_t: M_t and, as rows nr_b .. nc_b - 1,
+ * virtual rows that cost 0 everywhere but +inf on col[0 .. t-1], as every row
+ * below t.  It has M_t's optimum, and on a wide instance a child runs one
+ * Dijkstra where lsap_murty_children_* raises column duals and runs many.
+ *
+ * Arguments, outputs, d_work (lsap_kbest_work_bytes), flags and errors are the
+ * entries' above.  A node is still (col [nr], v [nc], p, F, cost): the virtual
+ * rows' pairs are not stored but recomputed from (col, v) by lsap_warm_fr_*'s
+ * rule, with theta the largest v over the columns no row < t forces.  d_v of a
+ * child holds the padded problem's column duals as the solver left them (no
+ * shift; a free column has v == theta up to rounding, not 0), d_u the real
+ * rows', d_kept the real pairs kept, d_cost the sum over the real rows.  The
+ * ranks of lsap_kbest_fr_* have the costs of lsap_kbest_*'s (equal bits
+ * wherever every sum is exact); among assignments of equal cost the order and
+ * the choice may differ.
+ * ------------------------------------------------------------------------ */
+int lsap_murty_children_fr_f64(const double *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                               const int32_t *d_pcol, const double *d_pv, const int32_t *d_p,
+                               const uint64_t *d_forb, int32_t *d_col, double *d_cost, double *d_u, double *d_v,
+                               int32_t *d_kept, unsigned flags, void *stream);
+int lsap_murty_children_fr_f32(const float *d_C, int nr, int nc, int B, const int32_t *d_shape,
+                               const int32_t *d_pcol, const double *d_pv, const int32_t *d_p,
+                               const uint64_t *d_forb, int32_t *d_col, double *d_cost, double *d_u, double *d_v,
+                               int32_t *d_kept, unsigned flags, void *stream);
+int lsap_kbest_fr_f64(const double *d_C, int nr, int nc, int B, const int32_t *d_shape, int k, int32_t *d_cols,
+                      double *d_costs, int32_t *d_count, void *d_work, size_t work_bytes, unsigned flags,
+                      void *stream);
+int lsap_kbest_fr_f32(const float *d_C, int nr, int nc, int B, const int32_t *d_shape, int k, int32_t *d_cols,
+                      double *d_costs, int32_t *d_count, void *d_work, size_t work_bytes, unsigned flags,
+                      void *stream);
 
 /* ---------------------------------------------------------------------------
  * The batched float solver on sparse (CSR) costs, a missing entry being a

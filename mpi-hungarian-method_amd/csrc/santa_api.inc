@@ -1199,6 +1199,53 @@ int launch_warm(const S *C, int nr, int n, int B, const int32_t *shape, int32_t 
   return SH_OK;
 }
 
+// The lsap_warm_fr_ entries: launch_warm's checks, its two launches and its
+// table, with frow_prep_kernel and the frow_ continuations.  The continuations
+// hold the padded problem's n rows: their LDS is the square footprint (plus 12
+// static bytes a wave).
+static_assert(lsap_i64_lds(SH_MAX_N_LARGE, SH_MAX_N_LARGE, 16, 12) + 16 * 12 <= LDS_NO_ATTR);
+static_assert(lsap_f64_mw_lds(SH_MAX_N_LARGE, SH_MAX_N_LARGE, 8, 12) + 8 * 12 <= LDS_NO_ATTR);
+
+template <typename S, typename T>
+int launch_warm_fr(const S *C, int nr, int n, int B, const int32_t *shape, int32_t *col, T *cost, T *du, T *dv,
+                   int32_t *kept, T *theta, unsigned flags, hipStream_t s) {
+  HIP_TRY_RC(check_lsap_args(nr, n, B, col, SH_MAX_N_LARGE));
+  if (!C && B > 0) return fail(SH_ERR_ARGS, "null C");
+  if ((!du || !dv) && B > 0) return fail(SH_ERR_ARGS, "null u or v");
+  if (B == 0) return SH_OK;
+  hipLaunchKernelGGL((frow_prep_kernel<S, T>), dim3(B), dim3(PREP_WG), warm_prep_lds(nr, n), s, C, nr, n, shape, col,
+                     du, dv, kept, theta);
+  HIP_TRY(hipGetLastError());
+  if (flags & SH_FLAG_BUILD_ONLY) return SH_OK;
+  auto mw = [&](auto cfg) {
+    using C_ = decltype(cfg);
+    if constexpr (std::is_same<T, int64_t>::value)
+      hipLaunchKernelGGL((frow_i64_kernel<C_::NW, C_::K, S, C_::FB>), dim3(B), dim3(C_::NW * WAVE),
+                         lsap_i64_lds(n, n, C_::NW, C_::FB), s, C, nr, n, shape, col, cost, du, dv, theta, flags);
+    else
+      hipLaunchKernelGGL((frow_f64_mw_kernel<C_::NW, C_::K, S, C_::FB>), dim3(B), dim3(C_::NW * WAVE),
+                         lsap_f64_mw_lds(n, n, C_::NW, C_::FB), s, C, nr, n, shape, col, cost, du, dv, theta);
+    return SH_OK;
+  };
+  if (n > SH_MAX_N) {
+    if constexpr (std::is_same<T, int64_t>::value) with_large_cfg(n, mw);
+    else with_large_f64_cfg(n, mw);
+  } else if (n > 512) {
+    mw(BigCfg<4, 4, 10>{});
+  } else if (n > 256) {
+    mw(BigCfg<4, 2, 10>{});
+  } else if (n > WAVE) {
+    mw(BigCfg<4, 1, 10>{});
+  } else if constexpr (std::is_same<T, int64_t>::value) {
+    mw(BigCfg<1, 1, 10>{});
+  } else {
+    hipLaunchKernelGGL((frow_f64_kernel<1, S>), dim3(B), dim3(WAVE), lsap_f64_lds(n), s, C, nr, n, shape, col, cost,
+                       du, dv, theta);
+  }
+  HIP_TRY(hipGetLastError());
+  return SH_OK;
+}
+
 // The lsap_murty_children_ entries and each expansion of lsap_kbest_: the two
 // launches of launch_warm over the B * nr children, murty_prep_kernel and then
 // the continuation by launch_warm's float table up to SH_MAX_N columns (the
@@ -1207,21 +1254,35 @@ int launch_warm(const S *C, int nr, int n, int B, const int32_t *shape, int32_t 
 // each child's F_t, or null.
 static_assert(murty_prep_lds(SH_MAX_N, SH_MAX_N) <= LDS_NO_ATTR);
 
+// fr (the _fr_ entries, DESIGN.md §22): the free-rows kernels, whose
+// continuations hold the padded problem's n rows.
 template <typename S>
 int launch_murty(const S *C, int nr, int n, int B, const int32_t *shape, const int32_t *pcol, const double *pv,
                  const int32_t *pp, const uint64_t *forb, int32_t *col, double *cost, double *du, double *dv,
-                 int32_t *kept, uint64_t *forb_out, hipStream_t s) {
+                 int32_t *kept, uint64_t *forb_out, bool fr, hipStream_t s) {
   const dim3 grid((unsigned)((size_t)B * nr));
-  hipLaunchKernelGGL((murty_prep_kernel<S>), grid, dim3(PREP_WG), murty_prep_lds(nr, n), s, C, nr, n, shape, pcol, pv,
-                     pp, forb, col, du, dv, kept, forb_out);
+  if (fr)
+    hipLaunchKernelGGL((frow_mprep_kernel<S>), grid, dim3(PREP_WG), murty_prep_lds(nr, n), s, C, nr, n, shape, pcol,
+                       pv, pp, forb, col, du, dv, kept, forb_out);
+  else
+    hipLaunchKernelGGL((murty_prep_kernel<S>), grid, dim3(PREP_WG), murty_prep_lds(nr, n), s, C, nr, n, shape, pcol,
+                       pv, pp, forb, col, du, dv, kept, forb_out);
   auto mw = [&](auto cfg) {
     using C_ = decltype(cfg);
-    hipLaunchKernelGGL((murty_f64_mw_kernel<C_::NW, C_::K, S, C_::FB>), grid, dim3(C_::NW * WAVE),
-                       lsap_f64_mw_lds(nr, n, C_::NW, C_::FB), s, C, nr, n, shape, pcol, pp, forb, col, cost, du, dv);
+    if (fr)
+      hipLaunchKernelGGL((frow_mf64_mw_kernel<C_::NW, C_::K, S, C_::FB>), grid, dim3(C_::NW * WAVE),
+                         lsap_f64_mw_lds(n, n, C_::NW, C_::FB), s, C, nr, n, shape, pcol, pp, forb, col, cost, du, dv);
+    else
+      hipLaunchKernelGGL((murty_f64_mw_kernel<C_::NW, C_::K, S, C_::FB>), grid, dim3(C_::NW * WAVE),
+                         lsap_f64_mw_lds(nr, n, C_::NW, C_::FB), s, C, nr, n, shape, pcol, pp, forb, col, cost, du,
+                         dv);
   };
   if (n > 512) mw(BigCfg<4, 4, 10>{});
   else if (n > 256) mw(BigCfg<4, 2, 10>{});
   else if (n > WAVE) mw(BigCfg<4, 1, 10>{});
+  else if (fr)
+    hipLaunchKernelGGL((frow_mf64_kernel<1, S>), grid, dim3(WAVE), lsap_f64_lds(n), s, C, nr, n, shape, pcol, pp, forb,
+                       col, cost, du, dv);
   else
     hipLaunchKernelGGL((murty_f64_kernel<1, S>), grid, dim3(WAVE), lsap_f64_lds(nr), s, C, nr, n, shape, pcol, pp,
                        forb, col, cost, du, dv);
@@ -1240,12 +1301,12 @@ int check_murty_sizes(int nr, int nc, int B) {
 template <typename S>
 int murty_children(const S *C, int nr, int n, int B, const int32_t *shape, const int32_t *pcol, const double *pv,
                    const int32_t *pp, const uint64_t *forb, int32_t *col, double *cost, double *du, double *dv,
-                   int32_t *kept, hipStream_t s) {
+                   int32_t *kept, bool fr, hipStream_t s) {
   HIP_TRY_RC(check_murty_sizes(nr, n, B));
   if (B > 0 && (!C || !pcol || !pv || !pp || !forb)) return fail(SH_ERR_ARGS, "null C, pcol, pv, p or forb");
   if (B > 0 && (!col || !cost || !du || !dv)) return fail(SH_ERR_ARGS, "null col, cost, u or v");
   if (B == 0) return SH_OK;
-  return launch_murty(C, nr, n, B, shape, pcol, pv, pp, forb, col, cost, du, dv, kept, (uint64_t *)nullptr, s);
+  return launch_murty(C, nr, n, B, shape, pcol, pv, pp, forb, col, cost, du, dv, kept, (uint64_t *)nullptr, fr, s);
 }
 
 // The pool of lsap_kbest_ (KbestPool) inside d_work: the 8-byte arrays, then
@@ -1288,7 +1349,7 @@ size_t kbest_carve(unsigned char *base, int nr, int nc, int B, int k, KbestPool 
 // round r's block: 1 + k + 2 (k - 1) launches, whatever the data.
 template <typename S>
 int kbest(const S *C, int nr, int n, int B, const int32_t *shape, int k, int32_t *cols, double *costs,
-          int32_t *count, void *work, size_t work_bytes, unsigned flags, hipStream_t s) {
+          int32_t *count, void *work, size_t work_bytes, unsigned flags, bool fr, hipStream_t s) {
   HIP_TRY_RC(check_murty_sizes(nr, n, B));
   if (k < 1) return fail(SH_ERR_ARGS, "k < 1");
   if ((uint64_t)k * (uint64_t)nr > (uint64_t)INT32_MAX) return fail(SH_ERR_ARGS, "k * nr exceeds 2^31 - 1");
@@ -1307,7 +1368,7 @@ int kbest(const S *C, int nr, int n, int B, const int32_t *shape, int k, int32_t
     if (r == k - 1) break;
     HIP_TRY_RC(launch_murty(C, nr, n, B, shape, P.stage_col, P.stage_v, P.stage_p, P.stage_forb,
                             P.col + r * bn * nr, P.cost + r * bn, P.u, P.v + r * bn * n, (int32_t *)nullptr,
-                            P.forb + r * bn * W, s));
+                            P.forb + r * bn * W, fr, s));
   }
   HIP_TRY(hipGetLastError());
   return SH_OK;
@@ -1775,24 +1836,43 @@ SH_WARM_ENTRY(f16, uint16_t, _Float16, double)
 SH_WARM_ENTRY(bf16, uint16_t, sh_bf16, double)
 #undef SH_WARM_ENTRY
 
-// The k-best entries of a float cost type (murty_children, kbest).
-#define SH_KBEST_ENTRIES(SUF, CT)                                                                               \
-  int lsap_murty_children_##SUF(const CT *d_C, int nr, int nc, int B, const int32_t *d_shape,                   \
-                                const int32_t *d_pcol, const double *d_pv, const int32_t *d_p,                  \
-                                const uint64_t *d_forb, int32_t *d_col, double *d_cost, double *d_u,            \
-                                double *d_v, int32_t *d_kept, unsigned flags, void *stream) {                   \
+// ... and with free rows (launch_warm_fr): d_kept [B x 2] and d_theta [B] are
+// out and nullable.
+#define SH_WARM_FR_ENTRY(SUF, CT, KT, T)                                                                       \
+  int lsap_warm_fr_##SUF(const CT *d_C, int nr, int nc, int B, const int32_t *d_shape, int32_t *d_col,         \
+                         T *d_cost, T *d_u, T *d_v, int32_t *d_kept, T *d_theta, unsigned flags,               \
+                         void *stream) {                                                                       \
+    return launch_warm_fr((const KT *)d_C, nr, nc, B, d_shape, d_col, d_cost, d_u, d_v, d_kept, d_theta,       \
+                          flags, (hipStream_t)stream);                                                         \
+  }
+SH_WARM_FR_ENTRY(i64, int64_t, int64_t, int64_t)
+SH_WARM_FR_ENTRY(i32, int32_t, int32_t, int64_t)
+SH_WARM_FR_ENTRY(f64, double, double, double)
+SH_WARM_FR_ENTRY(f32, float, float, double)
+SH_WARM_FR_ENTRY(f16, uint16_t, _Float16, double)
+SH_WARM_FR_ENTRY(bf16, uint16_t, sh_bf16, double)
+#undef SH_WARM_FR_ENTRY
+
+// The k-best entries of a float cost type (murty_children, kbest); FR: with free rows.
+#define SH_KBEST_ENTRIES(NAME, CT, FR)                                                                          \
+  int lsap_murty_children_##NAME(const CT *d_C, int nr, int nc, int B, const int32_t *d_shape,                  \
+                                 const int32_t *d_pcol, const double *d_pv, const int32_t *d_p,                 \
+                                 const uint64_t *d_forb, int32_t *d_col, double *d_cost, double *d_u,           \
+                                 double *d_v, int32_t *d_kept, unsigned flags, void *stream) {                  \
     (void)flags;                                                                                                \
     return murty_children(d_C, nr, nc, B, d_shape, d_pcol, d_pv, d_p, d_forb, d_col, d_cost, d_u, d_v, d_kept,  \
-                          (hipStream_t)stream);                                                                 \
+                          FR, (hipStream_t)stream);                                                             \
   }                                                                                                             \
-  int lsap_kbest_##SUF(const CT *d_C, int nr, int nc, int B, const int32_t *d_shape, int k, int32_t *d_cols,    \
-                       double *d_costs, int32_t *d_count, void *d_work, size_t work_bytes, unsigned flags,      \
-                       void *stream) {                                                                          \
-    return kbest(d_C, nr, nc, B, d_shape, k, d_cols, d_costs, d_count, d_work, work_bytes, flags,               \
+  int lsap_kbest_##NAME(const CT *d_C, int nr, int nc, int B, const int32_t *d_shape, int k, int32_t *d_cols,   \
+                        double *d_costs, int32_t *d_count, void *d_work, size_t work_bytes, unsigned flags,     \
+                        void *stream) {                                                                         \
+    return kbest(d_C, nr, nc, B, d_shape, k, d_cols, d_costs, d_count, d_work, work_bytes, flags, FR,           \
                  (hipStream_t)stream);                                                                          \
   }
-SH_KBEST_ENTRIES(f64, double)
-SH_KBEST_ENTRIES(f32, float)
+SH_KBEST_ENTRIES(f64, double, false)
+SH_KBEST_ENTRIES(f32, float, false)
+SH_KBEST_ENTRIES(fr_f64, double, true)
+SH_KBEST_ENTRIES(fr_f32, float, true)
 #undef SH_KBEST_ENTRIES
 
 size_t lsap_kbest_work_bytes(int nr, int nc, int B, int k) {

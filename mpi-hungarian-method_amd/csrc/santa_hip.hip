@@ -8921,6 +8921,653 @@ __global__ void unpack_kernel(int16_t *types, const int32_t *rows, int count, co
   }
 }
 
+// ---------------------------------------------------------------------------
+// Free rows (the lsap_warm_fr_ entries): the warm start of a
+// wide instance (nr < n) solved as the square n x n instance whose rows
+// nr .. n-1 cost 0 everywhere.  Those virtual rows are never stored: FreeRows
+// answers their loads with zeros, their u, col4row and row4col live in the
+// continuation's LDS only and are rebuilt from (col, v) at its entry.  A
+// square state needs neither step 3 nor step 6 of warm_prep_kernel, so a
+// dropped pair costs one Dijkstra and raises no column.
+//   frow_prep_kernel   warm_prep_kernel's steps 1, 2, 4, 5 and 7 on the real
+//     rows, whatever nr; then theta = max_j v[j] and the number of virtual
+//     pairs the rule below keeps (kept[2b + 1])
+//   frow_i64_kernel / frow_f64_kernel / frow_f64_mw_kernel   warm_i64_kernel's,
+//     warm_f64_kernel's and warm_f64_mw_kernel's bodies on n rows behind
+//     FreeRows.  At entry: m = min_j (0 - v[j]) is u of every virtual row (step
+//     4 on a row of zeros), and the columns that are free and have 0 - v[j] ==
+//     m (step 5's test of a virtual pair) go, ascending, to rows nr, nr + 1,
+//     ... while both last.  At exit only the real rows' col and u are
+//     written, the cost is summed over them, and theta = 0 - min_j (0 - v[j])
+//     of the final v.  In exact arithmetic every column no real row holds ends
+//     with v == theta, so the integer kernels (nr < n) store u + theta and
+//     v - theta: lsap_warm_'s contract (v <= 0, v == 0 on a free column).  The
+//     float kernels store the duals as they are: a shift would round.
+// ---------------------------------------------------------------------------
+template <typename L>
+struct FreeRows : L {
+  int nr_real;  // rows i >= nr_real cost 0 in every column and are not read
+  template <typename T, int K, typename... LA>
+  __device__ __forceinline__ void load(int i, T (&c)[K], const LA &...la) const {
+    if (i < nr_real) {
+      L::load(i, c, la...);
+    } else {
+#pragma unroll
+      for (int k = 0; k < K; ++k) c[k] = 0;
+    }
+  }
+};
+
+// min over the workgroup (NW waves), block-uniform; part: LDS [NW], free to
+// reuse after the next barrier
+template <int NW, typename T>
+__device__ __forceinline__ T frow_block_min(T x, T *part) {
+  x = wave_min(x);
+  if constexpr (NW > 1) {
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = x;
+    __syncthreads();
+    x = part[0];
+#pragma unroll
+    for (int q = 1; q < NW; ++q) x = (part[q] < x) ? part[q] : x;
+  }
+  return x;
+}
+
+// m = min_j (0 - v[j]) over the live columns, block-uniform.  skip: bit q
+// leaves column threadIdx.x + 64 NW q out (MurtyLoader's `forced` mask: a
+// column closed to every row below t, the virtual rows among them).
+template <int NW, typename T>
+__device__ __forceinline__ T frow_neg_theta(const T *v_b, int n, T *part, uint32_t skip = 0) {
+  T m = VT<T>::inf();
+  int q = 0;
+  for (int j = threadIdx.x; j < n; j += NW * WAVE, ++q) {
+    const T d = cert_sub((T)0, v_b[j]);
+    m = (d < m && !((skip >> q) & 1u)) ? d : m;
+  }
+  return frow_block_min<NW>(m, part);
+}
+
+// The virtual rows' state (see above).  In: c4r[0 .. nr) and r4c hold the real
+// pairs, every thread is past its writes of them (the caller's barrier).
+// Out: u, c4r of rows nr .. n-1 and r4c of their columns; a barrier ends it.
+// skip: frow_neg_theta's; a skipped column goes to no virtual row.
+template <int NW, typename T>
+__device__ __forceinline__ void frow_virtual_rows(int nr, int n, const T *v_b, T *u_l, int16_t *c4r_l, int16_t *r4c_l,
+                                                  T *part, int *cnt, uint32_t skip = 0) {
+  constexpr int WG = NW * WAVE;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const T m = frow_neg_theta<NW>(v_b, n, part, skip);
+  for (int i = nr + tid; i < n; i += WG) {
+    u_l[i] = m;
+    c4r_l[i] = -1;
+  }
+  __syncthreads();
+  const int room = n - nr;
+  int run = 0;  // free columns at theta below `base` (block-uniform)
+  int q = 0;
+  for (int base = 0; base < n && run < room; base += WG, ++q) {
+    const int j = base + tid;
+    const bool f = j < n && r4c_l[j] < 0 && !((skip >> q) & 1u) && cert_sub((T)0, v_b[j]) == m;
+    const uint64_t bal = __ballot(f);
+    if (lane == 0) cnt[w] = __popcll(bal);
+    __syncthreads();
+    int before = run, tot = 0;
+#pragma unroll
+    for (int q = 0; q < NW; ++q) {
+      const int c = cnt[q];
+      before += (q < w) ? c : 0;
+      tot += c;
+    }
+    const int rank = before + __popcll(bal & ((1ull << lane) - 1ull));
+    if (f && rank < room) {
+      c4r_l[nr + rank] = (int16_t)j;
+      r4c_l[j] = (int16_t)(nr + rank);
+    }
+    run += tot;
+    __syncthreads();  // (cnt is read; the next round writes it)
+  }
+}
+
+template <typename S, typename T>
+__global__ __launch_bounds__(PREP_WG) void frow_prep_kernel(const S *C, int NR, int NC, const int32_t *shape,
+                                                            int32_t *col, T *du, T *dv, int32_t *kept, T *theta) {
+  constexpr bool FLT = std::is_same<T, double>::value;
+  constexpr int NW = PREP_WG / WAVE;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ int s_bad, s_kept, s_free;
+  __shared__ T s_part[NW];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  int nr, n;
+  if (!lsap_shape(shape, b, NR, NC, nr, n)) {
+    lsap_no_instance<PREP_WG>(col, (T *)nullptr, b, NR, NC, du, dv);
+    if (tid == 0 && kept) kept[2 * (size_t)b] = kept[2 * (size_t)b + 1] = 0;
+    if (tid == 0 && theta) theta[b] = 0;
+    return;
+  }
+  size_t off = 0;
+  T *u_l;
+  int16_t *r4c_l, *c4r_l, *q_l;  // (warm_prep_kernel's list; the queue is not used)
+  WARM_PREP_LDS(LDS_CARVE, nr, n)
+  (void)q_l;
+  int32_t *claim = (int32_t *)u_l;
+  int32_t *col_b = col + (size_t)b * NR;
+  T *u_b = du + (size_t)b * NR, *v_b = dv + (size_t)b * NC;
+  const S *C_b = C + (size_t)b * NR * NC;
+  const T INF = VT<T>::inf();
+  if (tid == 0) s_bad = s_kept = s_free = 0;
+  for (int j = tid; j < n; j += PREP_WG) {  // 1
+    v_b[j] = warm_clean_v(v_b[j]);
+    claim[j] = INT32_MAX;
+  }
+  __syncthreads();
+  for (int i = tid; i < nr; i += PREP_WG) {  // 2
+    const int j = col_b[i];
+    const bool ok = j >= 0 && j < n;
+    c4r_l[i] = ok ? (int16_t)j : (int16_t)-1;
+    if (ok) atomicMin(&claim[j], i);
+  }
+  __syncthreads();
+  for (int j = tid; j < n; j += PREP_WG) {
+    const int r = claim[j];
+    r4c_l[j] = (r == INT32_MAX) ? (int16_t)-1 : (int16_t)r;
+  }
+  __syncthreads();  // (the claims are read: u_l may be written)
+  for (int i = w; i < nr; i += NW) {  // 4 and 5
+    const S *row = C_b + (size_t)i * NC;
+    T m = INF;
+#pragma unroll 4
+    for (int j = lane; j < n; j += WAVE) {
+      const T r = cert_sub(cert_widen<T>(row[j]), v_b[j]);
+      m = (r < m) ? r : m;
+    }
+    m = wave_min(m);
+    if (lane == 0) {
+      u_l[i] = m;
+      if (FLT && !(m < INF)) s_bad = 1;
+      const int j = c4r_l[i];
+      if (j >= 0) {
+        const bool mine = r4c_l[j] == i;  // (only row r4c_l[j] ever writes that slot)
+        if (!(mine && cert_sub(cert_widen<T>(row[j]), v_b[j]) == m)) {
+          c4r_l[i] = -1;
+          if (mine) r4c_l[j] = -1;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const bool bad = FLT && s_bad;
+  // theta and the virtual pairs that frow_virtual_rows will keep
+  const T m = frow_neg_theta<NW>(v_b, n, s_part);
+  int fr = 0;
+  for (int j = tid; j < n; j += PREP_WG) fr += r4c_l[j] < 0 && cert_sub((T)0, v_b[j]) == m;
+  int k = 0;
+  for (int i = tid; i < NR; i += PREP_WG) {
+    const int c = (i < nr && !bad) ? c4r_l[i] : -1;
+    col_b[i] = c;
+    k += c >= 0;
+    T x = (i < nr) ? u_l[i] : (T)0;
+    if constexpr (FLT) x = (bad && i < nr) ? __builtin_nan("") : x;
+    u_b[i] = x;
+  }
+  __syncthreads();  // (every thread has read v: the NaNs below may be written)
+  for (int j = tid; j < NC; j += PREP_WG) {
+    if (j >= n) v_b[j] = 0;
+    if constexpr (FLT) {
+      if (bad && j < n) v_b[j] = __builtin_nan("");
+    }
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    k += __shfl_xor(k, o, WAVE);
+    fr += __shfl_xor(fr, o, WAVE);
+  }
+  if (lane == 0 && k) atomicAdd(&s_kept, k);
+  if (lane == 0 && fr) atomicAdd(&s_free, fr);
+  __syncthreads();
+  if (tid == 0) {
+    if (kept) {
+      kept[2 * (size_t)b] = s_kept;
+      kept[2 * (size_t)b + 1] = bad ? 0 : min(s_free, n - nr);
+    }
+    if (theta) {
+      T t = cert_sub((T)0, m);
+      if constexpr (FLT) t = bad ? __builtin_nan("") : t;
+      theta[b] = t;
+    }
+  }
+}
+
+// warm_i64_kernel on the padded problem (col, du, dv in / out; theta out).
+template <int NW, int K, typename S, int FB>
+__global__ __launch_bounds__(NW * WAVE) void frow_i64_kernel(const S *C, int NR, int NC, const int32_t *shape,
+                                                             int32_t *col, int64_t *cost, int64_t *du, int64_t *dv,
+                                                             int64_t *theta, unsigned flags) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ int64_t s_part[NW];
+  __shared__ int s_cnt[NW];
+  constexpr int WG = NW * WAVE;
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  int nr, n;
+  if (!lsap_shape(shape, b, NR, NC, nr, n)) {  // (frow_prep_kernel wrote the rest)
+    if (tid == 0 && cost) cost[b] = 0;
+    return;
+  }
+  size_t off = 0;
+  SolveLds Sl;
+  int64_t *part;
+  LSAP_I64_LDS(LDS_CARVE, n, n, NW)
+  int64_t *v_b = dv + (size_t)b * NC;
+  for (int i = tid; i < n; i += WG) {
+    if (i < nr) {
+      Sl.u[i] = du[(size_t)b * NR + i];
+      Sl.c4r[i] = (int16_t)col[(size_t)b * NR + i];
+    }
+    Sl.r4c[i] = -1;
+  }
+  __syncthreads();
+  for (int i = tid; i < nr; i += WG) {
+    const int j = Sl.c4r[i];
+    if (j >= 0) Sl.r4c[j] = (int16_t)i;
+  }
+  __syncthreads();
+  frow_virtual_rows<NW>(nr, n, v_b, Sl.u, Sl.c4r, Sl.r4c, s_part, s_cnt);
+  int64_t steps = 0;
+  int fallbacks = 0;
+  const bool exact = (flags & SH_FLAG_EXACT_ARGMIN) != 0;
+  const size_t base = (size_t)b * NR * NC;
+  using LD = WithDuals<FreeRows<GlobalLoader<NW, K, S>>, int64_t>;
+  const LD ld{{{C + base, n, NC, n}, nr}, v_b};
+  sap_solve_mw<NW, K, LD, FB, true, true, true>(n, ld, Sl, steps, fallbacks, exact);
+  __syncthreads();  // (every thread stored the v of its columns)
+  const int64_t th = cert_sub((int64_t)0, frow_neg_theta<NW>(v_b, n, s_part));
+  const int64_t sh = (nr < n) ? th : 0;  // (a square instance is lsap_warm_'s, duals and all)
+  for (int j = tid; j < n; j += WG) v_b[j] = cert_sub(v_b[j], sh);  // (after frow_neg_theta's barrier)
+  for (int i = tid; i < nr; i += WG) du[(size_t)b * NR + i] = cert_add(Sl.u[i], sh);
+  duals_fill<int64_t, WG>(du, dv, b, NR, NC, nr, n, 0);
+  if (tid == 0 && theta) theta[b] = th;
+  int64_t acc = 0;
+  for (int i = tid; i < NR; i += WG) {
+    const int cidx = (i < nr) ? Sl.c4r[i] : -1;
+    col[(size_t)b * NR + i] = cidx;
+    if (cost && i < nr) acc += (int64_t)C[base + (size_t)i * NC + cidx];
+  }
+  acc = wave_sum_i64(acc);
+  if ((tid & 63) == 0) part[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0 && cost) {
+    int64_t t = 0;
+    for (int q = 0; q < NW; ++q) t += part[q];
+    cost[b] = t;
+  }
+}
+
+// warm_f64_kernel on the padded problem: one wave, n <= 64, lane j owns column j.
+template <int K, typename S>
+__global__ __launch_bounds__(WAVE) void frow_f64_kernel(const S *C, int NR, int NC, const int32_t *shape,
+                                                        int32_t *col, double *cost, double *du, double *dv,
+                                                        double *theta) {
+  static_assert(K == 1, "the virtual rows' ranks are one ballot");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int b = blockIdx.x;
+  const int lane = threadIdx.x;
+  int nr, n;
+  if (warm_f64_done(shape, b, NR, NC, nr, n, du, cost)) return;
+  size_t off = 0;
+  double *u_l;
+  int16_t *c4r_l;
+  LSAP_F64_LDS(LDS_CARVE, n)
+  const double *v_b = dv + (size_t)b * NC;
+  for (int i = lane; i < nr; i += WAVE) {
+    u_l[i] = du[(size_t)b * NR + i];
+    c4r_l[i] = (int16_t)col[(size_t)b * NR + i];
+  }
+  __syncthreads();
+  {  // the virtual rows (frow_virtual_rows with the columns' state in registers)
+    bool taken = false;
+    for (int i = 0; i < nr; ++i) taken |= c4r_l[i] == lane;
+    const double d = (lane < n) ? 0.0 - v_b[lane] : __builtin_inf();
+    const double m = wave_min(d);
+    const bool f = lane < n && !taken && d == m;
+    const uint64_t bal = __ballot(f);
+    const int rank = __popcll(bal & ((1ull << lane) - 1ull));
+    for (int i = nr + lane; i < n; i += WAVE) {
+      u_l[i] = m;
+      c4r_l[i] = -1;
+    }
+    __syncthreads();
+    if (f && rank < n - nr) c4r_l[nr + rank] = (int16_t)lane;
+    __syncthreads();
+  }
+  int64_t steps = 0;
+  const size_t base = (size_t)b * NR * NC;
+  using GL = FreeRows<GlobalLoaderF64<1, K, S>>;
+  WithDuals<GL, double> ld{GL{{C + base, n, NC}, nr}};
+  ld.dv = dv + (size_t)b * NC;
+  const int st = sap_solve<K, double, true, true>(n, n, ld, u_l, c4r_l, steps);
+  __syncthreads();
+  duals_store_f64<WAVE>(du, dv, u_l, st, b, NR, NC, nr, n);
+  if (theta) {
+    const double m = wave_min((lane < n) ? 0.0 - v_b[lane] : __builtin_inf());
+    if (lane == 0) theta[b] = (st == 0) ? 0.0 - m : __builtin_nan("");
+  }
+  double acc = 0;
+  for (int i = lane; i < NR; i += WAVE) {
+    const bool live = st == 0 && i < nr;
+    const int cidx = live ? c4r_l[i] : -1;
+    col[(size_t)b * NR + i] = cidx;
+    if (live && cost) acc += widen_f64(C[base + (size_t)i * NC + cidx]);
+  }
+  if (cost) {  // (lsap_f64_kernel's order)
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, WAVE);
+    if (lane == 0) cost[b] = acc;
+  }
+}
+
+// ... and warm_f64_mw_kernel.
+template <int NW, int K, typename S, int FB>
+__global__ __launch_bounds__(NW * WAVE) void frow_f64_mw_kernel(const S *C, int NR, int NC, const int32_t *shape,
+                                                                int32_t *col, double *cost, double *du, double *dv,
+                                                                double *theta) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ double s_part[NW];
+  __shared__ int s_cnt[NW];
+  constexpr int WG = NW * WAVE;
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  int nr, n;
+  if (warm_f64_done(shape, b, NR, NC, nr, n, du, cost)) return;
+  size_t off = 0;
+  SolveLdsF64 Sl;
+  LSAP_F64_MW_LDS(LDS_CARVE, n, n, NW, FB)
+  const double *v_b = dv + (size_t)b * NC;
+  for (int i = tid; i < n; i += WG) {
+    if (i < nr) {
+      Sl.u[i] = du[(size_t)b * NR + i];
+      Sl.c4r[i] = (int16_t)col[(size_t)b * NR + i];
+    }
+    Sl.r4c[i] = -1;
+    Sl.path[i] = -1;
+  }
+  __syncthreads();
+  for (int i = tid; i < nr; i += WG) {
+    const int j = Sl.c4r[i];
+    if (j >= 0) Sl.r4c[j] = (int16_t)i;
+  }
+  __syncthreads();
+  frow_virtual_rows<NW>(nr, n, v_b, Sl.u, Sl.c4r, Sl.r4c, s_part, s_cnt);
+  const size_t base = (size_t)b * NR * NC;
+  using GL = FreeRows<GlobalLoaderF64<NW, K, S>>;
+  WithDuals<GL, double> ld{GL{{C + base, n, NC}, nr}};
+  ld.dv = dv + (size_t)b * NC;
+  const int st = sap_solve_mw_f64<NW, K, true, FB, true>(n, n, ld, Sl);
+  __syncthreads();
+  if (st == 0) {  // (block-uniform; before duals_store_f64 could write NaN over v)
+    const double m = frow_neg_theta<NW>(v_b, n, s_part);
+    if (tid == 0 && theta) theta[b] = 0.0 - m;
+  } else if (tid == 0 && theta) {
+    theta[b] = __builtin_nan("");
+  }
+  duals_store_f64<WG>(du, dv, Sl.u, st, b, NR, NC, nr, n);
+  for (int i = tid; i < NR; i += WG) col[(size_t)b * NR + i] = (st == 0 && i < nr) ? Sl.c4r[i] : -1;
+  if (cost && tid < WAVE) {
+    double acc = 0;
+    for (int i = tid; i < NR; i += WAVE)
+      if (st == 0 && i < nr) acc += widen_f64(C[base + (size_t)i * NC + Sl.c4r[i]]);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, WAVE);
+    if (tid == 0) cost[b] = acc;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Free rows in Murty's partition (the lsap_murty_children_fr_ and
+// lsap_kbest_fr_ entries): child t of a node is the free-rows
+// warm start on M_t, whose virtual rows nr .. n-1 are rows > t: 0, and +inf on
+// the columns the rows < t force.  A node stays (col [nr], v [n], p, F, cost):
+// the virtual pairs are recomputed from (col, v) by frow_virtual_rows' rule
+// with the forced columns left out (theta is the maximum over the others).
+//   frow_mprep_kernel   murty_prep_kernel without steps 3 and 6
+//   frow_mf64_kernel / frow_mf64_mw_kernel   murty_f64_kernel's and
+//     murty_f64_mw_kernel's bodies on n rows behind FreeRowsMurty
+// ---------------------------------------------------------------------------
+template <int NW, int K, typename S>
+struct FreeRowsMurty : MurtyLoader<NW, K, S> {
+  int nr_real;
+  __device__ __forceinline__ void load(int i, double (&c)[K]) const {
+    if (i < nr_real) {
+      MurtyLoader<NW, K, S>::load(i, c);
+    } else {
+#pragma unroll
+      for (int k = 0; k < K; ++k) c[k] = ((this->forced >> k) & 1u) ? __builtin_inf() : 0.0;
+    }
+  }
+};
+
+template <typename S>
+__global__ __launch_bounds__(PREP_WG) void frow_mprep_kernel(const S *C, int NR, int NC, const int32_t *shape,
+                                                             const int32_t *pcol, const double *pv,
+                                                             const int32_t *pp, const uint64_t *forb, int32_t *col,
+                                                             double *du, double *dv, int32_t *kept,
+                                                             uint64_t *forb_out) {
+  using T = double;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ int s_bad, s_kept;
+  const int c = blockIdx.x, b = c / NR, t = c - b * NR;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int W = murty_words(NC);
+  int nr, n, p;
+  if (!murty_child(shape, pp, b, t, NR, NC, nr, n, p)) {
+    lsap_no_instance<PREP_WG>(col, (T *)nullptr, c, NR, NC, du, dv);
+    if (tid == 0 && kept) kept[c] = 0;
+    if (forb_out)
+      for (int x = tid; x < W; x += PREP_WG) forb_out[(size_t)c * W + x] = 0;
+    return;
+  }
+  size_t off = 0;
+  T *u_l;
+  int16_t *r4c_l, *c4r_l, *q_l;  // (murty_prep_kernel's list; the queue is not used)
+  uint8_t *msk_l;
+  MURTY_PREP_LDS(LDS_CARVE, nr, n)
+  (void)q_l;
+  int32_t *claim = (int32_t *)u_l;
+  const int32_t *pcol_b = pcol + (size_t)b * NR;
+  const double *pv_b = pv + (size_t)b * NC;
+  const uint64_t *F_b = forb + (size_t)b * W;
+  int32_t *col_c = col + (size_t)c * NR;
+  T *u_c = du + (size_t)c * NR, *v_c = dv + (size_t)c * NC;
+  const S *C_b = C + (size_t)b * NR * NC;
+  const T INF = VT<T>::inf();
+  int ct = pcol_b[t];
+  ct = (ct >= 0 && ct < n) ? ct : -1;
+  if (tid == 0) s_bad = s_kept = 0;
+  for (int j = tid; j < n; j += PREP_WG) {  // 1
+    v_c[j] = warm_clean_v(pv_b[j]);
+    claim[j] = INT32_MAX;
+  }
+  __syncthreads();
+  for (int i = tid; i < nr; i += PREP_WG) {  // 2
+    const int j = pcol_b[i];
+    const bool ok = j >= 0 && j < n;
+    c4r_l[i] = ok ? (int16_t)j : (int16_t)-1;
+    if (ok) atomicMin(&claim[j], i);
+  }
+  __syncthreads();
+  for (int j = tid; j < n; j += PREP_WG) {
+    const int r = claim[j];
+    r4c_l[j] = (r == INT32_MAX) ? (int16_t)-1 : (int16_t)r;
+    msk_l[j] = (uint8_t)((r < t ? 1 : 0) | (murty_forbidden(F_b, p, t, ct, j) ? 2 : 0));
+  }
+  __syncthreads();  // (the claims are read: u_l may be written)
+  for (int i = w; i < nr; i += PREP_WG / WAVE) {  // 4 and 5
+    const S *row = C_b + (size_t)i * NC;
+    T m = INF;
+    if (i < t) {
+      const int j = c4r_l[i];
+      if (lane == 0 && j >= 0) m = cert_sub(cert_widen<T>(row[j]), v_c[j]);
+    } else {
+      const int bits = (i == t) ? 3 : 1;
+#pragma unroll 4
+      for (int j = lane; j < n; j += WAVE) {
+        const T x = (msk_l[j] & bits) ? INF : cert_widen<T>(row[j]);
+        const T r = cert_sub(x, v_c[j]);
+        m = (r < m) ? r : m;
+      }
+    }
+    m = wave_min(m);
+    if (lane == 0) {
+      u_l[i] = m;
+      if (!(m < INF)) s_bad = 1;
+      const int j = c4r_l[i];
+      if (j >= 0) {
+        const bool mine = r4c_l[j] == i;  // (only row r4c_l[j] ever writes that slot)
+        const bool masked = i >= t && (msk_l[j] & (i == t ? 3 : 1)) != 0;  // (i < t: j is its own column)
+        const T x = masked ? INF : cert_widen<T>(row[j]);
+        if (!(mine && cert_sub(x, v_c[j]) == m)) {
+          c4r_l[i] = -1;
+          if (mine) r4c_l[j] = -1;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const bool bad = s_bad;
+  int k = 0;
+  for (int i = tid; i < NR; i += PREP_WG) {
+    const int x = (i < nr && !bad) ? c4r_l[i] : -1;
+    col_c[i] = x;
+    k += x >= 0;
+    u_c[i] = (i < nr) ? (bad ? (T)__builtin_nan("") : u_l[i]) : (T)0;
+  }
+  for (int j = tid; j < NC; j += PREP_WG) {
+    if (j >= n) v_c[j] = 0;
+    else if (bad) v_c[j] = __builtin_nan("");
+  }
+  if (forb_out)
+    for (int x = tid; x < W; x += PREP_WG)
+      forb_out[(size_t)c * W + x] = (t == p ? F_b[x] : 0) | ((ct >= 0 && (ct >> 6) == x) ? 1ull << (ct & 63) : 0ull);
+  if (kept) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) k += __shfl_xor(k, o, WAVE);
+    if (lane == 0 && k) atomicAdd(&s_kept, k);
+    __syncthreads();
+    if (tid == 0) kept[c] = s_kept;
+  }
+}
+
+// murty_f64_kernel on the padded M_t: one wave, n <= 64, lane j owns column j.
+template <int K, typename S>
+__global__ __launch_bounds__(WAVE) void frow_mf64_kernel(const S *C, int NR, int NC, const int32_t *shape,
+                                                         const int32_t *pcol, const int32_t *pp,
+                                                         const uint64_t *forb, int32_t *col, double *cost,
+                                                         double *du, double *dv) {
+  static_assert(K == 1, "the virtual rows' ranks are one ballot");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int c = blockIdx.x, b = c / NR, t = c - b * NR;
+  const int lane = threadIdx.x;
+  int nr, n, p;
+  if (murty_done(shape, pp, b, t, c, NR, NC, nr, n, p, du, cost)) return;
+  size_t off = 0;
+  double *u_l;
+  int16_t *c4r_l;
+  LSAP_F64_LDS(LDS_CARVE, n)
+  const double *v_c = dv + (size_t)c * NC;
+  for (int i = lane; i < nr; i += WAVE) {
+    u_l[i] = du[(size_t)c * NR + i];
+    c4r_l[i] = (int16_t)col[(size_t)c * NR + i];
+  }
+  __syncthreads();
+  const size_t base = (size_t)b * NR * NC;
+  using ML = FreeRowsMurty<1, K, S>;
+  WithDuals<ML, double> ld{ML{{C + base, n, NC, pcol + (size_t)b * NR, t, 0u, 0u}, nr}};
+  ld.masks(forb + (size_t)b * murty_words(NC), p);
+  ld.dv = dv + (size_t)c * NC;
+  {  // the virtual rows (frow_f64_kernel's block, the forced columns left out)
+    bool taken = false;
+    for (int i = 0; i < nr; ++i) taken |= c4r_l[i] == lane;
+    const bool open = lane < n && !(ld.forced & 1u);
+    const double d = open ? 0.0 - v_c[lane] : __builtin_inf();
+    const double m = wave_min(d);
+    const bool f = open && !taken && d == m;
+    const uint64_t bal = __ballot(f);
+    const int rank = __popcll(bal & ((1ull << lane) - 1ull));
+    for (int i = nr + lane; i < n; i += WAVE) {
+      u_l[i] = m;
+      c4r_l[i] = -1;
+    }
+    __syncthreads();
+    if (f && rank < n - nr) c4r_l[nr + rank] = (int16_t)lane;
+    __syncthreads();
+  }
+  int64_t steps = 0;
+  const int st = sap_solve<K, double, true, true>(n, n, ld, u_l, c4r_l, steps);
+  __syncthreads();
+  duals_store_f64<WAVE>(du, dv, u_l, st, c, NR, NC, nr, n);
+  double acc = 0;
+  for (int i = lane; i < NR; i += WAVE) {
+    const bool live = st == 0 && i < nr;
+    const int cidx = live ? c4r_l[i] : -1;
+    col[(size_t)c * NR + i] = cidx;
+    if (live) acc += widen_f64(C[base + (size_t)i * NC + cidx]);
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, WAVE);  // (warm_f64_kernel's order)
+  if (lane == 0) cost[c] = st == 0 ? acc : __builtin_inf();
+}
+
+// ... and murty_f64_mw_kernel.
+template <int NW, int K, typename S, int FB>
+__global__ __launch_bounds__(NW * WAVE) void frow_mf64_mw_kernel(const S *C, int NR, int NC, const int32_t *shape,
+                                                                 const int32_t *pcol, const int32_t *pp,
+                                                                 const uint64_t *forb, int32_t *col, double *cost,
+                                                                 double *du, double *dv) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ double s_part[NW];
+  __shared__ int s_cnt[NW];
+  constexpr int WG = NW * WAVE;
+  const int c = blockIdx.x, b = c / NR, t = c - b * NR;
+  const int tid = threadIdx.x;
+  int nr, n, p;
+  if (murty_done(shape, pp, b, t, c, NR, NC, nr, n, p, du, cost)) return;
+  size_t off = 0;
+  SolveLdsF64 Sl;
+  LSAP_F64_MW_LDS(LDS_CARVE, n, n, NW, FB)
+  for (int i = tid; i < n; i += WG) {
+    if (i < nr) {
+      Sl.u[i] = du[(size_t)c * NR + i];
+      Sl.c4r[i] = (int16_t)col[(size_t)c * NR + i];
+    }
+    Sl.r4c[i] = -1;
+    Sl.path[i] = -1;
+  }
+  __syncthreads();
+  for (int i = tid; i < nr; i += WG) {
+    const int j = Sl.c4r[i];
+    if (j >= 0) Sl.r4c[j] = (int16_t)i;
+  }
+  __syncthreads();
+  const size_t base = (size_t)b * NR * NC;
+  using ML = FreeRowsMurty<NW, K, S>;
+  WithDuals<ML, double> ld{ML{{C + base, n, NC, pcol + (size_t)b * NR, t, 0u, 0u}, nr}};
+  ld.masks(forb + (size_t)b * murty_words(NC), p);
+  ld.dv = dv + (size_t)c * NC;
+  // (bit k of ld.forced is column tid + WG k: frow_virtual_rows' skip)
+  frow_virtual_rows<NW>(nr, n, dv + (size_t)c * NC, Sl.u, Sl.c4r, Sl.r4c, s_part, s_cnt, ld.forced);
+  const int st = sap_solve_mw_f64<NW, K, true, FB, true>(n, n, ld, Sl);
+  __syncthreads();
+  duals_store_f64<WG>(du, dv, Sl.u, st, c, NR, NC, nr, n);
+  for (int i = tid; i < NR; i += WG) col[(size_t)c * NR + i] = (st == 0 && i < nr) ? Sl.c4r[i] : -1;
+  if (tid < WAVE) {
+    double acc = 0;
+    for (int i = tid; i < NR; i += WAVE)
+      if (st == 0 && i < nr) acc += widen_f64(C[base + (size_t)i * NC + Sl.c4r[i]]);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, WAVE);
+    if (tid == 0) cost[c] = st == 0 ? acc : __builtin_inf();
+  }
+}
+
 }  // namespace
 
 // Host side: the same translation unit, so it launches the kernels above by name.

@@ -158,6 +158,8 @@ for _suf in ("i64", "i32", "f64", "f32", "f16", "bf16"):  # the duals / check_du
     SIGNATURES["lbap_check_" + _suf] = (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _U, _P])
     # the warm start: C, nr, nc, B, shape, col (in / out), cost, u, v (in / out), kept, flags, stream
     SIGNATURES["lsap_warm_" + _suf] = (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _U, _P])
+    # ... with free rows: C, nr, nc, B, shape, col (in / out), cost, u, v (in / out), kept [B x 2], theta, flags, stream
+    SIGNATURES["lsap_warm_fr_" + _suf] = (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _U, _P])
 # the sparse (CSR) float entries: indptr, indices, data, nr, nc, B, shape, col, cost, u, v, work, work_bytes, flags, stream
 SIGNATURES["lsap_csr_work_bytes"] = (ctypes.c_size_t, [_I, _I, _I])
 for _suf in ("f64", "f32"):
@@ -177,6 +179,9 @@ for _suf in ("f64", "f32"):
     SIGNATURES["lsap_murty_children_" + _suf] = (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U, _P])
     # the k best: C, nr, nc, B, shape, k, cols, costs, count, work, work_bytes, flags, stream
     SIGNATURES["lsap_kbest_" + _suf] = (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P, _P, ctypes.c_size_t, _U, _P])
+    # ... both with free rows: their argument lists
+    SIGNATURES["lsap_murty_children_fr_" + _suf] = SIGNATURES["lsap_murty_children_" + _suf]
+    SIGNATURES["lsap_kbest_fr_" + _suf] = SIGNATURES["lsap_kbest_" + _suf]
     # Murty's expansion on the CSR: indptr, indices, data, nr, nc, B, shape, pcol, pv, p, forb, col, cost, u, v, kept,
     # work, work_bytes, flags, stream
     SIGNATURES["lsap_murty_children_csr_" + _suf] = (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P,

@@ -379,9 +379,93 @@ def resolve_batched(C: torch.Tensor, col: torch.Tensor, u: torch.Tensor, v: torc
     return col_w, cost, u_w, v_w, kept
 
 
-def linear_sum_assignment_resolve(cost_matrix, col_ind, u, v, maximize: bool = False, device: int | str = 0):
+def resolve_batched_free_rows(C: torch.Tensor, col: torch.Tensor, u: torch.Tensor, v: torch.Tensor,
+                              with_cost: bool = True, flags: int = 0, shapes=None, maximize: bool = False):
+    """resolve_batched for wide instances (nr < nc), solved as the padded
+    square problem whose nc - nr extra rows cost 0 everywhere (the lsap_warm_fr_
+    entries) -> (col, cost, u, v, kept int32 [B], kept_free
+    int32 [B], theta [B] of the duals' dtype).
+
+    The extra rows are never stored.  A square state needs no raising of column
+    duals: a previous pair that is no longer tight costs one Dijkstra and
+    breaks no other pair, where resolve_batched on a wide instance raises the
+    dual of every free and broken column to 0, which with generic costs breaks
+    most of the assignment.  The price is one Dijkstra for every virtual row
+    whose column the start state does not hold (nc_b - nr_b - kept_free of
+    them; none from the result of solve_batched_large or of an integer
+    resolve) and up to nc - nr steps more in each Dijkstra, which read no
+    memory but are steps.
+
+    When it pays (measured on the MI355X with random costs):
+    when nearly every column holds a row (nc - nr a few percent of nc) and few
+    rows changed.  One redrawn row: 8x to 10x over a cold solve at 250 x 256
+    and 4.4x to 6.6x at 1900 x 2000, where resolve_batched is no faster than
+    the cold solve.  It breaks even with the cold solve at about 1 % redrawn
+    rows at 1900 x 2000 (1.4x to 1.8x at 10 % of 250 x 256) and loses beyond:
+    0.2x at 10 % of 1900 x 2000, 0.05x to 0.5x with every row redrawn, below
+    resolve_batched.  With fewer rows than half the columns (64 x 1024, 1000 x
+    2000) it loses from the first redrawn row, 0.03x to 0.33x of
+    resolve_batched, which has little to raise there: use that.
+
+    Arguments, layout, padding, tall batches (solved as their transpose),
+    maximize, infeasibility and the reading of the previous state are
+    resolve_batched's.  (nr_b - kept) + (nc_b - nr_b - kept_free) Dijkstras
+    run.  theta is the largest column dual of the padded problem's final state
+    (the smallest under maximize).
+
+    Integer costs, nr_b < nc_b: u and v are the normalised duals u + theta and
+    v - theta, exact, with the signs and equalities check_duals_large tests on
+    the unpadded C; they may go back into this function or into
+    resolve_batched.  Float costs: u and v are the padded problem's duals bit
+    for bit; a free column holds v == theta up to rounding and not 0, so they
+    are the input of this function's next call and not of resolve_batched, and
+    check_duals_large's sign test does not apply to them.  A square instance
+    gets what resolve_batched returns.
+    flags: SH_FLAG_EXACT_ARGMIN; SH_FLAG_BUILD_ONLY returns the start state (the
+    kept real pairs, u, v without a shift, the counts, its theta; cost 0)."""
+    p = plan(C.shape, C.dtype, _lib.SH_MAX_N_LARGE, shapes)
+    check_solution(p, C.dtype, col, u, v)
+    dev = C.device
+    if p.empty:
+        z = torch.zeros(p.B, dtype=torch.int32, device=dev)
+        return empty_result(p, with_cost, True, p.ddt, dev) + (z, z.clone(), torch.zeros(p.B, dtype=p.ddt, device=dev))
+    require_gpu()
+    col0 = narrow_col(col)
+    if maximize:
+        C, u, v = minimised(C, u, v)
+    if p.tall:
+        C, u, v = wide_view(C, u, v)
+        col0, bad = invert_col(col0, p.NC)
+        col0[bad] = -1
+    C = C.contiguous()
+    _check_int64_range(C)
+    col_w, v_w = col0.clone().contiguous(), v.clone().contiguous()
+    u_w = torch.empty((p.B, p.nr), dtype=p.ddt, device=dev)
+    build_only = bool(flags & _lib.SH_FLAG_BUILD_ONLY)
+    cost = (torch.zeros if build_only else torch.empty)(p.B, dtype=p.ddt, device=dev) if with_cost else None
+    kept = torch.empty((p.B, 2), dtype=torch.int32, device=dev)
+    theta = torch.empty(p.B, dtype=p.ddt, device=dev)
+    shape_dev = p.shapes_on(dev) if p.shapes is not None else None
+    rc = getattr(_lib.lib(), "lsap_warm_fr_" + DTYPE_SUFFIX[C.dtype])(
+        _p(C), p.nr, p.nc, p.B, _p(shape_dev), _p(col_w), _p(cost), _p(u_w), _p(v_w), _p(kept), _p(theta),
+        _lib.SH_COMPAT_TIEBREAK | flags, current_stream_handle(dev))
+    _lib.check(rc, "lsap_warm_fr")
+    if p.tall:
+        col_w, u_w, v_w = tall_view(p, col_w, u_w, v_w)
+    if maximize:
+        cost = -cost if cost is not None else None
+        u_w, v_w, theta = -u_w, -v_w, -theta
+    return col_w, cost, u_w, v_w, kept[:, 0].contiguous(), kept[:, 1].contiguous(), theta
+
+
+def linear_sum_assignment_resolve(cost_matrix, col_ind, u, v, maximize: bool = False, device: int | str = 0,
+                                  free_rows: bool = False):
     """linear_sum_assignment_large(duals=True) started from a previous solution
     of a nearby matrix -> (row_ind, col_ind, u, v).
+
+    free_rows=True solves a rectangular matrix as its padded square problem
+    (resolve_batched_free_rows, whose duals it returns: normalised on the exact
+    integer route, the padded problem's on the float64 route).
 
     col_ind [nr] holds the previous column of every row, -1 for a row without
     one (for wide and square input that is the col_ind of an earlier call; from
@@ -412,8 +496,9 @@ def linear_sum_assignment_resolve(cost_matrix, col_ind, u, v, maximize: bool = F
         col0, bad = invert_col(col0, nc)
         col0[bad] = -1
     m = Ct.shape[0]
-    col, _, ru, rv, _ = resolve_batched(Ct.unsqueeze(0).to(dev), col0.to(dev), torch.zeros((1, m), dtype=v0.dtype, device=dev),
-                                        v0.to(dev), with_cost=False)
+    resolve = resolve_batched_free_rows if free_rows else resolve_batched
+    col, _, ru, rv = resolve(Ct.unsqueeze(0).to(dev), col0.to(dev), torch.zeros((1, m), dtype=v0.dtype, device=dev),
+                             v0.to(dev), with_cost=False)[:4]
     return single_result(col, tall, ru, rv, negate=maximize)
 
 
@@ -438,7 +523,7 @@ def forbidden_words(nc: int) -> int:
 
 
 def murty_children_batched(C: torch.Tensor, col: torch.Tensor, v: torch.Tensor, p: torch.Tensor,
-                           forb: torch.Tensor, shapes=None):
+                           forb: torch.Tensor, shapes=None, free_rows: bool = False):
     """Expand one Murty node per instance into its NR children (the
     lsap_murty_children_ entries) -> (col int32 [B, NR, NR], cost float64
     [B, NR], u [B, NR, NR], v [B, NR, NC], kept int32 [B, NR]).
@@ -451,7 +536,16 @@ def murty_children_batched(C: torch.Tensor, col: torch.Tensor, v: torch.Tensor, 
     their columns, those columns closed to the rows below, and forb (if
     t == p) and col[t] closed to row t; its slot is [b, t].  A child that does
     not exist or is infeasible has col -1 and cost +inf.  The node is read as
-    data and not modified."""
+    data and not modified.
+
+    free_rows=True (the lsap_murty_children_fr_ entries) computes every child
+    as resolve_batched_free_rows does, on the masked matrix padded square with
+    rows that cost 0 and are closed to the columns of the rows < t: the same
+    optimum, one Dijkstra a child on a wide instance where the default raises
+    column duals and runs many (measured at 250 x 256: 1 against 53 to 58 for
+    the root's children).  v then holds the padded
+    problem's column duals (a free column has v == theta up to rounding, not 0)
+    and kept the real pairs; such a v is a node for free_rows=True only."""
     _kbest_dtype(C)
     p_ = plan(C.shape, C.dtype, _lib.SH_MAX_N, shapes)
     if p_.tall:
@@ -484,14 +578,15 @@ def murty_children_batched(C: torch.Tensor, col: torch.Tensor, v: torch.Tensor, 
     cv = torch.empty((B, NR, NC), dtype=torch.float64, device=dev)
     kept = torch.empty((B, NR), dtype=torch.int32, device=dev)
     shape_dev = p_.shapes_on(dev) if p_.shapes is not None else None
-    rc = getattr(_lib.lib(), "lsap_murty_children_" + DTYPE_SUFFIX[C.dtype])(
+    entry = ("lsap_murty_children_fr_" if free_rows else "lsap_murty_children_") + DTYPE_SUFFIX[C.dtype]
+    rc = getattr(_lib.lib(), entry)(
         _p(C), NR, NC, B, _p(shape_dev), _p(col0), _p(v0), _p(p0), _p(f0), _p(ccol), _p(cost), _p(cu), _p(cv),
         _p(kept), _lib.SH_COMPAT_TIEBREAK, current_stream_handle(dev))
     _lib.check(rc, "lsap_murty_children")
     return ccol, cost, cu, cv, kept
 
 
-def kbest_batched(C: torch.Tensor, k: int, shapes=None, maximize: bool = False):
+def kbest_batched(C: torch.Tensor, k: int, shapes=None, maximize: bool = False, free_rows: bool = False):
     """The k best assignments of every instance (the lsap_kbest_ entries) ->
     (cols int32 [B, k, NR], costs float64 [B, k], count int32 [B]).
 
@@ -503,7 +598,17 @@ def kbest_batched(C: torch.Tensor, k: int, shapes=None, maximize: bool = False):
     distinct, and count[b] <= k of them exist: the ranks beyond have col -1 and
     cost +inf (-inf under maximize).  cols[b, r, i] is the column of row i, -1
     for the rows a tall instance leaves out.  One call launches 3 k - 1 kernels
-    whatever the data, allocates its pool once and never synchronises."""
+    whatever the data, allocates its pool once and never synchronises.
+
+    free_rows=True (the lsap_kbest_fr_ entries) expands every node with
+    murty_children_batched(free_rows=True): the same launches and pool, the
+    same costs rank by rank (equal bits where every sum is exact); among
+    assignments of equal cost the order and the choice may differ.  Measured
+    (MI355X): an assignment of a 250 x 256 instance costs 2.5x to
+    2.85x less and a 60 x 64 one 1.6x to 2.8x less, which is what they cost at
+    256 x 256 and 64 x 64; a square instance is the same work either way (0.98x
+    to 1.03x).  Not measured with far fewer rows than columns, where
+    resolve_batched_free_rows itself loses: leave it off there."""
     _kbest_dtype(C)
     if int(k) != k or k < 1:
         raise ValueError(f"k must be an integer >= 1, got {k!r}")
@@ -529,7 +634,7 @@ def kbest_batched(C: torch.Tensor, k: int, shapes=None, maximize: bool = False):
     costs = torch.empty((p.B, k), dtype=torch.float64, device=dev)
     count = torch.empty(p.B, dtype=torch.int32, device=dev)
     shape_dev = p.shapes_on(dev) if p.shapes is not None else None
-    rc = getattr(L, "lsap_kbest_" + DTYPE_SUFFIX[C.dtype])(
+    rc = getattr(L, ("lsap_kbest_fr_" if free_rows else "lsap_kbest_") + DTYPE_SUFFIX[C.dtype])(
         _p(C), p.nr, p.nc, p.B, _p(shape_dev), k, _p(cols), _p(costs), _p(count), _p(work), nbytes,
         _lib.SH_COMPAT_TIEBREAK, current_stream_handle(dev))
     _lib.check(rc, "lsap_kbest")
@@ -540,13 +645,15 @@ def kbest_batched(C: torch.Tensor, k: int, shapes=None, maximize: bool = False):
     return cols, costs, count
 
 
-def kbest_assignments(cost_matrix, k: int, maximize: bool = False, device: int | str = 0):
+def kbest_assignments(cost_matrix, k: int, maximize: bool = False, device: int | str = 0,
+                      free_rows: bool = False):
     """The k best assignments of one matrix -> (col_inds int64 [m, nr], costs
     float64 [m]), m <= k the number that exist, best first.  col_inds[r, i] is
     the column of row i in the rank-r assignment, -1 for a row a tall matrix
     leaves out.  The matrix is solved in float64 (float32 input at its own
     width); +inf forbids a pair (under maximize: -inf), NaN and -inf (under
-    maximize: +inf) raise ValueError as in linear_sum_assignment."""
+    maximize: +inf) raise ValueError as in linear_sum_assignment.  free_rows:
+    kbest_batched's."""
     C = np.asarray(cost_matrix)
     if C.ndim != 2:
         raise ValueError("expected a matrix (2-D array), got a %r array" % (C.shape,))
@@ -563,7 +670,7 @@ def kbest_assignments(cost_matrix, k: int, maximize: bool = False, device: int |
     if np.isnan(C).any() or (C == bad).any():
         raise ValueError("matrix contains invalid numeric entries")
     Ct = torch.from_numpy(np.ascontiguousarray(C)).to(device_of(device))
-    cols, costs, count = kbest_batched(Ct.unsqueeze(0), k, maximize=maximize)
+    cols, costs, count = kbest_batched(Ct.unsqueeze(0), k, maximize=maximize, free_rows=free_rows)
     m = int(count[0])
     return cols[0, :m].cpu().numpy().astype(np.int64), costs[0, :m].cpu().numpy()
 
