@@ -932,6 +932,78 @@ int lsap_kbest_csr_f32(const int64_t *d_indptr, const int32_t *d_indices, const 
                        void *d_work, size_t work_bytes, unsigned flags, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Free rows on sparse (CSR) costs: the lsap_warm_fr_,
+ * lsap_murty_children_fr_ and lsap_kbest_fr_ entries on the densification (the
+ * stored values, +inf elsewhere; a stored +inf counts as a missing entry),
+ * without densifying, float64 and float32 values.  A wide instance (nr_b <
+ * nc_b) is solved as the PADDED square problem of lsap_warm_fr_: nc_b - nr_b
+ * virtual rows that cost 0 in every column, never stored and never read -- the
+ * virtual rows read nothing but d_v, so they cost no entry of the CSR and can
+ * never make an instance infeasible.  The batch is lsap_solve_csr_'s: one CSR
+ * of B * nr rows, canonical rows, d_shape for ragged corners, d_work of
+ * lsap_csr_work_bytes (8-byte aligned), and its memory-safety rule (an index
+ * outside [0, nc_b) never forms an address; reads of d_indices and d_data for
+ * row r stay inside [d_indptr[r], d_indptr[r + 1])).
+ *
+ * lsap_warm_fr_csr_*: what lsap_warm_fr_f64 / _f32 return for the densification
+ *   with the same d_shape, previous d_col and previous d_v: d_col and both
+ *   counts of d_kept [B x 2] the same integers, d_cost the same bits, d_u, d_v
+ *   and d_theta [B] equal by value (a zero may carry the other sign, as on
+ *   lsap_warm_csr_).  The duals are the padded problem's as the solver left
+ *   them, with no shift (lsap_warm_fr_'s float rule), so they are the input of
+ *   this entry's next call.  The previous state is data and may be anything; a
+ *   previously chosen pair that is no longer stored is dropped, a new entry is
+ *   an edge.  An instance without a perfect matching of its REAL rows gets -1,
+ *   cost 0, NaN duals in its live slots and NaN theta.  nr_b == nc_b: the
+ *   instance is lsap_warm_csr_'s, and theta is still reported.  1 <= nr <= nc
+ *   <= SH_MAX_N_LARGE.  Three launches: the pass over the CSR, the first pass
+ *   of lsap_warm_fr_ on the stored entries, and the continuation chosen by nc
+ *   alone.  SH_FLAG_BUILD_ONLY stops after the second launch and leaves the
+ *   start state: the kept real pairs, u of the real rows, v, both counts and
+ *   the start state's theta.  SH_FLAG_F64_MW / SH_FLAG_F64_SW are ignored.
+ *   SH_ERR_ARGS as on lsap_warm_csr_; d_kept and d_theta are nullable.
+ *
+ * lsap_murty_children_fr_csr_* and lsap_kbest_fr_csr_*: what
+ *   lsap_murty_children_fr_* and lsap_kbest_fr_* return for the densification:
+ *   col, kept, cols and count the same integers, cost and costs the same bits,
+ *   the same rank order, tie rule and -1 / +inf tail, u and v equal by value.
+ *   1 <= nr <= nc <= SH_MAX_N.  A node stays (col [nr], v [nc], p, F, cost);
+ *   the virtual pairs are recomputed from (col, v), with theta taken over the
+ *   columns no row < t forces.  d_work is lsap_csr_work_bytes on the children
+ *   entry and lsap_kbest_csr_work_bytes on the k-best entry, unchanged; a
+ *   k-best call is 3 k launches whatever the data, and rank 0 is
+ *   lsap_solve_csr_'s solve with duals.  Arguments, flags and SH_ERR_ARGS are
+ *   those of lsap_murty_children_csr_* and lsap_kbest_csr_*.
+ *
+ * Every check is made on the host before any device call; nothing is allocated
+ * and nothing synchronises.  B == 0 is a no-op after the checks.
+ * ------------------------------------------------------------------------ */
+int lsap_warm_fr_csr_f64(const int64_t *d_indptr, const int32_t *d_indices, const double *d_data, int nr, int nc,
+                         int B, const int32_t *d_shape, int32_t *d_col, double *d_cost, double *d_u, double *d_v,
+                         int32_t *d_kept, double *d_theta, void *d_work, size_t work_bytes, unsigned flags,
+                         void *stream);
+int lsap_warm_fr_csr_f32(const int64_t *d_indptr, const int32_t *d_indices, const float *d_data, int nr, int nc,
+                         int B, const int32_t *d_shape, int32_t *d_col, double *d_cost, double *d_u, double *d_v,
+                         int32_t *d_kept, double *d_theta, void *d_work, size_t work_bytes, unsigned flags,
+                         void *stream);
+int lsap_murty_children_fr_csr_f64(const int64_t *d_indptr, const int32_t *d_indices, const double *d_data, int nr,
+                                   int nc, int B, const int32_t *d_shape, const int32_t *d_pcol,
+                                   const double *d_pv, const int32_t *d_p, const uint64_t *d_forb, int32_t *d_col,
+                                   double *d_cost, double *d_u, double *d_v, int32_t *d_kept, void *d_work,
+                                   size_t work_bytes, unsigned flags, void *stream);
+int lsap_murty_children_fr_csr_f32(const int64_t *d_indptr, const int32_t *d_indices, const float *d_data, int nr,
+                                   int nc, int B, const int32_t *d_shape, const int32_t *d_pcol,
+                                   const double *d_pv, const int32_t *d_p, const uint64_t *d_forb, int32_t *d_col,
+                                   double *d_cost, double *d_u, double *d_v, int32_t *d_kept, void *d_work,
+                                   size_t work_bytes, unsigned flags, void *stream);
+int lsap_kbest_fr_csr_f64(const int64_t *d_indptr, const int32_t *d_indices, const double *d_data, int nr, int nc,
+                          int B, const int32_t *d_shape, int k, int32_t *d_cols, double *d_costs,
+                          int32_t *d_count, void *d_work, size_t work_bytes, unsigned flags, void *stream);
+int lsap_kbest_fr_csr_f32(const int64_t *d_indptr, const int32_t *d_indices, const float *d_data, int nr, int nc,
+                          int B, const int32_t *d_shape, int k, int32_t *d_cols, double *d_costs,
+                          int32_t *d_count, void *d_work, size_t work_bytes, unsigned flags, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Certificates on the CSR itself: optimality of a sparse solve, and a proof
  * that a sparsity pattern has, or has not, a perfect matching of its rows.
  * Nothing is densified.  Batch layout, d_shape, sizes, canonical rows and the

@@ -1491,6 +1491,53 @@ int launch_warm_csr(const int64_t *indptr, const int32_t *indices, const S *data
   return SH_OK;
 }
 
+// The lsap_warm_fr_csr_ entries (DESIGN.md §23): launch_warm_csr's checks, its
+// three launches and its table, with fcsr_prep_kernel and the fcsr_
+// continuations.  The continuations hold the padded problem's n rows: their LDS
+// is the square footprint (plus frow_virtual_rows' 12 static bytes a wave).
+static_assert(lsap_f64_mw_lds(SH_MAX_N_LARGE, SH_MAX_N_LARGE, 8, 12) + 8 * 12 <= LDS_NO_ATTR);
+static_assert(lsap_f64_lds(WAVE) <= LDS_NO_ATTR);
+
+template <typename S>
+int launch_warm_fr_csr(const int64_t *indptr, const int32_t *indices, const S *data, int nr, int n, int B,
+                       const int32_t *shape, int32_t *col, double *cost, double *du, double *dv, int32_t *kept,
+                       double *theta, void *work, size_t work_bytes, unsigned flags, hipStream_t s) {
+  HIP_TRY_RC(check_lsap_args(nr, n, B, col, SH_MAX_N_LARGE));
+  if (!indptr && B > 0) return fail(SH_ERR_ARGS, "null indptr");
+  if ((!du || !dv) && B > 0) return fail(SH_ERR_ARGS, "null u or v");
+  if (work_bytes < lsap_csr_work_bytes(nr, n, B) || (B > 0 && !work))
+    return fail(SH_ERR_ARGS, "work buffer smaller than lsap_csr_work_bytes");
+  if ((uintptr_t)work % 8) return fail(SH_ERR_ARGS, "work buffer not 8-byte aligned");
+  const int64_t rows = (int64_t)B * nr;
+  constexpr int PREP_ROWS = CSR_PREP_WG / WAVE;
+  if ((rows + PREP_ROWS - 1) / PREP_ROWS > INT32_MAX) return fail(SH_ERR_ARGS, "B * nr too large");
+  if (B == 0) return SH_OK;
+  uint64_t *mask = (uint64_t *)work;
+  uint16_t *pre = (uint16_t *)(mask + csr_words(nr, n, B));
+  hipLaunchKernelGGL(lsap_csr_prep_kernel, dim3((unsigned)((rows + PREP_ROWS - 1) / PREP_ROWS)), dim3(CSR_PREP_WG),
+                     0, s, indptr, indices, nr, n, rows, shape, mask, pre);
+  hipLaunchKernelGGL((fcsr_prep_kernel<S>), dim3(B), dim3(PREP_WG), warm_prep_lds(nr, n), s, indptr, data, mask, pre,
+                     nr, n, shape, col, du, dv, kept, theta);
+  HIP_TRY(hipGetLastError());
+  if (flags & SH_FLAG_BUILD_ONLY) return SH_OK;
+  auto mw = [&](auto cfg) {
+    using C_ = decltype(cfg);
+    hipLaunchKernelGGL((fcsr_mw_kernel<C_::NW, C_::K, S, C_::FB>), dim3(B), dim3(C_::NW * WAVE),
+                       lsap_f64_mw_lds(n, n, C_::NW, C_::FB), s, indptr, data, mask, pre, nr, n, shape, col, cost, du,
+                       dv, theta);
+    return SH_OK;
+  };
+  if (n > SH_MAX_N) with_large_f64_cfg(n, mw);
+  else if (n > 512) mw(BigCfg<4, 4, 10>{});
+  else if (n > 256) mw(BigCfg<4, 2, 10>{});
+  else if (n > WAVE) mw(BigCfg<4, 1, 10>{});
+  else
+    hipLaunchKernelGGL((fcsr_kernel<1, S>), dim3(B), dim3(WAVE), lsap_f64_lds(n), s, indptr, data, mask, pre, nr, n,
+                       shape, col, cost, du, dv, theta);
+  HIP_TRY(hipGetLastError());
+  return SH_OK;
+}
+
 // ---------------------------------------------------------------------------
 // k-best on the CSR (DESIGN.md §21): the lsap_murty_children_csr_ and
 // lsap_kbest_csr_ entries.  launch_mcsr is launch_murty behind the masking CSR
@@ -1500,23 +1547,37 @@ int launch_warm_csr(const int64_t *indptr, const int32_t *indices, const S *data
 // ---------------------------------------------------------------------------
 static_assert(mcsr_prep_lds(SH_MAX_N, SH_MAX_N) <= LDS_NO_ATTR);
 
+// fr (the _fr_csr_ entries, DESIGN.md §23): the free-rows kernels, whose
+// continuations hold the padded problem's n rows.
 template <typename S>
 int launch_mcsr(const int64_t *indptr, const S *data, const uint64_t *mask, const uint16_t *pre, int nr, int n, int B,
                 const int32_t *shape, const int32_t *pcol, const double *pv, const int32_t *pp, const uint64_t *forb,
-                int32_t *col, double *cost, double *du, double *dv, int32_t *kept, uint64_t *forb_out,
+                int32_t *col, double *cost, double *du, double *dv, int32_t *kept, uint64_t *forb_out, bool fr,
                 hipStream_t s) {
   const dim3 grid((unsigned)((size_t)B * nr));
-  hipLaunchKernelGGL((mcsr_prep_kernel<S>), grid, dim3(PREP_WG), mcsr_prep_lds(nr, n), s, indptr, data, mask, pre, nr,
-                     n, shape, pcol, pv, pp, forb, col, du, dv, kept, forb_out);
+  if (fr)
+    hipLaunchKernelGGL((fcsr_mprep_kernel<S>), grid, dim3(PREP_WG), mcsr_prep_lds(nr, n), s, indptr, data, mask, pre,
+                       nr, n, shape, pcol, pv, pp, forb, col, du, dv, kept, forb_out);
+  else
+    hipLaunchKernelGGL((mcsr_prep_kernel<S>), grid, dim3(PREP_WG), mcsr_prep_lds(nr, n), s, indptr, data, mask, pre,
+                       nr, n, shape, pcol, pv, pp, forb, col, du, dv, kept, forb_out);
   auto mw = [&](auto cfg) {
     using C_ = decltype(cfg);
-    hipLaunchKernelGGL((mcsr_f64_mw_kernel<C_::NW, C_::K, S, C_::FB>), grid, dim3(C_::NW * WAVE),
-                       lsap_f64_mw_lds(nr, n, C_::NW, C_::FB), s, indptr, data, mask, pre, nr, n, shape, pcol, pp, forb,
-                       col, cost, du, dv);
+    if (fr)
+      hipLaunchKernelGGL((fcsr_mf64_mw_kernel<C_::NW, C_::K, S, C_::FB>), grid, dim3(C_::NW * WAVE),
+                         lsap_f64_mw_lds(n, n, C_::NW, C_::FB), s, indptr, data, mask, pre, nr, n, shape, pcol, pp,
+                         forb, col, cost, du, dv);
+    else
+      hipLaunchKernelGGL((mcsr_f64_mw_kernel<C_::NW, C_::K, S, C_::FB>), grid, dim3(C_::NW * WAVE),
+                         lsap_f64_mw_lds(nr, n, C_::NW, C_::FB), s, indptr, data, mask, pre, nr, n, shape, pcol, pp,
+                         forb, col, cost, du, dv);
   };
   if (n > 512) mw(BigCfg<4, 4, 10>{});
   else if (n > 256) mw(BigCfg<4, 2, 10>{});
   else if (n > WAVE) mw(BigCfg<4, 1, 10>{});
+  else if (fr)
+    hipLaunchKernelGGL((fcsr_mf64_kernel<1, S>), grid, dim3(WAVE), lsap_f64_lds(n), s, indptr, data, mask, pre, nr, n,
+                       shape, pcol, pp, forb, col, cost, du, dv);
   else
     hipLaunchKernelGGL((mcsr_f64_kernel<1, S>), grid, dim3(WAVE), lsap_f64_lds(nr), s, indptr, data, mask, pre, nr, n,
                        shape, pcol, pp, forb, col, cost, du, dv);
@@ -1538,7 +1599,7 @@ template <typename S>
 int murty_children_csr(const int64_t *indptr, const int32_t *indices, const S *data, int nr, int n, int B,
                        const int32_t *shape, const int32_t *pcol, const double *pv, const int32_t *pp,
                        const uint64_t *forb, int32_t *col, double *cost, double *du, double *dv, int32_t *kept,
-                       void *work, size_t work_bytes, hipStream_t s) {
+                       void *work, size_t work_bytes, bool fr, hipStream_t s) {
   HIP_TRY_RC(check_murty_sizes(nr, n, B));
   if (B > 0 && (!indptr || !pcol || !pv || !pp || !forb)) return fail(SH_ERR_ARGS, "null indptr, pcol, pv, p or forb");
   if (B > 0 && (!col || !cost || !du || !dv)) return fail(SH_ERR_ARGS, "null col, cost, u or v");
@@ -1550,7 +1611,7 @@ int murty_children_csr(const int64_t *indptr, const int32_t *indices, const S *d
   uint16_t *pre = (uint16_t *)(mask + csr_words(nr, n, B));
   launch_csr_prep(indptr, indices, nr, n, B, shape, mask, pre, s);
   return launch_mcsr(indptr, data, mask, pre, nr, n, B, shape, pcol, pv, pp, forb, col, cost, du, dv, kept,
-                     (uint64_t *)nullptr, s);
+                     (uint64_t *)nullptr, fr, s);
 }
 
 // d_work of lsap_kbest_csr_: the dense pool (kbest_carve), then the words of
@@ -1569,7 +1630,7 @@ size_t kbest_csr_bytes(int nr, int nc, int B, int k, size_t *pool_bytes) {
 template <typename S>
 int kbest_csr(const int64_t *indptr, const int32_t *indices, const S *data, int nr, int n, int B,
               const int32_t *shape, int k, int32_t *cols, double *costs, int32_t *count, void *work,
-              size_t work_bytes, unsigned flags, hipStream_t s) {
+              size_t work_bytes, unsigned flags, bool fr, hipStream_t s) {
   HIP_TRY_RC(check_murty_sizes(nr, n, B));
   if (k < 1) return fail(SH_ERR_ARGS, "k < 1");
   if ((uint64_t)k * (uint64_t)nr > (uint64_t)INT32_MAX) return fail(SH_ERR_ARGS, "k * nr exceeds 2^31 - 1");
@@ -1593,7 +1654,7 @@ int kbest_csr(const int64_t *indptr, const int32_t *indices, const S *data, int 
     if (r == k - 1) break;
     HIP_TRY_RC(launch_mcsr(indptr, data, mask, pre, nr, n, B, shape, P.stage_col, P.stage_v, P.stage_p, P.stage_forb,
                            P.col + r * bn * nr, P.cost + r * bn, P.u, P.v + r * bn * n, (int32_t *)nullptr,
-                           P.forb + r * bn * W, s));
+                           P.forb + r * bn * W, fr, s));
   }
   HIP_TRY(hipGetLastError());
   return SH_OK;
@@ -1922,25 +1983,41 @@ SH_WARM_CSR_ENTRY(f64, double)
 SH_WARM_CSR_ENTRY(f32, float)
 #undef SH_WARM_CSR_ENTRY
 
-// The k-best entries of a CSR value type (murty_children_csr, kbest_csr).
-#define SH_KBEST_CSR_ENTRIES(SUF, CT)                                                                             \
-  int lsap_murty_children_csr_##SUF(const int64_t *d_indptr, const int32_t *d_indices, const CT *d_data, int nr,  \
-                                    int nc, int B, const int32_t *d_shape, const int32_t *d_pcol,                 \
-                                    const double *d_pv, const int32_t *d_p, const uint64_t *d_forb,               \
-                                    int32_t *d_col, double *d_cost, double *d_u, double *d_v, int32_t *d_kept,    \
-                                    void *d_work, size_t work_bytes, unsigned flags, void *stream) {              \
-    (void)flags;                                                                                                  \
-    return murty_children_csr(d_indptr, d_indices, d_data, nr, nc, B, d_shape, d_pcol, d_pv, d_p, d_forb, d_col,  \
-                              d_cost, d_u, d_v, d_kept, d_work, work_bytes, (hipStream_t)stream);                 \
-  }                                                                                                               \
-  int lsap_kbest_csr_##SUF(const int64_t *d_indptr, const int32_t *d_indices, const CT *d_data, int nr, int nc,   \
-                           int B, const int32_t *d_shape, int k, int32_t *d_cols, double *d_costs,                \
-                           int32_t *d_count, void *d_work, size_t work_bytes, unsigned flags, void *stream) {     \
-    return kbest_csr(d_indptr, d_indices, d_data, nr, nc, B, d_shape, k, d_cols, d_costs, d_count, d_work,        \
-                     work_bytes, flags, (hipStream_t)stream);                                                     \
+// ... and with free rows (launch_warm_fr_csr): d_kept [B x 2] and d_theta [B]
+// are out and nullable.
+#define SH_WARM_FR_CSR_ENTRY(SUF, CT)                                                                             \
+  int lsap_warm_fr_csr_##SUF(const int64_t *d_indptr, const int32_t *d_indices, const CT *d_data, int nr, int nc, \
+                             int B, const int32_t *d_shape, int32_t *d_col, double *d_cost, double *d_u,          \
+                             double *d_v, int32_t *d_kept, double *d_theta, void *d_work, size_t work_bytes,      \
+                             unsigned flags, void *stream) {                                                      \
+    return launch_warm_fr_csr(d_indptr, d_indices, d_data, nr, nc, B, d_shape, d_col, d_cost, d_u, d_v, d_kept,   \
+                              d_theta, d_work, work_bytes, flags, (hipStream_t)stream);                           \
   }
-SH_KBEST_CSR_ENTRIES(f64, double)
-SH_KBEST_CSR_ENTRIES(f32, float)
+SH_WARM_FR_CSR_ENTRY(f64, double)
+SH_WARM_FR_CSR_ENTRY(f32, float)
+#undef SH_WARM_FR_CSR_ENTRY
+
+// The k-best entries of a CSR value type (murty_children_csr, kbest_csr); FR: with free rows.
+#define SH_KBEST_CSR_ENTRIES(NAME, CT, FR)                                                                         \
+  int lsap_murty_children_##NAME(const int64_t *d_indptr, const int32_t *d_indices, const CT *d_data, int nr,      \
+                                 int nc, int B, const int32_t *d_shape, const int32_t *d_pcol,                     \
+                                 const double *d_pv, const int32_t *d_p, const uint64_t *d_forb,                   \
+                                 int32_t *d_col, double *d_cost, double *d_u, double *d_v, int32_t *d_kept,        \
+                                 void *d_work, size_t work_bytes, unsigned flags, void *stream) {                  \
+    (void)flags;                                                                                                   \
+    return murty_children_csr(d_indptr, d_indices, d_data, nr, nc, B, d_shape, d_pcol, d_pv, d_p, d_forb, d_col,   \
+                              d_cost, d_u, d_v, d_kept, d_work, work_bytes, FR, (hipStream_t)stream);              \
+  }                                                                                                                \
+  int lsap_kbest_##NAME(const int64_t *d_indptr, const int32_t *d_indices, const CT *d_data, int nr, int nc,       \
+                        int B, const int32_t *d_shape, int k, int32_t *d_cols, double *d_costs,                    \
+                        int32_t *d_count, void *d_work, size_t work_bytes, unsigned flags, void *stream) {         \
+    return kbest_csr(d_indptr, d_indices, d_data, nr, nc, B, d_shape, k, d_cols, d_costs, d_count, d_work,         \
+                     work_bytes, flags, FR, (hipStream_t)stream);                                                  \
+  }
+SH_KBEST_CSR_ENTRIES(csr_f64, double, false)
+SH_KBEST_CSR_ENTRIES(csr_f32, float, false)
+SH_KBEST_CSR_ENTRIES(fr_csr_f64, double, true)
+SH_KBEST_CSR_ENTRIES(fr_csr_f32, float, true)
 #undef SH_KBEST_CSR_ENTRIES
 
 size_t lsap_kbest_csr_work_bytes(int nr, int nc, int B, int k) {

@@ -9568,6 +9568,536 @@ __global__ __launch_bounds__(NW * WAVE) void frow_mf64_mw_kernel(const S *C, int
   }
 }
 
+// ---------------------------------------------------------------------------
+// Free rows on CSR costs (the lsap_warm_fr_csr_, lsap_murty_children_fr_csr_
+// and lsap_kbest_fr_csr_ entries): the free-rows kernels above
+// on the densification (the stored values, +inf elsewhere), after
+// lsap_csr_prep_kernel, as the warm_csr_ and mcsr_ kernels stand beside the
+// dense ones.  The virtual rows nr .. n-1 read nothing but v.
+//   fcsr_prep_kernel   warm_csr_prep_kernel without steps 3 and 6, whatever nr,
+//     then frow_prep_kernel's tail: theta and the count of virtual pairs
+//   fcsr_kernel / fcsr_mw_kernel   warm_csr_kernel's and warm_csr_mw_kernel's
+//     bodies on n rows behind FreeRows<CsrLoader>, with frow_f64_kernel's and
+//     frow_f64_mw_kernel's entry and exit
+//   fcsr_mprep_kernel   mcsr_prep_kernel without steps 3 and 6
+//   fcsr_mf64_kernel / fcsr_mf64_mw_kernel   mcsr_f64_kernel's and
+//     mcsr_f64_mw_kernel's bodies on n rows behind FreeRowsMaskedCsr
+// Memory safety is CsrLoader's: `indices` is not read, a value's address comes
+// from the prep's words alone, a previous col is compared or bounds-checked
+// into LDS and never forms a global address, and v is indexed under a set bit
+// or by a column below n.
+// ---------------------------------------------------------------------------
+template <typename S>
+__global__ __launch_bounds__(PREP_WG) void fcsr_prep_kernel(const int64_t *indptr, const S *data,
+                                                            const uint64_t *mask, const uint16_t *pre, int NR,
+                                                            int NC, const int32_t *shape, int32_t *col, double *du,
+                                                            double *dv, int32_t *kept, double *theta) {
+  using T = double;
+  constexpr int NW = PREP_WG / WAVE;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ int s_bad, s_kept, s_free;
+  __shared__ T s_part[NW];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  int nr, n;  // live rows and columns (see lsap_i64_kernel)
+  if (!lsap_shape(shape, b, NR, NC, nr, n)) {
+    lsap_no_instance<PREP_WG>(col, (T *)nullptr, b, NR, NC, du, dv);
+    if (tid == 0 && kept) kept[2 * (size_t)b] = kept[2 * (size_t)b + 1] = 0;
+    if (tid == 0 && theta) theta[b] = 0;
+    return;
+  }
+  size_t off = 0;
+  T *u_l;
+  int16_t *r4c_l, *c4r_l, *q_l;  // (warm_prep_kernel's list; the queue is not used)
+  WARM_PREP_LDS(LDS_CARVE, nr, n)
+  (void)q_l;
+  int32_t *claim = (int32_t *)u_l;
+  int32_t *col_b = col + (size_t)b * NR;
+  T *u_b = du + (size_t)b * NR, *v_b = dv + (size_t)b * NC;
+  const int nw = (NC + 63) >> 6;
+  const CsrLoader<1, 1, S> ld{indptr + (size_t)b * NR, data, mask + (size_t)b * NR * nw, pre + (size_t)b * NR * nw,
+                              nw};
+  const T INF = VT<T>::inf();
+  if (tid == 0) s_bad = s_kept = s_free = 0;
+  for (int j = tid; j < n; j += PREP_WG) {  // 1
+    v_b[j] = warm_clean_v(v_b[j]);
+    claim[j] = INT32_MAX;
+  }
+  __syncthreads();
+  for (int i = tid; i < nr; i += PREP_WG) {  // 2
+    const int j = col_b[i];
+    const bool ok = j >= 0 && j < n;
+    c4r_l[i] = ok ? (int16_t)j : (int16_t)-1;
+    if (ok) atomicMin(&claim[j], i);
+  }
+  __syncthreads();
+  for (int j = tid; j < n; j += PREP_WG) {
+    const int r = claim[j];
+    r4c_l[j] = (r == INT32_MAX) ? (int16_t)-1 : (int16_t)r;
+  }
+  __syncthreads();  // (the claims are read: u_l may be written)
+  for (int i = w; i < nr; i += NW) {  // 4 and 5 (warm_csr_prep_kernel's walk)
+    const size_t r = (size_t)i * nw;
+    const S *row = ld.data + ld.indptr[i];
+    const int ql = min(lane, nw - 1);  // (a lane past the row's last word holds an empty one)
+    const uint64_t mw = (lane < nw) ? ld.mask[r + ql] : 0;
+    const int pw = ld.pre[r + ql];
+    uint64_t words = __ballot(mw != 0);  // the words that hold an entry
+    T m = INF;
+    while (words) {
+      const int q = __builtin_ctzll(words);
+      words &= words - 1;
+      const uint64_t mq = readlane_u64(mw, q);
+      const int pq = __builtin_amdgcn_readlane(pw, q);
+      if ((mq >> lane) & 1) {
+        const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mq >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mq, 0u));
+        const T x = cert_sub(widen_f64(row[pq + rank]), v_b[64 * q + lane]);
+        m = (x < m) ? x : m;
+      }
+    }
+    m = wave_min(m);
+    if (lane == 0) {
+      u_l[i] = m;
+      if (!(m < INF)) s_bad = 1;
+      const int j = c4r_l[i];
+      if (j >= 0) {
+        const bool mine = r4c_l[j] == i;  // (only row r4c_l[j] ever writes that slot)
+        if (!(mine && cert_sub(ld.at(i, j), v_b[j]) == m)) {
+          c4r_l[i] = -1;
+          if (mine) r4c_l[j] = -1;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const bool bad = s_bad;
+  // theta and the virtual pairs that frow_virtual_rows will keep
+  const T m = frow_neg_theta<NW>(v_b, n, s_part);
+  int fr = 0;
+  for (int j = tid; j < n; j += PREP_WG) fr += r4c_l[j] < 0 && cert_sub((T)0, v_b[j]) == m;
+  int k = 0;
+  for (int i = tid; i < NR; i += PREP_WG) {
+    const int c = (i < nr && !bad) ? c4r_l[i] : -1;
+    col_b[i] = c;
+    k += c >= 0;
+    u_b[i] = (i < nr) ? (bad ? __builtin_nan("") : u_l[i]) : 0.0;
+  }
+  __syncthreads();  // (every thread has read v: the NaNs below may be written)
+  for (int j = tid; j < NC; j += PREP_WG) {
+    if (j >= n) v_b[j] = 0;
+    else if (bad) v_b[j] = __builtin_nan("");
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    k += __shfl_xor(k, o, WAVE);
+    fr += __shfl_xor(fr, o, WAVE);
+  }
+  if (lane == 0 && k) atomicAdd(&s_kept, k);
+  if (lane == 0 && fr) atomicAdd(&s_free, fr);
+  __syncthreads();
+  if (tid == 0) {
+    if (kept) {
+      kept[2 * (size_t)b] = s_kept;
+      kept[2 * (size_t)b + 1] = bad ? 0 : min(s_free, n - nr);
+    }
+    if (theta) theta[b] = bad ? __builtin_nan("") : cert_sub((T)0, m);
+  }
+}
+
+// warm_csr_kernel on the padded problem: one wave, n <= 64, lane j owns column j.
+template <int K, typename S>
+__global__ __launch_bounds__(WAVE) void fcsr_kernel(const int64_t *indptr, const S *data, const uint64_t *mask,
+                                                    const uint16_t *pre, int NR, int NC, const int32_t *shape,
+                                                    int32_t *col, double *cost, double *du, double *dv,
+                                                    double *theta) {
+  static_assert(K == 1, "the virtual rows' ranks are one ballot");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int b = blockIdx.x;
+  const int lane = threadIdx.x;
+  int nr, n;
+  if (warm_f64_done(shape, b, NR, NC, nr, n, du, cost)) return;
+  size_t off = 0;
+  double *u_l;
+  int16_t *c4r_l;
+  LSAP_F64_LDS(LDS_CARVE, n)
+  const double *v_b = dv + (size_t)b * NC;
+  for (int i = lane; i < nr; i += WAVE) {
+    u_l[i] = du[(size_t)b * NR + i];
+    c4r_l[i] = (int16_t)col[(size_t)b * NR + i];
+  }
+  __syncthreads();
+  {  // the virtual rows (frow_f64_kernel's block)
+    bool taken = false;
+    for (int i = 0; i < nr; ++i) taken |= c4r_l[i] == lane;
+    const double d = (lane < n) ? 0.0 - v_b[lane] : __builtin_inf();
+    const double m = wave_min(d);
+    const bool f = lane < n && !taken && d == m;
+    const uint64_t bal = __ballot(f);
+    const int rank = __popcll(bal & ((1ull << lane) - 1ull));
+    for (int i = nr + lane; i < n; i += WAVE) {
+      u_l[i] = m;
+      c4r_l[i] = -1;
+    }
+    __syncthreads();
+    if (f && rank < n - nr) c4r_l[nr + rank] = (int16_t)lane;
+    __syncthreads();
+  }
+  int64_t steps = 0;
+  const int nw = (NC + 63) >> 6;
+  using CL = FreeRows<CsrLoader<1, K, S>>;
+  WithDuals<CL, double> ld{
+      CL{{indptr + (size_t)b * NR, data, mask + (size_t)b * NR * nw, pre + (size_t)b * NR * nw, nw}, nr}};
+  ld.dv = dv + (size_t)b * NC;
+  const int st = sap_solve<K, double, true, true>(n, n, ld, u_l, c4r_l, steps);
+  __syncthreads();
+  duals_store_f64<WAVE>(du, dv, u_l, st, b, NR, NC, nr, n);
+  if (theta) {
+    const double m = wave_min((lane < n) ? 0.0 - v_b[lane] : __builtin_inf());
+    if (lane == 0) theta[b] = (st == 0) ? 0.0 - m : __builtin_nan("");
+  }
+  double acc = 0;
+  for (int i = lane; i < NR; i += WAVE) {
+    const bool live = st == 0 && i < nr;
+    const int cidx = live ? c4r_l[i] : -1;
+    col[(size_t)b * NR + i] = cidx;
+    if (live && cost) acc += ld.at(i, cidx);
+  }
+  if (cost) {  // (lsap_f64_kernel's order)
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, WAVE);
+    if (lane == 0) cost[b] = acc;
+  }
+}
+
+// ... and warm_csr_mw_kernel.
+template <int NW, int K, typename S, int FB>
+__global__ __launch_bounds__(NW * WAVE) void fcsr_mw_kernel(const int64_t *indptr, const S *data,
+                                                            const uint64_t *mask, const uint16_t *pre, int NR,
+                                                            int NC, const int32_t *shape, int32_t *col,
+                                                            double *cost, double *du, double *dv, double *theta) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ double s_part[NW];
+  __shared__ int s_cnt[NW];
+  constexpr int WG = NW * WAVE;
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  int nr, n;
+  if (warm_f64_done(shape, b, NR, NC, nr, n, du, cost)) return;
+  size_t off = 0;
+  SolveLdsF64 Sl;
+  LSAP_F64_MW_LDS(LDS_CARVE, n, n, NW, FB)
+  const double *v_b = dv + (size_t)b * NC;
+  for (int i = tid; i < n; i += WG) {
+    if (i < nr) {
+      Sl.u[i] = du[(size_t)b * NR + i];
+      Sl.c4r[i] = (int16_t)col[(size_t)b * NR + i];
+    }
+    Sl.r4c[i] = -1;
+    Sl.path[i] = -1;
+  }
+  __syncthreads();
+  for (int i = tid; i < nr; i += WG) {
+    const int j = Sl.c4r[i];
+    if (j >= 0) Sl.r4c[j] = (int16_t)i;
+  }
+  __syncthreads();
+  frow_virtual_rows<NW>(nr, n, v_b, Sl.u, Sl.c4r, Sl.r4c, s_part, s_cnt);
+  const int nw = (NC + 63) >> 6;
+  using CL = FreeRows<CsrLoader<NW, K, S>>;
+  WithDuals<CL, double> ld{
+      CL{{indptr + (size_t)b * NR, data, mask + (size_t)b * NR * nw, pre + (size_t)b * NR * nw, nw}, nr}};
+  ld.dv = dv + (size_t)b * NC;
+  const int st = sap_solve_mw_f64<NW, K, true, FB, true>(n, n, ld, Sl);
+  __syncthreads();
+  if (st == 0) {  // (block-uniform; before duals_store_f64 could write NaN over v)
+    const double m = frow_neg_theta<NW>(v_b, n, s_part);
+    if (tid == 0 && theta) theta[b] = 0.0 - m;
+  } else if (tid == 0 && theta) {
+    theta[b] = __builtin_nan("");
+  }
+  duals_store_f64<WG>(du, dv, Sl.u, st, b, NR, NC, nr, n);
+  for (int i = tid; i < NR; i += WG) col[(size_t)b * NR + i] = (st == 0 && i < nr) ? Sl.c4r[i] : -1;
+  if (cost && tid < WAVE) {
+    double acc = 0;
+    for (int i = tid; i < NR; i += WAVE)
+      if (st == 0 && i < nr) acc += ld.at(i, Sl.c4r[i]);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, WAVE);
+    if (tid == 0) cost[b] = acc;
+  }
+}
+
+// MaskedCsrLoader on the padded M_t: a virtual row (a row > t) is 0, and +inf
+// on the columns the rows < t force (FreeRowsMurty's rule); it issues no load.
+template <int NW, int K, typename S>
+struct FreeRowsMaskedCsr : MaskedCsrLoader<NW, K, S> {
+  int nr_real;
+  __device__ __forceinline__ void load(int i, double (&c)[K]) const {
+    if (i < nr_real) {
+      MaskedCsrLoader<NW, K, S>::load(i, c);
+    } else {
+#pragma unroll
+      for (int k = 0; k < K; ++k) c[k] = ((this->forced >> k) & 1u) ? __builtin_inf() : 0.0;
+    }
+  }
+};
+
+// mcsr_prep_kernel without steps 3 and 6 (as frow_mprep_kernel is to
+// murty_prep_kernel): no dual is raised, whatever nr.
+template <typename S>
+__global__ __launch_bounds__(PREP_WG) void fcsr_mprep_kernel(const int64_t *indptr, const S *data,
+                                                             const uint64_t *mask, const uint16_t *pre, int NR,
+                                                             int NC, const int32_t *shape, const int32_t *pcol,
+                                                             const double *pv, const int32_t *pp,
+                                                             const uint64_t *forb, int32_t *col, double *du,
+                                                             double *dv, int32_t *kept, uint64_t *forb_out) {
+  using T = double;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ int s_bad, s_kept;
+  const int c = blockIdx.x, b = c / NR, t = c - b * NR;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int nw = murty_words(NC);
+  int nr, n, p;
+  if (!murty_child(shape, pp, b, t, NR, NC, nr, n, p)) {
+    lsap_no_instance<PREP_WG>(col, (T *)nullptr, c, NR, NC, du, dv);
+    if (tid == 0 && kept) kept[c] = 0;
+    if (forb_out)
+      for (int x = tid; x < nw; x += PREP_WG) forb_out[(size_t)c * nw + x] = 0;
+    return;
+  }
+  size_t off = 0;
+  T *u_l;
+  int16_t *r4c_l, *c4r_l, *q_l;  // (mcsr_prep_kernel's list; the queue is not used)
+  uint64_t *closed_l, *closedt_l;
+  MCSR_PREP_LDS(LDS_CARVE, nr, n, nw)
+  (void)q_l;
+  int32_t *claim = (int32_t *)u_l;
+  const int32_t *pcol_b = pcol + (size_t)b * NR;
+  const double *pv_b = pv + (size_t)b * NC;
+  const uint64_t *F_b = forb + (size_t)b * nw;
+  int32_t *col_c = col + (size_t)c * NR;
+  T *u_c = du + (size_t)c * NR, *v_c = dv + (size_t)c * NC;
+  const CsrLoader<1, 1, S> ld{indptr + (size_t)b * NR, data, mask + (size_t)b * NR * nw, pre + (size_t)b * NR * nw,
+                              nw};
+  const T INF = VT<T>::inf();
+  int ct = pcol_b[t];
+  ct = (ct >= 0 && ct < n) ? ct : -1;
+  // F_t's word x
+  auto ft = [&](int x) -> uint64_t {
+    return (t == p ? F_b[x] : 0) | ((ct >= 0 && (ct >> 6) == x) ? 1ull << (ct & 63) : 0ull);
+  };
+  // M_t[i][j], j < n
+  auto at = [&](int i, int j) -> T {
+    const bool masked = (i < t) ? (j != pcol_b[i]) : (((i == t ? closedt_l : closed_l)[j >> 6] >> (j & 63)) & 1) != 0;
+    return masked ? INF : ld.at(i, j);
+  };
+  if (tid == 0) s_bad = s_kept = 0;
+  for (int j = tid; j < n; j += PREP_WG) {  // 1
+    v_c[j] = warm_clean_v(pv_b[j]);
+    claim[j] = INT32_MAX;
+  }
+  __syncthreads();
+  for (int i = tid; i < nr; i += PREP_WG) {  // 2
+    const int j = pcol_b[i];
+    const bool ok = j >= 0 && j < n;
+    c4r_l[i] = ok ? (int16_t)j : (int16_t)-1;
+    if (ok) atomicMin(&claim[j], i);
+  }
+  __syncthreads();
+  for (int j = tid; j < 64 * nw; j += PREP_WG) {  // (a wave holds one word's columns)
+    const int r = (j < n) ? claim[j] : INT32_MAX;
+    if (j < n) r4c_l[j] = (r == INT32_MAX) ? (int16_t)-1 : (int16_t)r;
+    const uint64_t f = __ballot(r < t);
+    if (lane == 0) {
+      closed_l[j >> 6] = f;
+      closedt_l[j >> 6] = f | ft(j >> 6);
+    }
+  }
+  __syncthreads();  // (the claims are read: u_l may be written)
+  for (int i = w; i < nr; i += PREP_WG / WAVE) {  // 4 and 5
+    T m = INF;
+    if (i < t) {
+      const int j = c4r_l[i];
+      if (lane == 0 && j >= 0) m = cert_sub(ld.at(i, j), v_c[j]);
+    } else {
+      const size_t r = (size_t)i * nw;
+      const S *row = ld.data + ld.indptr[i];
+      const int ql = min(lane, nw - 1);  // (a lane past the row's last word holds an empty one)
+      const uint64_t mw = (lane < nw) ? ld.mask[r + ql] : 0;
+      const int pw = ld.pre[r + ql];
+      const uint64_t ow = mw & ~(i == t ? closedt_l : closed_l)[ql];  // the open entries
+      uint64_t words = __ballot(ow != 0);  // the words that hold one
+      while (words) {
+        const int q = __builtin_ctzll(words);
+        words &= words - 1;
+        const uint64_t mq = readlane_u64(mw, q);
+        const uint64_t oq = readlane_u64(ow, q);
+        const int pq = __builtin_amdgcn_readlane(pw, q);
+        if ((oq >> lane) & 1) {  // (rank and address from the unmasked word)
+          const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mq >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mq, 0u));
+          const T x = cert_sub(widen_f64(row[pq + rank]), v_c[64 * q + lane]);
+          m = (x < m) ? x : m;
+        }
+      }
+    }
+    m = wave_min(m);
+    if (lane == 0) {
+      u_l[i] = m;
+      if (!(m < INF)) s_bad = 1;
+      const int j = c4r_l[i];
+      if (j >= 0) {
+        const bool mine = r4c_l[j] == i;  // (only row r4c_l[j] ever writes that slot)
+        if (!(mine && cert_sub(at(i, j), v_c[j]) == m)) {
+          c4r_l[i] = -1;
+          if (mine) r4c_l[j] = -1;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const bool bad = s_bad;
+  int k = 0;
+  for (int i = tid; i < NR; i += PREP_WG) {
+    const int x = (i < nr && !bad) ? c4r_l[i] : -1;
+    col_c[i] = x;
+    k += x >= 0;
+    u_c[i] = (i < nr) ? (bad ? (T)__builtin_nan("") : u_l[i]) : (T)0;
+  }
+  for (int j = tid; j < NC; j += PREP_WG) {
+    if (j >= n) v_c[j] = 0;
+    else if (bad) v_c[j] = __builtin_nan("");
+  }
+  if (forb_out)
+    for (int x = tid; x < nw; x += PREP_WG) forb_out[(size_t)c * nw + x] = ft(x);
+  if (kept) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) k += __shfl_xor(k, o, WAVE);
+    if (lane == 0 && k) atomicAdd(&s_kept, k);
+    __syncthreads();
+    if (tid == 0) kept[c] = s_kept;
+  }
+}
+
+// mcsr_f64_kernel on the padded M_t: one wave, n <= 64, lane j owns column j.
+template <int K, typename S>
+__global__ __launch_bounds__(WAVE) void fcsr_mf64_kernel(const int64_t *indptr, const S *data, const uint64_t *mask,
+                                                         const uint16_t *pre, int NR, int NC, const int32_t *shape,
+                                                         const int32_t *pcol, const int32_t *pp,
+                                                         const uint64_t *forb, int32_t *col, double *cost,
+                                                         double *du, double *dv) {
+  static_assert(K == 1, "the virtual rows' ranks are one ballot");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int c = blockIdx.x, b = c / NR, t = c - b * NR;
+  const int lane = threadIdx.x;
+  int nr, n, p;
+  if (murty_done(shape, pp, b, t, c, NR, NC, nr, n, p, du, cost)) return;
+  size_t off = 0;
+  double *u_l;
+  int16_t *c4r_l;
+  LSAP_F64_LDS(LDS_CARVE, n)
+  const double *v_c = dv + (size_t)c * NC;
+  for (int i = lane; i < nr; i += WAVE) {
+    u_l[i] = du[(size_t)c * NR + i];
+    c4r_l[i] = (int16_t)col[(size_t)c * NR + i];
+  }
+  __syncthreads();
+  const int nw = murty_words(NC);
+  using ML = FreeRowsMaskedCsr<1, K, S>;
+  WithDuals<ML, double> ld{
+      ML{{{indptr + (size_t)b * NR, data, mask + (size_t)b * NR * nw, pre + (size_t)b * NR * nw, nw},
+          pcol + (size_t)b * NR, t, 0u, 0u},
+         nr}};
+  ld.masks(forb + (size_t)b * nw, p, n);
+  ld.dv = dv + (size_t)c * NC;
+  {  // the virtual rows (frow_mf64_kernel's block)
+    bool taken = false;
+    for (int i = 0; i < nr; ++i) taken |= c4r_l[i] == lane;
+    const bool open = lane < n && !(ld.forced & 1u);
+    const double d = open ? 0.0 - v_c[lane] : __builtin_inf();
+    const double m = wave_min(d);
+    const bool f = open && !taken && d == m;
+    const uint64_t bal = __ballot(f);
+    const int rank = __popcll(bal & ((1ull << lane) - 1ull));
+    for (int i = nr + lane; i < n; i += WAVE) {
+      u_l[i] = m;
+      c4r_l[i] = -1;
+    }
+    __syncthreads();
+    if (f && rank < n - nr) c4r_l[nr + rank] = (int16_t)lane;
+    __syncthreads();
+  }
+  int64_t steps = 0;
+  const int st = sap_solve<K, double, true, true>(n, n, ld, u_l, c4r_l, steps);
+  __syncthreads();
+  duals_store_f64<WAVE>(du, dv, u_l, st, c, NR, NC, nr, n);
+  double acc = 0;
+  for (int i = lane; i < NR; i += WAVE) {
+    const bool live = st == 0 && i < nr;
+    const int cidx = live ? c4r_l[i] : -1;
+    col[(size_t)c * NR + i] = cidx;
+    if (live) acc += ld.at(i, cidx);  // (a chosen column is never masked: the CSR's own value)
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, WAVE);  // (warm_f64_kernel's order)
+  if (lane == 0) cost[c] = st == 0 ? acc : __builtin_inf();
+}
+
+// ... and mcsr_f64_mw_kernel.
+template <int NW, int K, typename S, int FB>
+__global__ __launch_bounds__(NW * WAVE) void fcsr_mf64_mw_kernel(const int64_t *indptr, const S *data,
+                                                                 const uint64_t *mask, const uint16_t *pre, int NR,
+                                                                 int NC, const int32_t *shape, const int32_t *pcol,
+                                                                 const int32_t *pp, const uint64_t *forb,
+                                                                 int32_t *col, double *cost, double *du,
+                                                                 double *dv) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ double s_part[NW];
+  __shared__ int s_cnt[NW];
+  constexpr int WG = NW * WAVE;
+  const int c = blockIdx.x, b = c / NR, t = c - b * NR;
+  const int tid = threadIdx.x;
+  int nr, n, p;
+  if (murty_done(shape, pp, b, t, c, NR, NC, nr, n, p, du, cost)) return;
+  size_t off = 0;
+  SolveLdsF64 Sl;
+  LSAP_F64_MW_LDS(LDS_CARVE, n, n, NW, FB)
+  for (int i = tid; i < n; i += WG) {
+    if (i < nr) {
+      Sl.u[i] = du[(size_t)c * NR + i];
+      Sl.c4r[i] = (int16_t)col[(size_t)c * NR + i];
+    }
+    Sl.r4c[i] = -1;
+    Sl.path[i] = -1;
+  }
+  __syncthreads();
+  for (int i = tid; i < nr; i += WG) {
+    const int j = Sl.c4r[i];
+    if (j >= 0) Sl.r4c[j] = (int16_t)i;
+  }
+  __syncthreads();
+  const int nw = murty_words(NC);
+  using ML = FreeRowsMaskedCsr<NW, K, S>;
+  WithDuals<ML, double> ld{
+      ML{{{indptr + (size_t)b * NR, data, mask + (size_t)b * NR * nw, pre + (size_t)b * NR * nw, nw},
+          pcol + (size_t)b * NR, t, 0u, 0u},
+         nr}};
+  ld.masks(forb + (size_t)b * nw, p, n);
+  ld.dv = dv + (size_t)c * NC;
+  // (bit k of ld.forced is column tid + WG k: frow_virtual_rows' skip)
+  frow_virtual_rows<NW>(nr, n, dv + (size_t)c * NC, Sl.u, Sl.c4r, Sl.r4c, s_part, s_cnt, ld.forced);
+  const int st = sap_solve_mw_f64<NW, K, true, FB, true>(n, n, ld, Sl);
+  __syncthreads();
+  duals_store_f64<WG>(du, dv, Sl.u, st, c, NR, NC, nr, n);
+  for (int i = tid; i < NR; i += WG) col[(size_t)c * NR + i] = (st == 0 && i < nr) ? Sl.c4r[i] : -1;
+  if (tid < WAVE) {
+    double acc = 0;
+    for (int i = tid; i < NR; i += WAVE)
+      if (st == 0 && i < nr) acc += ld.at(i, Sl.c4r[i]);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, WAVE);
+    if (tid == 0) cost[c] = st == 0 ? acc : __builtin_inf();
+  }
+}
+
 }  // namespace
 
 // Host side: the same translation unit, so it launches the kernels above by name.

@@ -25,7 +25,7 @@ from .lsap import (check_duals, check_duals_large, check_duals_sparse, check_mat
                    linear_sum_assignment, linear_sum_assignment_duals, linear_sum_assignment_large,
                    linear_sum_assignment_resolve, linear_sum_assignment_sparse,
                    linear_sum_assignment_sparse_resolve, resolve_batched, resolve_batched_free_rows,
-                   resolve_batched_sparse,
+                   resolve_batched_sparse, resolve_batched_sparse_free_rows,
                    kbest_assignments, kbest_batched, murty_children_batched,
                    kbest_assignments_sparse, kbest_batched_sparse, murty_children_batched_sparse,
                    solve_batched, solve_batched_large, solve_batched_sparse, solve_hash, validate_csr)
@@ -40,7 +40,7 @@ __all__ = [
     "linear_sum_assignment_large", "solve_batched_large", "check_duals_large",
     "linear_sum_assignment_resolve", "resolve_batched", "resolve_batched_free_rows",
     "linear_sum_assignment_sparse", "solve_batched_sparse", "densify", "csr_transpose", "validate_csr",
-    "resolve_batched_sparse", "linear_sum_assignment_sparse_resolve",
+    "resolve_batched_sparse", "resolve_batched_sparse_free_rows", "linear_sum_assignment_sparse_resolve",
     "kbest_assignments", "kbest_batched", "murty_children_batched",
     "kbest_assignments_sparse", "kbest_batched_sparse", "murty_children_batched_sparse",
     "check_duals_sparse", "maximum_matching_sparse", "check_matching_sparse", "maximum_bipartite_matching",

@@ -190,6 +190,11 @@ for _suf in ("f64", "f32"):
     # stream
     SIGNATURES["lsap_kbest_csr_" + _suf] = (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, ctypes.c_size_t, _U,
                                                  _P])
+    # free rows on the CSR: the warm start with kept [B x 2] and theta after kept; the k-best entries' argument lists
+    SIGNATURES["lsap_warm_fr_csr_" + _suf] = (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P,
+                                                   ctypes.c_size_t, _U, _P])
+    SIGNATURES["lsap_murty_children_fr_csr_" + _suf] = SIGNATURES["lsap_murty_children_csr_" + _suf]
+    SIGNATURES["lsap_kbest_fr_csr_" + _suf] = SIGNATURES["lsap_kbest_csr_" + _suf]
 SIGNATURES["lsap_kbest_work_bytes"] = (ctypes.c_size_t, [_I, _I, _I, _I])
 SIGNATURES["lsap_kbest_csr_work_bytes"] = (ctypes.c_size_t, [_I, _I, _I, _I])
 

@@ -1069,9 +1069,86 @@ def resolve_batched_sparse(crow, col_indices, values, shape, col, u, v, with_cos
     return col_w, cost, u_w, v_w, kept
 
 
-def linear_sum_assignment_sparse_resolve(A, col_ind, u, v, maximize: bool = False, device: int | str = 0):
+def resolve_batched_sparse_free_rows(crow, col_indices, values, shape, col, u, v, with_cost: bool = True,
+                                     flags: int = 0, shapes=None, maximize: bool = False, validate: bool = True):
+    """resolve_batched_sparse for wide instances (nr < nc), solved as the padded
+    square problem whose nc - nr extra rows cost 0 everywhere (the
+    lsap_warm_fr_csr_ entries) -> (col, cost, u, v, kept int32
+    [B], kept_free int32 [B], theta float64 [B]): what resolve_batched_free_rows
+    returns for the densification (densify) with the same shapes and the same
+    previous col and v -- the same col, kept and kept_free, the same bits in
+    cost, u, v and theta equal by value (a zero may carry the other sign) --
+    without building it.
+
+    The extra rows are never stored and read no entry of the CSR; they cannot
+    make an instance infeasible, and an instance without a perfect matching of
+    its real rows gets -1, cost 0, NaN duals and NaN theta.  The batch,
+    `shapes`, `validate`, maximize and the reading of the previous state are
+    resolve_batched_sparse's: a previous pair that is no longer stored is
+    dropped, a new entry is an edge.  (nr_b - kept) + (nc_b - nr_b - kept_free)
+    Dijkstras run.  u and v are the padded problem's duals as the solver left
+    them (no shift): a free column holds v == theta up to rounding and not 0, so
+    they are the input of this function's next call and not of
+    resolve_batched_sparse.  A square instance gets what resolve_batched_sparse
+    returns.  flags: SH_FLAG_BUILD_ONLY returns the start state (the kept real
+    pairs, u, v, both counts, its theta; cost 0).
+
+    When it pays (measured on the MI355X, 64 instances, band patterns at 1 %,
+    5 % and 40 % density): when nearly every column holds a row
+    and few rows changed.  One redrawn row re-solves 5.4x to 9.3x faster than
+    resolve_batched_sparse at 250 x 256, 12x to 20x at 1018 x 1024 and 5.0x to
+    6.5x at 1900 x 2000 (about the same over a cold solve_batched_sparse, which
+    resolve_batched_sparse does not beat there); 1 % of the rows: 3.8x to 6.7x,
+    4.5x to 4.8x and 1.1x to 1.3x; 10 %: 1.2x to 1.5x up to 1024 columns, but
+    0.2x to 0.3x at 1900 x 2000; with every row redrawn it loses everywhere
+    (0.55x to 0.8x up to 1024 columns, 0.08x to 0.11x at 2000), and an
+    unchanged batch costs 2 % to 6 % more than resolve_batched_sparse.  With
+    few rows on many columns (64 x 1024) it loses from the first row, 0.02x to
+    0.45x of resolve_batched_sparse: use that.  Against
+    resolve_batched_free_rows on a densification built beforehand it takes
+    0.94x to 1.15x the time at 1 % density and 1.0x to 1.7x at 5 % and 40 % once
+    a row changed.
+    """
+    crow, col_indices, values, shape, p = _sparse_batch(crow, col_indices, values, shape, shapes, validate)
+    check_solution(p, values.dtype, col, u, v)
+    dev = values.device
+    if p.empty:
+        z = torch.zeros(p.B, dtype=torch.int32, device=dev)
+        return empty_result(p, with_cost, True, p.ddt, dev) + (z, z.clone(),
+                                                               torch.zeros(p.B, dtype=torch.float64, device=dev))
+    require_gpu()
+    crow, col_indices, values, shape_dev = _sparse_operands(p, crow, col_indices, values, maximize)
+    # the C entry works in place on col and v: it gets copies, and only u and the cost are new
+    col_w = narrow_col(col).clone().contiguous()
+    v_w = (-v if maximize else v.clone()).contiguous()
+    u_w = torch.empty((p.B, p.NR), dtype=torch.float64, device=dev)
+    build_only = bool(flags & _lib.SH_FLAG_BUILD_ONLY)
+    cost = (torch.zeros if build_only else torch.empty)(p.B, dtype=torch.float64, device=dev) if with_cost else None
+    kept = torch.empty((p.B, 2), dtype=torch.int32, device=dev)
+    theta = torch.empty(p.B, dtype=torch.float64, device=dev)
+    L = _lib.lib()
+    nbytes = int(L.lsap_csr_work_bytes(p.NR, p.NC, p.B))
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    nnz = values.numel()
+    rc = getattr(L, "lsap_warm_fr_csr_" + DTYPE_SUFFIX[values.dtype])(
+        _p(crow), _p(col_indices) if nnz else None, _p(values) if nnz else None, p.NR, p.NC, p.B, _p(shape_dev),
+        _p(col_w), _p(cost), _p(u_w), _p(v_w), _p(kept), _p(theta), _p(work), nbytes,
+        _lib.SH_COMPAT_TIEBREAK | flags, current_stream_handle(dev))
+    _lib.check(rc, "lsap_warm_fr_csr")
+    if maximize:
+        cost = -cost if cost is not None else None
+        u_w, v_w, theta = -u_w, -v_w, -theta
+    return col_w, cost, u_w, v_w, kept[:, 0].contiguous(), kept[:, 1].contiguous(), theta
+
+
+def linear_sum_assignment_sparse_resolve(A, col_ind, u, v, maximize: bool = False, device: int | str = 0,
+                                         free_rows: bool = False):
     """linear_sum_assignment_sparse(duals=True) started from a previous solution
     of a nearby matrix -> (row_ind, col_ind, u, v).
+
+    free_rows=True solves a rectangular matrix as its padded square problem
+    (resolve_batched_sparse_free_rows, whose duals it returns: the padded
+    problem's, the input of the next call with free_rows=True).
 
     A is linear_sum_assignment_sparse's; col_ind [nr], u [nr] and v [nc] are
     linear_sum_assignment_resolve's, the duals float64 numpy arrays (TypeError
@@ -1103,11 +1180,12 @@ def linear_sum_assignment_sparse_resolve(A, col_ind, u, v, maximize: bool = Fals
         indptr, indices, data, (nr, nc) = csr_transpose(indptr, indices, data, (nr, nc))
         col0, bad = invert_col(col0, nr)
         col0[bad] = -1
-    col, _, ru, rv, _ = resolve_batched_sparse(
+    resolve = resolve_batched_sparse_free_rows if free_rows else resolve_batched_sparse
+    col, _, ru, rv = resolve(
         torch.from_numpy(np.ascontiguousarray(indptr, dtype=np.int64)).to(dev),
         torch.from_numpy(np.ascontiguousarray(indices, dtype=np.int32)).to(dev),
         torch.from_numpy(np.ascontiguousarray(data)).to(dev), (1, nr, nc), col0.to(dev),
-        torch.zeros((1, nr), dtype=torch.float64, device=dev), v0.to(dev), with_cost=False, maximize=maximize)
+        torch.zeros((1, nr), dtype=torch.float64, device=dev), v0.to(dev), with_cost=False, maximize=maximize)[:4]
     return single_result(col, tall, ru, rv)  # (the duals come back in the matrix's own signs)
 
 
@@ -1117,7 +1195,7 @@ def linear_sum_assignment_sparse_resolve(A, col_ind, u, v, maximize: bool = Fals
 # dense matrix.
 # ---------------------------------------------------------------------------
 def murty_children_batched_sparse(crow, col_indices, values, shape, col, v, p, forb, shapes=None,
-                                  validate: bool = True):
+                                  validate: bool = True, free_rows: bool = False):
     """murty_children_batched on sparse costs (the lsap_murty_children_csr_
     entries) -> (col int32 [B, NR, NR], cost float64 [B, NR], u [B, NR, NR],
     v [B, NR, NC], kept int32 [B, NR]): what murty_children_batched returns for
@@ -1129,7 +1207,12 @@ def murty_children_batched_sparse(crow, col_indices, values, shape, col, v, p, f
     <= SH_MAX_N; the node (col, v, p, forb) is murty_children_batched's: read as
     data and not modified.  A forced row whose column is not stored makes the
     child infeasible: col -1 and cost +inf, as for a child that does not
-    exist."""
+    exist.
+
+    free_rows=True (the lsap_murty_children_fr_csr_ entries):
+    what murty_children_batched(free_rows=True) returns for the densification;
+    every child is the free-rows warm start of the padded M_t, whose virtual
+    rows read no entry of the CSR."""
     crow, col_indices, values, shape, p_ = _sparse_batch(crow, col_indices, values, shape, shapes, validate,
                                                          limit=_lib.SH_MAX_N)
     B, NR, NC = shape
@@ -1163,16 +1246,17 @@ def murty_children_batched_sparse(crow, col_indices, values, shape, col, v, p, f
     nbytes = int(L.lsap_csr_work_bytes(NR, NC, B))
     work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     nnz = values.numel()
-    rc = getattr(L, "lsap_murty_children_csr_" + DTYPE_SUFFIX[values.dtype])(
+    rc = getattr(L, ("lsap_murty_children_fr_csr_" if free_rows else "lsap_murty_children_csr_")
+                 + DTYPE_SUFFIX[values.dtype])(
         _p(crow), _p(col_indices) if nnz else None, _p(values) if nnz else None, NR, NC, B, _p(shape_dev), _p(col0),
         _p(v0), _p(p0), _p(f0), _p(ccol), _p(cost), _p(cu), _p(cv), _p(kept), _p(work), nbytes,
         _lib.SH_COMPAT_TIEBREAK, current_stream_handle(dev))
-    _lib.check(rc, "lsap_murty_children_csr")
+    _lib.check(rc, "lsap_murty_children_fr_csr" if free_rows else "lsap_murty_children_csr")
     return ccol, cost, cu, cv, kept
 
 
 def kbest_batched_sparse(crow, col_indices=None, values=None, shape=None, k: int = 1, shapes=None,
-                         maximize: bool = False, validate: bool = True):
+                         maximize: bool = False, validate: bool = True, free_rows: bool = False):
     """kbest_batched on sparse costs, a missing entry being a forbidden pair
     (the lsap_kbest_csr_ entries) -> (cols int32 [B, k, NR], costs float64
     [B, k], count int32 [B]): cols, costs and count of kbest_batched on the
@@ -1185,7 +1269,22 @@ def kbest_batched_sparse(crow, col_indices=None, values=None, shape=None, k: int
     of crow), with 1 <= NR <= NC <= SH_MAX_N: ValueError for a tall batch, for a
     k that is no integer >= 1 and for a pool that does not fit.  One call
     launches 3 k kernels whatever the data, allocates its pool once and never
-    synchronises."""
+    synchronises.
+
+    free_rows=True (the lsap_kbest_fr_csr_ entries): cols, costs
+    and count of kbest_batched(free_rows=True) on the densification.  Every
+    child is computed on the padded square problem; the ranks have the default
+    mode's costs (equal bits wherever every sum is exact), and among
+    assignments of equal cost the order and the choice may differ.  The same
+    pool and the same 3 k launches.  When it pays (measured on the MI355X, 5 %
+    density, k = 10, 1 and 64 instances): on wide instances a few
+    rows short of square a child runs one search from 250 x 256 up (1.8 to 3.0
+    for the root's children at 60 x 64) instead of 2 to 65, and a call
+    takes 1.4x to 1.65x less time at 60 x 64, 2.5x to 2.6x less at 250 x 256
+    and 4.9x to 5.8x less at 1018 x 1024; it stays 1.14x to 1.25x behind
+    kbest_batched(free_rows=True) on a densification built beforehand.  Not
+    measured with far fewer rows than columns, where the warm start's records
+    say free rows loses."""
     crow, col_indices, values, shape, p = _sparse_batch(crow, col_indices, values, shape, shapes, validate,
                                                         limit=_lib.SH_MAX_N)
     if int(k) != k or k < 1:
@@ -1208,16 +1307,16 @@ def kbest_batched_sparse(crow, col_indices=None, values=None, shape=None, k: int
     costs = torch.empty((B, k), dtype=torch.float64, device=dev)
     count = torch.empty(B, dtype=torch.int32, device=dev)
     nnz = values.numel()
-    rc = getattr(L, "lsap_kbest_csr_" + DTYPE_SUFFIX[values.dtype])(
+    rc = getattr(L, ("lsap_kbest_fr_csr_" if free_rows else "lsap_kbest_csr_") + DTYPE_SUFFIX[values.dtype])(
         _p(crow), _p(col_indices) if nnz else None, _p(values) if nnz else None, NR, NC, B, _p(shape_dev), k,
         _p(cols), _p(costs), _p(count), _p(work), nbytes, _lib.SH_COMPAT_TIEBREAK, current_stream_handle(dev))
-    _lib.check(rc, "lsap_kbest_csr")
+    _lib.check(rc, "lsap_kbest_fr_csr" if free_rows else "lsap_kbest_csr")
     if maximize:
         costs = -costs
     return cols, costs, count
 
 
-def kbest_assignments_sparse(A, k: int, maximize: bool = False, device: int | str = 0):
+def kbest_assignments_sparse(A, k: int, maximize: bool = False, device: int | str = 0, free_rows: bool = False):
     """kbest_assignments for one sparse matrix whose missing entries are
     forbidden pairs -> (col_inds int64 [m, nr], costs float64 [m]), m <= k the
     number of assignments that exist, best first: those of kbest_assignments on
@@ -1225,7 +1324,7 @@ def kbest_assignments_sparse(A, k: int, maximize: bool = False, device: int | st
     longer side; a tall matrix is solved as its transpose (csr_transpose) and
     col_inds has -1 for the rows left out.  A stored +inf (under maximize:
     -inf) is a missing entry; NaN and -inf (under maximize: +inf) raise
-    ValueError."""
+    ValueError.  free_rows is kbest_batched_sparse's."""
     indptr, indices, data, (nr, nc) = _csr_of(A)
     if int(k) != k or k < 1:
         raise ValueError(f"k must be an integer >= 1, got {k!r}")
@@ -1247,7 +1346,7 @@ def kbest_assignments_sparse(A, k: int, maximize: bool = False, device: int | st
     cols, costs, count = kbest_batched_sparse(
         torch.from_numpy(np.ascontiguousarray(indptr, dtype=np.int64)).to(dev),
         torch.from_numpy(np.ascontiguousarray(indices, dtype=np.int32)).to(dev),
-        torch.from_numpy(np.ascontiguousarray(data)).to(dev), shape=(1, nr, nc), k=int(k))
+        torch.from_numpy(np.ascontiguousarray(data)).to(dev), shape=(1, nr, nc), k=int(k), free_rows=free_rows)
     if maximize:
         costs = -costs
     if tall:
